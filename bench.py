@@ -2,6 +2,7 @@
 """Headline benchmark: PerceiverIO forward on MI355X (BASELINE.json configs[1] by default).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config imagenet|language|flow|multimodal]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one full forward of the task model on synthetic inputs already resident in HBM.  Default config
 `imagenet`: ClassificationPerceiver (PrepType.FOURIER_POS_CONVNET), B = 32 per GPU:
@@ -18,7 +19,11 @@ line); under torch.distributed.run it is one rank per GPU over RCCL.  imagenet /
 batch (weak scaling; imagenet all-gathers its logits, the path's only collective), flow (B = 1 < world) shards the
 182 528 decoder queries and all-gathers the flow field (strong scaling).
 
-Rank 0 prints ONE JSON line.  Extra objects:
+A plain run sets up, warms up (including the untimed graph / eager launch calibration that picks the headline's launch
+mode), times K steps, writes the last timed step's outputs if --dump-outputs DIR is given (DIR/<name>.npy, float32;
+see dump_outputs) and prints the result line.  Everything else it measures or checks runs only with --full.
+
+Rank 0 prints ONE JSON line.  Extra objects (--full only):
   roofline     -- the dominant kernel: ALGORITHMIC flops / device time measured with HIP events around every launch of
                   that kernel class in an instrumented repeat of the step; `traffic` = HBM bytes per launch from the
                   committed PMC profile (profiles/traffic.json)
@@ -298,6 +303,27 @@ def parity_check(name, model, params, dev, policy):
     return out
 
 
+DUMP_NAMES = {"imagenet": "logits", "language": "logits", "flow": "flow"}     # (multimodal: the output dict's keys)
+DUMP_MAX_ELEMS = 4 << 20     # per array: 16 MB in float32, at most three arrays per config (64 MB in all)
+
+
+def dump_outputs(dirname, out, name):
+    """--dump-outputs: the arrays the timed step returned (the caller's view of the path) as DIR/<name>.npy in float32.
+    An array of more than DUMP_MAX_ELEMS elements (language logits: 53.7 M) is written as a fixed sample: its flattened
+    elements at the sorted unique positions of DUMP_MAX_ELEMS draws from a generator seeded 0, so two runs with the same
+    arguments write the same positions."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = out if isinstance(out, dict) else {DUMP_NAMES.get(name, "output"): out}
+    for key, t in arrays.items():
+        if t is None:
+            continue
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.unique(np.random.default_rng(0).integers(0, a.size, DUMP_MAX_ELEMS))]
+        np.save(os.path.join(dirname, key + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def cpu_quota():
     """CPUs this process may actually use at once: the cgroup CPU quota (v2 cpu.max / v1 cfs_quota_us) if one is set.
     On a shared host the affinity mask can show every core (256) while the container's share is 16: a thread pool
@@ -474,6 +500,8 @@ def main_stub(args):
         t = torch.tensor([el], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, "stub")
     # every rank holds every rank's rows, in rank order
     ok = tuple(out.shape) == (B * world, 10)
     if world > 1:
@@ -496,6 +524,44 @@ def main_stub(args):
         dist.destroy_process_group()
 
 
+def kernel_roofline(name, ms, fl, by, ln, nprof):
+    """--full: per-kernel-class figures of the instrumented repeat (pio_prof_*) and the roofline object of the dominant
+    MFMA kernel class."""
+    NCLS = len(ms)
+    names = ["gemm_nt_256", "gemm_nt_128_batched", "layernorm_cast", "softmax", "pack", "flash_attn",
+             "gemm_nt_128_flat", "gemm_nt_stream", "gemm_nt_wide"]
+    kernels = {}
+    for i, nm in enumerate(names):
+        if ln[i]:
+            kernels[nm] = {"launches_per_step": ln[i] // nprof, "ms_per_step": ms[i] / nprof,
+                           "avg_us": ms[i] / ln[i] * 1e3,
+                           "algo_tflops": (fl[i] / (ms[i] * 1e-3) / 1e12) if fl[i] else None,
+                           "algo_gbps": by[i] / (ms[i] * 1e-3) / 1e9}
+    # the dominant kernel: the MFMA kernel class with the most device time per step
+    dom = max((i for i in range(NCLS) if ln[i] and fl[i]), key=lambda i: ms[i])
+    g = kernels[names[dom]]
+    # HBM traffic of that kernel per launch: PMC counters (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 passes of
+    # this same command, gfx950 correction of MI355X_MICROARCH.md) condensed into profiles/traffic.json
+    traffic = None
+    if name == "imagenet":
+        try:
+            with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
+                traffic = json.load(f)["pio::" + names[dom]]["bytes_per_launch"]
+        except Exception:  # noqa: BLE001  (no committed profile yet)
+            traffic = None
+    what = {"gemm_nt_wide": "persistent 256x256-tile GEMM: the weight GEMMs of the latent stack (fused q|k|v, out, fc1 "
+                            "(GELU), fc2 with the LayerNorms folded into them) and the decoder projections",
+            "gemm_nt_stream": "persistent 256x128-tile streaming GEMM", "flash_attn": "fused attention",
+            "gemm_nt_256": "256x256-tile GEMM", "gemm_nt_128_flat": "128x128-tile GEMM",
+            "gemm_nt_128_batched": "batched 128x128-tile GEMM (materialised attention products)"}.get(names[dom], "")
+    roofline = {"kernel": f"pio::{names[dom]} ({what})",
+                "bound": "mfma", "achieved": g["algo_tflops"], "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": g["algo_tflops"] / MFMA_PEAK_TFLOPS, "traffic": traffic,
+                "avg_launch_us": g["avg_us"], "launches_per_step": g["launches_per_step"],
+                "algo_flops_per_launch": fl[dom] / ln[dom], "algo_bytes_per_launch": by[dom] / ln[dom]}
+    return kernels, roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -510,7 +576,14 @@ def main():
     ap.add_argument("--hot-path-only", action="store_true", help="imagenet: time encoder+decoder on a resident [B,3136,322] array")
     ap.add_argument("--launch", choices=["graph", "eager"], default=None,
                     help="replay the step's launches from ONE HIP graph (default) or launch them one by one")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity gate, the other launch mode, the per-kernel roofline, the stage and policy "
+                         "legs and the CPU baseline (--no-parity, --no-extras and --cpu-sample trim them)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # PIO_BENCH_REHEARSE=1 (1-GPU box): go through the same spawn + multi-rank code with every rank on cuda:0 and the
     # gloo backend (RCCL refuses two ranks on one device) -- a rehearsal of the control flow, not a measurement
@@ -583,7 +656,7 @@ def main():
         forward = model
 
     parity = None
-    if not args.no_parity and rank == 0:
+    if args.full and not args.no_parity and rank == 0:
         parity = parity_check(name, model, params, dev, policy)
         if name == "imagenet":
             fold_on = lib.pio_ln_fold_enable(1)            # (returns the previous setting: read it and put it back)
@@ -652,13 +725,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    last = {}
+
     def timed_region(nwarm, nsteps, eager=False):
         for _ in range(nwarm):
             step(eager)
         sync()
         t0 = time.perf_counter()
         for _ in range(nsteps):
-            step(eager)
+            last["out"] = step(eager)
         sync()
         el = time.perf_counter() - t0
         if world > 1:
@@ -693,32 +768,36 @@ def main():
                 launch = "eager"
         use_graph = graph is not None and launch == "graph"
         elapsed = timed_region(warmup, steps, eager=not use_graph)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last["out"], name)     # (before anything else replays into graph_out)
         if graph is not None:
             # the fp16 range guard of the replayed steps: the word the fold's producer GEMMs report into
             flag_t = P.runtime.last_range_flag(dev)
             assert flag_t is None or int(flag_t.item()) == 0, "range guard fired inside the replayed steps"
+        if graph is not None and args.full:
             n_e = max(3, steps // 2)
             el_e = timed_region(2, n_e, eager=use_graph)   # the OTHER launch mode, for the record
             eager_line = {"launch": "eager" if use_graph else "graph",
                           "value": (B if name == "flow" else world * B) * n_e / el_e, "unit": "samples/s",
                           "ms_per_step": el_e / n_e * 1e3, "steps": n_e}
 
-        # ---- instrumented repeat: HIP events around every kernel launch (same stream), per kernel class ----
-        nprof = 1 if heavy else max(1, min(3, steps))
-        L.check(lib.pio_prof_begin(16384 * nprof), "pio_prof_begin")
-        for _ in range(nprof):
-            step(eager=True)                               # (the recorder lives in the launch path: no graph replay)
-        ms = (C.c_double * NCLS)()
-        fl = (C.c_double * NCLS)()
-        by = (C.c_double * NCLS)()
-        ln = (C.c_int64 * NCLS)()
-        nrec = lib.pio_prof_end(ms, fl, by, ln)
-        assert nrec > 0, nrec
+        if args.full:
+            # ---- instrumented repeat: HIP events around every kernel launch (same stream), per kernel class ----
+            nprof = 1 if heavy else max(1, min(3, steps))
+            L.check(lib.pio_prof_begin(16384 * nprof), "pio_prof_begin")
+            for _ in range(nprof):
+                step(eager=True)                           # (the recorder lives in the launch path: no graph replay)
+            ms = (C.c_double * NCLS)()
+            fl = (C.c_double * NCLS)()
+            by = (C.c_double * NCLS)()
+            ln = (C.c_int64 * NCLS)()
+            nrec = lib.pio_prof_end(ms, fl, by, ln)
+            assert nrec > 0, nrec
 
         stages = None
         class_default = None
         robust = None
-        if name == "imagenet" and not args.no_extras:
+        if args.full and name == "imagenet" and not args.no_extras:
             # ---- per-stage timing of the three hot-path stages (HIP events on the launch stream) ----
             pio = model.perceiver
             from perceiverio_pytorch_amd.models import split_policy3
@@ -790,38 +869,6 @@ def main():
     ms_per_step = elapsed / steps * 1e3
     samples_per_step = B if (name == "flow") else world * B
     value = samples_per_step * steps / elapsed
-    names = ["gemm_nt_256", "gemm_nt_128_batched", "layernorm_cast", "softmax", "pack", "flash_attn",
-             "gemm_nt_128_flat", "gemm_nt_stream", "gemm_nt_wide"]
-    kernels = {}
-    for i, nm in enumerate(names):
-        if ln[i]:
-            kernels[nm] = {"launches_per_step": ln[i] // nprof, "ms_per_step": ms[i] / nprof,
-                           "avg_us": ms[i] / ln[i] * 1e3,
-                           "algo_tflops": (fl[i] / (ms[i] * 1e-3) / 1e12) if fl[i] else None,
-                           "algo_gbps": by[i] / (ms[i] * 1e-3) / 1e9}
-    # the dominant kernel: the MFMA kernel class with the most device time per step
-    dom = max((i for i in range(NCLS) if ln[i] and fl[i]), key=lambda i: ms[i])
-    g = kernels[names[dom]]
-    # HBM traffic of that kernel per launch: PMC counters (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 passes of
-    # this same command, gfx950 correction of MI355X_MICROARCH.md) condensed into profiles/traffic.json
-    traffic = None
-    if name == "imagenet":
-        try:
-            with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
-                traffic = json.load(f)["pio::" + names[dom]]["bytes_per_launch"]
-        except Exception:  # noqa: BLE001  (no committed profile yet)
-            traffic = None
-    what = {"gemm_nt_wide": "persistent 256x256-tile GEMM: the weight GEMMs of the latent stack (fused q|k|v, out, fc1 "
-                            "(GELU), fc2 with the LayerNorms folded into them) and the decoder projections",
-            "gemm_nt_stream": "persistent 256x128-tile streaming GEMM", "flash_attn": "fused attention",
-            "gemm_nt_256": "256x256-tile GEMM", "gemm_nt_128_flat": "128x128-tile GEMM",
-            "gemm_nt_128_batched": "batched 128x128-tile GEMM (materialised attention products)"}.get(names[dom], "")
-    roofline = {"kernel": f"pio::{names[dom]} ({what})",
-                "bound": "mfma", "achieved": g["algo_tflops"], "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": g["algo_tflops"] / MFMA_PEAK_TFLOPS, "traffic": traffic,
-                "avg_launch_us": g["avg_us"], "launches_per_step": g["launches_per_step"],
-                "algo_flops_per_launch": fl[dom] / ln[dom], "algo_bytes_per_launch": by[dom] / ln[dom]}
-
     workload = cfg["workload"]
     if args.hot_path_only:
         workload = "hot path only (encoder + decoder + final Linear) on a resident [B,3136,322] array"
@@ -842,8 +889,10 @@ def main():
         "per_gpu": value / world,
         "model_algo_tflops": value * cfg["gflop"] / 1e3,
         "model_mfma_frac": value / world * cfg["gflop"] / 1e3 / MFMA_PEAK_TFLOPS,
-        "roofline": roofline, "kernels": kernels, "parity": parity,
     }
+    if args.full:
+        kernels, roofline = kernel_roofline(name, ms, fl, by, ln, nprof)
+        out.update(roofline=roofline, kernels=kernels, parity=parity)
     if eager_line is not None:
         out["other_launch_mode"] = eager_line
     if calibration is not None:
@@ -859,7 +908,7 @@ def main():
         out["single_sweep_policy"] = robust
     if plain16 is not None:
         out["plain_fp16_policy"] = plain16       # one image per shared weight (round-to-nearest): same launches
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         nb = args.cpu_sample if args.cpu_sample is not None else {"imagenet": 8, "language": 4, "flow": 1,
                                                                   "multimodal": 1}[name]
         if nb > 0:

@@ -3,7 +3,7 @@
 OUT=gpurun_out/r4_bench_all
 mkdir -p $OUT
 for c in imagenet language flow multimodal; do
-  echo "== bench $c"; timeout -k 10 500 python bench.py --config $c --cpu-sample 0 > $OUT/$c.json 2> $OUT/$c.err || { tail -3 $OUT/$c.err | cut -c1-600; }
+  echo "== bench $c"; timeout -k 10 500 python bench.py --full --config $c --cpu-sample 0 > $OUT/$c.json 2> $OUT/$c.err || { tail -3 $OUT/$c.err | cut -c1-600; }
 done
 python - <<'PY'
 import json

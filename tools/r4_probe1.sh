@@ -5,7 +5,7 @@ set -o pipefail
 OUT=gpurun_out/r4_probe1
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-BENCH="bench.py --steps 10 --warmup 3 --cpu-sample 0 --no-parity --no-extras --launch eager"
+BENCH="bench.py --full --steps 10 --warmup 3 --cpu-sample 0 --no-parity --no-extras --launch eager"
 for v in 0 1; do
   export PIO_FOLD_INPLACE=$v
   echo "== trace inplace=$v"; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace$v -- python $BENCH > $OUT/trace$v.log 2>&1 || exit 1
