@@ -433,6 +433,15 @@ int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const vo
     if (debug)
         fprintf(stderr, "[pio] fused attention B=%d H=%d Tq=%d Tk=%d dkp=%d dvp=%d v_rowmajor=%d wide=%d variant=%d\n", B, H,
                 Tq, Tk, dkp, dvp, (int)v_rowmajor, (int)wide, variant);
+    // key split over two wave groups (KS = 2): when the launch offers at most one 128-row workgroup per CU
+    static const bool ksplit_on = [] {
+        const char *e = getenv("PIO_FLASH_KSPLIT");
+        return !e || atoi(e) != 0;
+    }();
+    const bool ksplit = ksplit_on && v_rowmajor && !wide && Tk >= 256 && (Tk % 128) == 0 &&
+                        (int64_t)B * H * nqt <= cu_budget();
+    // (four key parts = 16 waves per workgroup, four per SIMD: the narrow heads, whose waves need < 128 registers)
+    const bool ksplit4 = ksplit && dkp <= 64 && dvp <= 64 && Tk >= 1024 && (Tk % 256) == 0;
 #ifdef PIO_EXPERIMENTS
     const bool pipe = variant == 1, stagger = variant == 2;
     if (v_rowmajor && Tq >= 256 && Tk % 128 == 0 && pipe && o_rows16) {
@@ -446,15 +455,6 @@ int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const vo
         else hipLaunchKernelGGL((flash_attn_stag_kernel<PIO_DT_BF16>), grid, block, 0, s, p);
     } else
 #endif
-    // key split over two wave groups (KS = 2): when the launch offers at most one 128-row workgroup per CU
-    static const bool ksplit_on = [] {
-        const char *e = getenv("PIO_FLASH_KSPLIT");
-        return !e || atoi(e) != 0;
-    }();
-    const bool ksplit = ksplit_on && v_rowmajor && !wide && Tk >= 256 && (Tk % 128) == 0 &&
-                        (int64_t)B * H * nqt <= cu_budget();
-    // (four key parts = 16 waves per workgroup, four per SIMD: the narrow heads, whose waves need < 128 registers)
-    const bool ksplit4 = ksplit && dkp <= 64 && dvp <= 64 && Tk >= 1024 && (Tk % 256) == 0;
     if (ksplit4) {
         block = dim3(1024, 1, 1);
         if (dkp == 64) {

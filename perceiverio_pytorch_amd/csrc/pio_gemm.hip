@@ -33,7 +33,7 @@ __device__ int g128_block;
 #define G128_STAMP(i)
 #endif
 
-constexpr int BM = 128, BN = 128, BK = 64;   // the default tile (launcher arithmetic); the kernel is templated on TM x TN
+constexpr int BK = 64;   // (the default tile BM x BN: pio_gemm_route.h; the kernel is templated on TM x TN)
 
 // KIND only tags the instantiation (0: one flat [rows,K]x[N,K] linear, 1: batched attention product) so that
 // profilers report the two uses under different kernel names.
@@ -516,14 +516,6 @@ static int &gemm_kernel_choice() {
     }();
     return choice;
 }
-// A/B switch for benchmarks: env PIO_GEMM_WIDE_R=1 sends residual GEMMs to the wide kernel as well
-static bool wide_residual() {
-    static const bool on = [] {
-        const char *e = getenv("PIO_GEMM_WIDE_R");
-        return e && atoi(e) != 0;
-    }();
-    return on;
-}
 int gemm_kernel_override(int which) {
     int &c = gemm_kernel_choice();
     const int prev = c;
@@ -546,84 +538,11 @@ static void gemm_log(const char *kernel, const pio_gemm_t &g, const GemmParams &
             g.ln_part ? "consumer" : (g.row_part ? "producer" : "-"), p.n_store);
 }
 
-int gemm_nt_launch(const pio_gemm_t &g, hipStream_t s) {
-    if (!g.A || !g.B) return PIO_E_ARG;
-    if (!g.C && !(g.X16 && g.X16_lo && g.out_f32)) return PIO_E_ARG;  // (fp32 C is optional beside a 16-bit pair)
-    if (g.M <= 0 || g.N <= 0 || g.K <= 0 || g.batch <= 0 || g.nh <= 0) return PIO_E_SHAPE;
-    if (g.K % 8) return PIO_E_SHAPE;
-    if (g.batch % g.nh) return PIO_E_SHAPE;
-    if ((g.lda % 8) || (g.ldb % 8) || (g.sAb % 8) || (g.sAh % 8) || (g.sBb % 8) || (g.sBh % 8)) return PIO_E_ALIGN;
-    if (((uintptr_t)g.A & 15) || ((uintptr_t)g.B & 15) || ((uintptr_t)g.A_lo & 15) || ((uintptr_t)g.B_lo & 15) ||
-        ((uintptr_t)g.C_lo & 7))
-        return PIO_E_ALIGN;
-    if (g.batch > 65535) return PIO_E_SHAPE;
-    if (g.bias_mode && !g.bias) return PIO_E_ARG;
-    if (g.dtype != PIO_DT_F16 && g.dtype != PIO_DT_BF16) return PIO_E_ARG;
-
-    GemmParams p;
-    p.A = g.A; p.B = g.B; p.C = g.C;
-    p.C_lo = g.out_f32 ? nullptr : g.C_lo;
-    // K sweeps: (A,B) [+ (A,B_lo)] [+ (A_lo,B)]  -- the dropped A_lo*B_lo term is ~2^-22 relative
-    p.npass = 1;
-    p.dA1 = p.dB1 = p.dA2 = p.dB2 = 0;
-    auto delta = [](const void *lo, const void *hi) { return (int64_t)(((intptr_t)lo - (intptr_t)hi) / 2); };
-    if (g.B_lo) { p.dB1 = delta(g.B_lo, g.B); p.npass = 2; }
-    if (g.A_lo) {
-        if (p.npass == 1) { p.dA1 = delta(g.A_lo, g.A); p.npass = 2; }
-        else              { p.dA2 = delta(g.A_lo, g.A); p.npass = 3; }
-    }
-    p.M = g.M; p.N = g.N; p.K = g.K;
-    p.lda = g.lda; p.ldb = g.ldb; p.ldc = g.ldc;
-    p.nh = g.nh;
-    p.sAb = g.sAb; p.sAh = g.sAh; p.sBb = g.sBb; p.sBh = g.sBh; p.sCb = g.sCb; p.sCh = g.sCh;
-    p.bias = g.bias; p.bias_mode = g.bias_mode; p.act = g.act; p.alpha = g.alpha;
-    p.R = g.R; p.ldr = g.ldr; p.r_stride_b = g.r_stride_b; p.r_rows = g.r_rows_per_batch;
-    // a residual whose batches are contiguous ([B, T, C] with stride_b == T * ld) is one flat [B*T, C] matrix
-    if (p.R && p.r_rows > 0 && p.r_stride_b == (int64_t)p.r_rows * p.ldr) p.r_rows = 0;
-    p.out_f32 = g.out_f32;
-    p.X16 = g.X16; p.ld16 = g.ld16; p.row_part = g.row_part;
-    p.ln_part = g.ln_part; p.ln_c = g.ln_c; p.ln_eps = g.ln_eps;
-    p.X16_lo = g.X16_lo; p.R16_hi = g.R16_hi; p.R16_lo = g.R16_lo;
-    p.range_flag = g.row_part ? g.range_flag : nullptr;
-    p.lo_n0 = g.B_lo ? g.b_lo_n0 : 0;
-    p.k_rev = 0;
-    p.ln_slots = g.ln_part ? (g.ln_slots > 0 ? g.ln_slots : g.K / 128) : 0;
-    p.ln_inv_k = 1.0f / (float)g.K;
-    p.slot_w = g.row_part ? (g.row_slot_w > 0 ? g.row_slot_w : 128) : 0;
-    {
-        // A/B switch: env PIO_WIDE_STAGED_EPI=0 keeps the direct (16 rows x 64 bytes per instruction) epilogue
-        static const int staged = [] {
-            const char *e = getenv("PIO_WIDE_STAGED_EPI");
-            return (e && atoi(e) == 0) ? 0 : 1;
-        }();
-        p.staged_epi = staged;
-#ifdef PIO_EXPERIMENTS
-        p.mf32 = gemm_kernel_choice() == 4 ? 1 : 0;   // (experiments build: the MFMA 32x32x16 variants of the fold GEMMs)
-#else
-        p.mf32 = 0;
-#endif
-    }
-    if (g.b_lo_n0 && (!g.B_lo || g.A_lo)) return PIO_E_ARG;
-    p.n_store = g.n_store > g.N ? g.n_store : g.N;
-    if (g.C && p.n_store > g.ldc) return PIO_E_SHAPE;
-    p.tiles_n = (p.n_store + BN - 1) / BN;
-    const int tiles_m = (g.M + BM - 1) / BM;
-    const size_t esz = g.out_f32 ? 4 : 2;
-    const size_t valign = g.out_f32 ? 16 : 8;
-    bool vec = (((uintptr_t)g.C) % valign == 0) && ((g.ldc * esz) % valign == 0) && ((g.sCb * esz) % valign == 0) &&
-               ((g.sCh * esz) % valign == 0);
-    p.vec_ok = vec ? 1 : 0;
-    p.r_vec = (g.R && ((uintptr_t)g.R % 16 == 0) && (g.ldr % 4 == 0) && (g.r_stride_b % 4 == 0)) ? 1 : 0;
-    p.bias_vec = (g.bias && ((uintptr_t)g.bias % 16 == 0)) ? 1 : 0;
-
-    dim3 grid((unsigned)(tiles_m * p.tiles_n), (unsigned)g.batch, 1);
-    dim3 block(256, 1, 1);
-    const bool attn = g.batch > 1;
+// algorithmic bytes (profiler): operands once (every precision sweep reads its own image), the result in every form it
+// leaves in (fp32 C if written, 16-bit C [+ C_lo], the LayerNorm fold's 16-bit pair X16 [+ X16_lo] and row sums), the
+// residual in the form it arrives in (fp32 R or the 16-bit pair R16_hi + R16_lo), the consumer's row sums
+static double gemm_algo_bytes(const pio_gemm_t &g) {
     const double elems = (double)g.batch * ((double)g.M * g.K + (double)g.N * g.K);
-    const double algo_flops = 2.0 * g.M * g.N * (double)g.K * g.batch;
-    // algorithmic bytes: operands once (every precision sweep reads its own image), the result in every form it
-    // leaves in (fp32 C if written, 16-bit C [+ C_lo], the LayerNorm fold's 16-bit pair X16 [+ X16_lo] and row sums),
-    // the residual in the form it arrives in (fp32 R or the 16-bit pair R16_hi + R16_lo), the consumer's row sums
     const double mn = (double)g.batch * g.M * g.N;
     double algo_bytes = 2.0 * elems + (g.B_lo ? 2.0 * g.batch * (double)g.N * g.K : 0.0) +
                         (g.A_lo ? 2.0 * g.batch * (double)g.M * g.K : 0.0);
@@ -634,202 +553,72 @@ int gemm_nt_launch(const pio_gemm_t &g, hipStream_t s) {
     if (g.R16_hi) algo_bytes += 4.0 * mn;
     else if (g.R) algo_bytes += 4.0 * mn;
     if (g.ln_part) algo_bytes += 64.0 * g.M;
-    // A handful of output columns over many rows: no tile kernel (see gemm_nt_skinny); env PIO_GEMM_SKINNY=0: A/B switch
-    {
-        static const bool skinny_on = [] {
-            const char *e = getenv("PIO_GEMM_SKINNY");
-            return !e || atoi(e) != 0;
-        }();
-        const bool plain = !p.X16 && !p.row_part && !p.ln_part && !p.ln_c && !p.X16_lo && !p.R16_hi && !p.R16_lo && !p.R &&
-                           !p.C_lo && g.act == 0 && g.bias_mode <= 1 && !g.b_lo_n0 && g.C;
-        // (up to four columns: 182 528 x 328 -> 2 with split activations 42 us against 70 on the 128 x 128 tile; at eight
-        //  columns x K = 1032 the fp32 FMAs of this kernel cost more than the tile's padding: 190 against 125 us)
-        if (skinny_on && gemm_kernel_choice() == 0 && plain && g.batch == 1 && p.n_store <= 4 && g.M >= 2048 &&
-            g.K <= 2048 && p.n_store <= g.ldc) {
-            ProfScope prof(PROF_GEMM_SMALL, algo_flops, algo_bytes, s);
-            gemm_log("skinny", g, p);
-            const int nmax = p.n_store <= 2 ? 2 : 4;
-            const size_t lds = (size_t)p.npass * nmax * g.K * 2;   // <= 48 KiB
-            const unsigned blocks = (unsigned)(g.M / 4 < 256 * 8 ? (g.M + 3) / 4 : 256 * 8);
-#define PIO_SK(DTV)                                                                                                  \
-    do {                                                                                                             \
-        if (nmax == 2) hipLaunchKernelGGL((gemm_nt_skinny<DTV, 2>), dim3(blocks), dim3(256), lds, s, p);             \
-        else hipLaunchKernelGGL((gemm_nt_skinny<DTV, 4>), dim3(blocks), dim3(256), lds, s, p);                       \
-    } while (0)
-            if (g.dtype == PIO_DT_F16) PIO_SK(PIO_DT_F16);
-            else PIO_SK(PIO_DT_BF16);
-#undef PIO_SK
-            return launch_status();
-        }
+    return algo_bytes;
+}
+
+template <int DT, int KIND>
+static void gemm_tile_launch(GemmKernel k, dim3 grid, const GemmParams &p, hipStream_t s) {
+    const dim3 block(256, 1, 1), block2(512, 1, 1);   // (two K teams: eight waves)
+    switch (k) {
+    case GemmKernel::T128_KG2: hipLaunchKernelGGL((gemm_nt_128<DT, KIND, 128, 128, 2, 2>), grid, block2, 0, s, p); break;
+    case GemmKernel::T32_KG2: hipLaunchKernelGGL((gemm_nt_128<DT, KIND, 32, 64, 4, 2>), grid, block2, 0, s, p); break;
+    case GemmKernel::T64_KG2: hipLaunchKernelGGL((gemm_nt_128<DT, KIND, 64, 64, 4, 2>), grid, block2, 0, s, p); break;
+    case GemmKernel::T32: hipLaunchKernelGGL((gemm_nt_128<DT, KIND, 32, 64, 4>), grid, block, 0, s, p); break;
+    case GemmKernel::T64: hipLaunchKernelGGL((gemm_nt_128<DT, KIND, 64, 64, 4>), grid, block, 0, s, p); break;
+    default: hipLaunchKernelGGL((gemm_nt_128<DT, KIND, 128, 128, 2>), grid, block, 0, s, p); break;
     }
-    // Large problems go to the 256x256-tile / 4-slot-ring kernel: enough rows, and an N that fills whole
-    // 256-column tiles reasonably (<= 25 % padding).  PIO_GEMM_TILE=128|256 forces one (benchmarks).
-    {
-        const int forced = gemm_kernel_choice();
-        const int tn256 = (p.n_store + 255) / 256, tm256 = (g.M + 255) / 256;
-        bool fold_small = false;
-        bool big = g.batch == 1 && g.M >= 1024 && p.n_store >= 256 && (double)tn256 * 256.0 <= 1.25 * p.n_store &&
-                   (int64_t)tm256 * tn256 >= 128;
-        if (forced == 128) big = false;
-        if (forced == 256) big = true;
-        // Persistent 256x256 four-wave kernel (pio_gemm_wide.hip): 16-bit-out projections (bias, optional GELU) with
-        // at least one tile per CU.  Its epilogue is exposed, but it is bound by the stores, which the caches absorb
-        // at ~7 TB/s, and the GELU arithmetic hides behind them: 16384x1024x1024 takes 36 us (GELU: 42) against 42
-        // (48) on the streaming kernel.  Override 2 forces it wherever it is legal.
-        {
-            // (With a residual the kernel is legal but not chosen: the 64 MB residual read of a 16384x1024 launch is
-            //  exposed in its epilogue -- 49 us against 39 without -- where the streaming kernel hides most of it.)
-            // (from 128 tiles on: below one tile per CU the four-wave kernel still beats gemm_nt_256 tile for tile -- the
-            //  language model's 8192 x 1280 projections have 160 -- and with fewer than two 256x128 tiles per CU the
-            //  streaming kernel has nothing to hide a residual epilogue behind, so those come here too)
-            const int64_t t256 = (int64_t)tm256 * tn256;
-            static const int wide_min = [] {
-                const char *e = getenv("PIO_WIDE_MIN_TILES");
-                return e ? atoi(e) : 128;
-            }();
-            // (a residual with the hi + lo pair of the result -- the dense decoders' fc2 -- has no streaming variant: here
-            //  rather than on gemm_nt_256)
-            // (multimodal forward 23.23 -> 22.00 ms, in-process A/B)
-            const bool pair_res = p.R && !g.out_f32 && p.C_lo;
-            // (N = 384 = 1.5 tile columns: a third of the MFMAs multiply padding and the kernel still beats the 128 x 128
-            //  tile's exact three columns -- 182 528 x 384 x 384, split activations, GELU, pair out: 204 against 291 us)
-            const bool fill_ok = (double)tn256 * 256.0 <= 1.25 * p.n_store ||
-                                 (p.n_store >= 384 && (double)tn256 * 256.0 <= 1.34 * p.n_store);
-            bool wide = g.batch == 1 && g.M >= 2048 && fill_ok && t256 >= wide_min &&
-                        (!p.R || wide_residual() || 2 * t256 < 448 || pair_res);
-            if (forced == 2) wide = true;
-            if (forced == 1 || forced == 128 || forced == 256) wide = false;
-            const bool fold = p.X16 || p.row_part || p.ln_part || p.ln_c || p.X16_lo || p.R16_hi || p.R16_lo;
-            // The fold on the small tiles (a stack too short for 256 x 256 tiles): chosen by the caller through the slot
-            // form -- a producer asked for 64-column slots, a consumer given anything but K / 128 slots (or a shape the
-            // wide kernel does not take).
-            fold_small = fold && (p.row_part ? p.slot_w == 64
-                                             : (p.ln_slots != g.K / 128 || g.M < 2048 || !gemm_wide_ok(p, g.batch)));
-            if (fold_small) {
-                if (g.batch != 1 || p.npass != 1 || p.lo_n0 || g.bias_mode > 1) return PIO_E_SHAPE;
-                if (p.row_part) {  // producer
-                    if (!p.X16 || !p.X16_lo || !p.R16_hi || !p.R16_lo || !g.out_f32 || p.R || (g.N & 63) || p.n_store != g.N ||
-                        (p.ld16 & 3) || ((uintptr_t)p.X16 & 7) || ((uintptr_t)p.X16_lo & 7) || ((uintptr_t)p.R16_hi & 7) ||
-                        ((uintptr_t)p.R16_lo & 7) || p.ln_part || g.act != 0 || (g.C && ((g.ldc & 3) || ((uintptr_t)g.C & 15))))
-                        return PIO_E_SHAPE;
-                } else {           // consumer
-                    if (!p.ln_part || !p.ln_c || g.out_f32 || g.alpha != 1.0f || p.ln_slots <= 0) return PIO_E_SHAPE;
-                }
-                wide = false;
-            } else if (fold) {
+}
+
+template <int DT>
+static void gemm_skinny_launch(GemmKernel k, dim3 grid, const GemmParams &p, hipStream_t s) {
+    const int nmax = k == GemmKernel::SKINNY2 ? 2 : 4;
+    const size_t lds = (size_t)p.npass * nmax * p.K * 2;   // <= 48 KiB
+    if (nmax == 2) hipLaunchKernelGGL((gemm_nt_skinny<DT, 2>), grid, dim3(256), lds, s, p);
+    else hipLaunchKernelGGL((gemm_nt_skinny<DT, 4>), grid, dim3(256), lds, s, p);
+}
+
+int gemm_nt_launch(const pio_gemm_t &g, hipStream_t s) {
+    GemmParams p;
+    const int err = gemm_params(g, &p);
+    if (err) return err;
+    const int forced = gemm_kernel_choice();
 #ifdef PIO_EXPERIMENTS
-                // (experiments build) the producer on two half-height workgroups per CU: override 3 / env PIO_GEMM_DUO=1
-                static const bool duo_env = [] {
-                    const char *e = getenv("PIO_GEMM_DUO");
-                    return e && atoi(e) != 0;
-                }();
-                if ((forced == 3 || (forced == 0 && duo_env)) && gemm_duo_ok(p, g.batch)) {
-                    ProfScope prof(PROF_GEMM_WIDE, algo_flops, algo_bytes, s);
-                    gemm_log("duo", g, p);
-                    gemm_duo_launch(p, g.dtype, s);
-                    return launch_status();
-                }
+    p.mf32 = forced == 4 ? 1 : 0;   // (experiments build: the MFMA 32x32x16 variants of the fold GEMMs)
 #endif
-                if (!gemm_wide_ok(p, g.batch)) return PIO_E_SHAPE;
-                wide = true;
-            }
-            if (wide && gemm_wide_ok(p, g.batch)) {
-                ProfScope prof(PROF_GEMM_WIDE, algo_flops, algo_bytes, s);
-                gemm_log("wide", g, p);
-                gemm_wide_launch(p, g.dtype, s);
-                return launch_status();
-            }
-        }
-        if (p.lo_n0) return PIO_E_SHAPE;  // (a partial B_lo is a gemm_nt_wide feature)
-        if (fold_small) big = false;
-        // Persistent 256x128 streaming kernel (epilogue of tile j hidden behind the MFMAs of tile j+1): deep-K flat
-        // problems with about two or more tiles per CU (with fewer there is nothing to hide an epilogue behind and
-        // the 256x256 tile's lower operand traffic wins).  Override 1 forces it wherever it is legal.
-        {
-            const int tn128 = (p.n_store + 127) / 128;
-            bool stream = !fold_small && g.batch == 1 && g.M >= 1024 && p.n_store >= 128 &&
-                          (double)tn128 * 128.0 <= 1.25 * p.n_store && (int64_t)tm256 * tn128 >= 448;
-            if (forced == 1) stream = true;
-            if (forced == 128 || forced == 256) stream = false;
-            if (stream && gemm_stream_ok(p, g.batch)) {
-                ProfScope prof(PROF_GEMM_STREAM, algo_flops, algo_bytes, s);
-                gemm_log("stream", g, p);
-                gemm_stream_launch(p, g.dtype, g.batch, s);
-                return launch_status();
-            }
-        }
-        if (big) {
-            ProfScope prof(PROF_GEMM_LINEAR, algo_flops, algo_bytes, s);  // class 0 == kernel gemm_nt_256
-            p.tiles_n = tn256;
-            gemm_log("t256", g, p);
-            gemm256_launch(p, g.dtype, attn, tm256, tn256, g.batch, s);
-            return launch_status();
-        }
+    const GemmRoute r = gemm_route(g, p, forced, cu_budget());
+    if (r.err) return r.err;
+    p.tiles_n = r.tiles_n;
+    gemm_log(r.label, g, p);
+
+    const bool attn = g.batch > 1, f16 = g.dtype == PIO_DT_F16;
+    int cls = attn ? PROF_GEMM_ATTN : PROF_GEMM_SMALL;   // kernel gemm_nt_128 / gemm_nt_skinny
+    if (r.kernel == GemmKernel::WIDE) cls = PROF_GEMM_WIDE;
+    if (r.kernel == GemmKernel::STREAM) cls = PROF_GEMM_STREAM;
+    if (r.kernel == GemmKernel::T256) cls = PROF_GEMM_LINEAR;
+#ifdef PIO_EXPERIMENTS
+    if (r.kernel == GemmKernel::DUO) cls = PROF_GEMM_WIDE;
+#endif
+    ProfScope prof(cls, 2.0 * g.M * g.N * (double)g.K * g.batch, gemm_algo_bytes(g), s);
+    const dim3 grid(r.grid_x, r.grid_y, 1);
+    switch (r.kernel) {
+    case GemmKernel::SKINNY2:
+    case GemmKernel::SKINNY4:
+        if (f16) gemm_skinny_launch<PIO_DT_F16>(r.kernel, grid, p, s);
+        else gemm_skinny_launch<PIO_DT_BF16>(r.kernel, grid, p, s);
+        break;
+    case GemmKernel::WIDE: gemm_wide_launch(p, g.dtype, (int)r.grid_x, s); break;
+    case GemmKernel::STREAM: gemm_stream_launch(p, g.dtype, g.batch, (int)r.grid_x, s); break;
+    case GemmKernel::T256: gemm256_launch(p, g.dtype, attn, grid, s); break;
+#ifdef PIO_EXPERIMENTS
+    case GemmKernel::DUO: gemm_duo_launch(p, g.dtype, s); break;
+#endif
+    default:
+        if (f16 && attn) gemm_tile_launch<PIO_DT_F16, 1>(r.kernel, grid, p, s);
+        else if (f16) gemm_tile_launch<PIO_DT_F16, 0>(r.kernel, grid, p, s);
+        else if (attn) gemm_tile_launch<PIO_DT_BF16, 1>(r.kernel, grid, p, s);
+        else gemm_tile_launch<PIO_DT_BF16, 0>(r.kernel, grid, p, s);
+        break;
     }
-    ProfScope prof(attn ? PROF_GEMM_ATTN : PROF_GEMM_SMALL, algo_flops, algo_bytes, s);  // kernel gemm_nt_128
-    // 64 x 64 tiles when the 128 x 128 tiling would leave most CUs without a tile (small batches: the 2048-row latent
-    // stack of the flow model at B = 1 has 64 tiles of 128 x 128 per GEMM, 256 of 64 x 64); override 64 forces them
-    const int64_t tiles128 = (int64_t)tiles_m * p.tiles_n * g.batch;
-    // ... and up to ONE 128 x 128 tile per CU (the double buffer then has no second workgroup to hide its waits behind) when
-    // the 64 x 64 tiling fills whole rounds of the chip's 512 resident workgroups or K is short: same box, ms per forward
-    // (tools/latency_probe.py / ab_env.py): ImageNet B = 8 (4096 x 1024 x 1024 projections: 256 -> 1024 tiles) 7.63 -> 7.27,
-    // flow (q|k|v 2048 x 1536 x 512: 192 -> 768 tiles) 5.31 -> 5.24; NOT the B = 2 q|k|v (1024 x 3072 x 1024: 192 -> 768
-    // tiles = 1.5 rounds of 16 K steps): 4.11 -> 4.18.
-    const int64_t tiles64_all = (int64_t)((g.M + 63) / 64) * ((p.n_store + 63) / 64) * g.batch;
-    const bool one_round = tiles128 <= cu_budget() && (g.K <= 512 || tiles64_all % (2 * (int64_t)cu_budget()) == 0);
-    const bool small = gemm_kernel_choice() == 64 || (gemm_kernel_choice() == 0 && (tiles128 < 192 || one_round));
-    // ... and 32 x 64 tiles when even the 64 x 64 tiling leaves a third of the CUs without one (ImageNet B = 1: the
-    // 512 x 1024 projections have 128 tiles of 64 x 64, 256 of 32 x 64); env PIO_GEMM_T32=0: A/B switch
-    static const bool t32_on = [] {
-        const char *e = getenv("PIO_GEMM_T32");
-        return !e || atoi(e) != 0;
-    }();
-    const int64_t tiles64 = tiles64_all;
-    const bool tiny = small && t32_on && gemm_kernel_choice() == 0 && 3 * tiles64 < 2 * (int64_t)cu_budget();
-    gemm_log(tiny ? "t32" : small ? "t64" : "t128", g, p);
-    if (small) {
-        p.tiles_n = (p.n_store + 63) / 64;
-        grid = dim3((unsigned)(((g.M + (tiny ? 31 : 63)) / (tiny ? 32 : 64)) * p.tiles_n), (unsigned)g.batch, 1);
-    }
-    // 128 x 128 tiles on problems of at most ONE workgroup per CU (nobody covers a wave's wait for its next operand
-    // stage): the four-stage LDS-DMA ring instead of the double buffer -- measured level on the flow stack's q|k|v GEMM
-    // (2048 x 1536 x 512: 5.69 -> 5.68 ms per forward) and not better anywhere, so opt-in (env PIO_GEMM_RING128=1)
-    static const bool ring128_on = [] {
-        const char *e = getenv("PIO_GEMM_RING128");
-        return e && atoi(e) != 0;
-    }();
-    const bool ring128 = !small && ring128_on && tiles128 <= cu_budget();
-    // two K teams (eight waves) for small tiles that own their CU alone (see the kernel); env PIO_GEMM_KG2=0: A/B switch
-    static const bool kg2_on = [] {
-        const char *e = getenv("PIO_GEMM_KG2");
-        return !e || atoi(e) != 0;
-    }();
-    // (from K = 1024: the flow stack's 2048 x 512 x 512 projections -- four steps a team -- lose 2 % of a forward to it,
-    //  ImageNet B = 1 gains 5.6 %: tools/ab_env.py)
-    const bool kg2 = small && kg2_on && gemm_kernel_choice() == 0 && p.npass * g.K >= 1024 &&
-                     (int64_t)grid.x * grid.y <= (int64_t)cu_budget();
-    // ... and the 128 x 128 tile likewise when it owns its CU alone (ImageNet B = 2: the 1024 x 3072 x 1024 q|k|v GEMM has
-    // 192 tiles; forward 4.62 -> 4.46 ms, tools/ab_env.py)
-    const bool kg2_128 = !small && !ring128 && kg2_on && gemm_kernel_choice() == 0 && p.npass * g.K >= 1024 &&
-                         (int64_t)grid.x * grid.y <= (int64_t)cu_budget();
-#define PIO_G128(DTV, KINDV)                                                                            \
-    do {                                                                                                \
-        if (kg2_128) hipLaunchKernelGGL((gemm_nt_128<DTV, KINDV, 128, 128, 2, 2>), grid, dim3(512, 1, 1), 0, s, p); \
-        else if (tiny && kg2) hipLaunchKernelGGL((gemm_nt_128<DTV, KINDV, 32, 64, 4, 2>), grid, dim3(512, 1, 1), 0, s, p); \
-        else if (small && kg2) hipLaunchKernelGGL((gemm_nt_128<DTV, KINDV, 64, 64, 4, 2>), grid, dim3(512, 1, 1), 0, s, p); \
-        else if (tiny) hipLaunchKernelGGL((gemm_nt_128<DTV, KINDV, 32, 64, 4>), grid, block, 0, s, p);  \
-        else if (small) hipLaunchKernelGGL((gemm_nt_128<DTV, KINDV, 64, 64, 4>), grid, block, 0, s, p); \
-        else if (ring128) hipLaunchKernelGGL((gemm_nt_128<DTV, KINDV, 128, 128, 4>), grid, block, 0, s, p); \
-        else hipLaunchKernelGGL((gemm_nt_128<DTV, KINDV, 128, 128, 2>), grid, block, 0, s, p);          \
-    } while (0)
-    if (g.dtype == PIO_DT_F16) {
-        if (attn) PIO_G128(PIO_DT_F16, 1);
-        else PIO_G128(PIO_DT_F16, 0);
-    } else {
-        if (attn) PIO_G128(PIO_DT_BF16, 1);
-        else PIO_G128(PIO_DT_BF16, 0);
-    }
-#undef PIO_G128
     return launch_status();
 }
 

@@ -10,9 +10,9 @@
 //     * blockIdx is remapped so that the 8 XCDs each own a contiguous run of tiles (neighbouring tiles share
 //       their A panel / the weight in that XCD's L2);
 //     * epilogue in two 128-row halves through the (now idle) ring: whole 1-KiB rows per wave instruction.
-//   Schedule variants (template VAR, env PIO_GEMM256_VAR for A/B runs in one process):
-//     bit 0: fragments of tile kt+1 are read from LDS while the MFMAs of tile kt run (register double buffer)
-//     bit 1: the 4 DMA pieces of the refill are issued between the four 8-MFMA groups instead of up front
+//   Schedule: the two waves that share a SIMD ping-pong between LDS reads + refill and MFMAs (below): 712 -> 745 TF on
+//   16384x3072x1024; a register double buffer of the fragments (-2 %) and DMA pieces interleaved between the MFMA
+//   groups (-9 %) measured slower and are gone (DESIGN_LOG.md).
 // Same GemmParams / epilogue semantics as the 128x128 kernel (pio_gemm.hip).
 #include "pio_gemm_common.h"
 
@@ -46,13 +46,11 @@ __device__ __forceinline__ void wait_vm_tiles(int tiles_in_flight) {  // 4 DMA i
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int DT, int KIND, int VAR>
+template <int DT, int KIND>
 __global__ __launch_bounds__(512) void gemm_nt_256(const GemmParams p) {
     typedef typename Op<DT>::T T;
     typedef typename Op<DT>::V8 V8;
-    constexpr bool PREFETCH = (VAR & 1) != 0;
-    constexpr bool INTERLEAVE = (VAR & 2) != 0;
-    constexpr int AHEAD = PREFETCH ? L_STAGES : L_STAGES - 1;  // refill distance (tiles)
+    constexpr int AHEAD = L_STAGES - 1;  // refill distance (tiles)
     __shared__ __attribute__((aligned(16))) char smem[L_STAGES * L_STAGE];
 
     const int tid = threadIdx.x;
@@ -129,82 +127,39 @@ __global__ __launch_bounds__(512) void gemm_nt_256(const GemmParams p) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) af[i] = *(const V8 *)(abase + a_off0 + i * 16 * 64);
     };
-    auto mma = [&](int kt, V8 (&afc)[8], V8 (&bfc)[4]) {
-        const bool more = kt + AHEAD < nk;
-        if (!INTERLEAVE && more) stage(kt + AHEAD);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-#pragma unroll
-            for (int mi = 2 * g; mi < 2 * g + 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = Op<DT>::mfma16(bfc[ni], afc[mi], acc[mi][ni]);
-            if (INTERLEAVE && more) stage_piece(kt + AHEAD, g >> 1, (g & 1) != 0);
-        }
-    };
-
     PIO_STAMP(0);
 #pragma unroll
     for (int t = 0; t < AHEAD; ++t)
         if (t < nk) stage(t);
 
-    if constexpr ((VAR & 4) != 0) {
-        // PING-PONG: the two waves that share a SIMD (wave w and w+4 = the two wave rows wr 0/1) run half a K tile
-        // out of phase: while one row issues its LDS reads + DMA refill (LOAD) the other owns the matrix pipe (MFMA).
-        // Both rows run the same instruction stream LOAD(0) MFMA(0) LOAD(1) MFMA(1) ... with ONE barrier per K tile
-        // and wave, at different points: wr1 meets wr0 after its LOAD, wr0 after its MFMA phase -- so between two
-        // barriers wr0 runs LOAD(t) MFMA(t) while wr1 runs MFMA(t-1) LOAD(t).  Tile t+1 is complete before barrier t
-        // (wr0 waits for its pieces at the end of MFMA(t), wr1 at the end of LOAD(t)); the slot refilled in LOAD(t)
-        // (tile t+3) held tile t-1, whose last reads (wr1's LOAD(t-1)) drained before barrier t-1.
-        V8 af[8], bf[4];
-        wait_vm_tiles<0>(nk - 1 < AHEAD - 1 ? nk - 1 : AHEAD - 1);
-        __builtin_amdgcn_s_barrier();  // tile 0 visible to everyone
-        PIO_STAMP(1);
-        for (int kt = 0; kt < nk; ++kt) {
-            const int rem = nk - 2 - kt;
-            const int infl = rem < 0 ? 0 : (rem > 2 ? 2 : rem);
-            load_frags(kt, af, bf);
-            if (kt + AHEAD < nk) stage(kt + AHEAD);
-            if (wr == 1) wait_vm_tiles<0>(infl);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (wr == 1) __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_s_setprio(1);
+    // PING-PONG: the two waves that share a SIMD (wave w and w+4 = the two wave rows wr 0/1) run half a K tile
+    // out of phase: while one row issues its LDS reads + DMA refill (LOAD) the other owns the matrix pipe (MFMA).
+    // Both rows run the same instruction stream LOAD(0) MFMA(0) LOAD(1) MFMA(1) ... with ONE barrier per K tile
+    // and wave, at different points: wr1 meets wr0 after its LOAD, wr0 after its MFMA phase -- so between two
+    // barriers wr0 runs LOAD(t) MFMA(t) while wr1 runs MFMA(t-1) LOAD(t).  Tile t+1 is complete before barrier t
+    // (wr0 waits for its pieces at the end of MFMA(t), wr1 at the end of LOAD(t)); the slot refilled in LOAD(t)
+    // (tile t+3) held tile t-1, whose last reads (wr1's LOAD(t-1)) drained before barrier t-1.
+    V8 af[8], bf[4];
+    wait_vm_tiles<0>(nk - 1 < AHEAD - 1 ? nk - 1 : AHEAD - 1);
+    __builtin_amdgcn_s_barrier();  // tile 0 visible to everyone
+    PIO_STAMP(1);
+    for (int kt = 0; kt < nk; ++kt) {
+        const int rem = nk - 2 - kt;
+        const int infl = rem < 0 ? 0 : (rem > 2 ? 2 : rem);
+        load_frags(kt, af, bf);
+        if (kt + AHEAD < nk) stage(kt + AHEAD);
+        if (wr == 1) wait_vm_tiles<0>(infl);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (wr == 1) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int mi = 0; mi < 8; ++mi)
+        for (int mi = 0; mi < 8; ++mi)
 #pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = Op<DT>::mfma16(bf[ni], af[mi], acc[mi][ni]);
-            __builtin_amdgcn_s_setprio(0);
-            if (wr == 0) {
-                wait_vm_tiles<0>(infl);
-                __builtin_amdgcn_s_barrier();
-            }
-        }
-    } else if constexpr (PREFETCH) {
-        // tile kt+1's fragments are read while tile kt is multiplied; the refill goes into tile kt's own slot
-        V8 af0[8], bf0[4], af1[8], bf1[4];
-        wait_vm_tiles<0>(nk - 1 < AHEAD - 1 ? nk - 1 : AHEAD - 1);
-        __builtin_amdgcn_s_barrier();
-        load_frags(0, af0, bf0);
-        auto iter = [&](int kt, V8 (&afc)[8], V8 (&bfc)[4], V8 (&afn)[8], V8 (&bfn)[4]) {
-            const int rem = nk - 2 - kt;  // issued tiles after kt+1 (<= 2) may stay in flight
-            wait_vm_tiles<0>(rem < 0 ? 0 : (rem > 2 ? 2 : rem));
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of tile kt have RETURNED
-            __builtin_amdgcn_s_barrier();  // tile kt+1 visible to all; tile kt's slot is free
-            if (kt + 1 < nk) load_frags(kt + 1, afn, bfn);
-            mma(kt, afc, bfc);
-        };
-        for (int kt = 0; kt < nk; kt += 2) {
-            iter(kt, af0, bf0, af1, bf1);
-            if (kt + 1 < nk) iter(kt + 1, af1, bf1, af0, bf0);
-        }
-    } else {
-        V8 af[8], bf[4];
-        for (int kt = 0; kt < nk; ++kt) {
-            const int rem = nk - 1 - kt;  // issued tiles after kt (<= 2) may stay in flight
-            wait_vm_tiles<0>(rem > 2 ? 2 : rem);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();  // tile kt visible to all; tile kt-1's slot is free
-            load_frags(kt, af, bf);
-            mma(kt, af, bf);
+            for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = Op<DT>::mfma16(bf[ni], af[mi], acc[mi][ni]);
+        __builtin_amdgcn_s_setprio(0);
+        if (wr == 0) {
+            wait_vm_tiles<0>(infl);
+            __builtin_amdgcn_s_barrier();
         }
     }
 
@@ -289,26 +244,15 @@ extern "C" int pio_debug_gemm_stamps(unsigned long long *out8, int epi_mode) {
 }
 #endif
 
-void gemm256_launch(const GemmParams &p, int dtype, bool attn, int tiles_m, int tiles_n, int batch, hipStream_t s) {
-    static const int var = [] {
-        const char *e = getenv("PIO_GEMM256_VAR");
-        return e ? atoi(e) : 4;  // default: ping-pong schedule (fastest in A/B runs)
-    }();
-    dim3 grid((unsigned)(tiles_m * tiles_n), (unsigned)batch, 1), block(512, 1, 1);
-#define PIO_G256(DTV, KINDV)                                                                          \
-    switch (var & 7) {                                                                                \
-        case 4: hipLaunchKernelGGL((gemm_nt_256<DTV, KINDV, 4>), grid, block, 0, s, p); break;       \
-        case 1: hipLaunchKernelGGL((gemm_nt_256<DTV, KINDV, 1>), grid, block, 0, s, p); break;       \
-        case 2: hipLaunchKernelGGL((gemm_nt_256<DTV, KINDV, 2>), grid, block, 0, s, p); break;       \
-        case 3: hipLaunchKernelGGL((gemm_nt_256<DTV, KINDV, 3>), grid, block, 0, s, p); break;       \
-        default: hipLaunchKernelGGL((gemm_nt_256<DTV, KINDV, 0>), grid, block, 0, s, p); break;      \
-    }
+void gemm256_launch(const GemmParams &p, int dtype, bool attn, dim3 grid, hipStream_t s) {
+    const dim3 block(512, 1, 1);
     if (dtype == PIO_DT_F16) {
-        if (attn) { PIO_G256(PIO_DT_F16, 1) } else { PIO_G256(PIO_DT_F16, 0) }
+        if (attn) hipLaunchKernelGGL((gemm_nt_256<PIO_DT_F16, 1>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((gemm_nt_256<PIO_DT_F16, 0>), grid, block, 0, s, p);
     } else {
-        if (attn) { PIO_G256(PIO_DT_BF16, 1) } else { PIO_G256(PIO_DT_BF16, 0) }
+        if (attn) hipLaunchKernelGGL((gemm_nt_256<PIO_DT_BF16, 1>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((gemm_nt_256<PIO_DT_BF16, 0>), grid, block, 0, s, p);
     }
-#undef PIO_G256
 }
 
 }  // namespace pio

@@ -1,49 +1,9 @@
 // Shared by the two NT-GEMM kernels (pio_gemm.hip: 128x128 tile; pio_gemm256.hip: 256x256 tile).
 #pragma once
 #include "pio_internal.h"
+#include "pio_gemm_route.h"
 
 namespace pio {
-
-struct GemmParams {
-    const void *A, *B;
-    int64_t dA1, dB1, dA2, dB2;  // element offsets of the pass-1 / pass-2 operands relative to A / B
-    int npass;                   // 1..3 K sweeps accumulating into the same registers
-    int staged_epi;              // (gemm_nt_wide, LayerNorm-fold producer) 1: LDS-staged, row-coalesced epilogue
-    int mf32;                    // (experiments build only) gemm_nt_wide fold GEMMs on the MFMA 32x32x16 variants
-    int lo_n0;                   // (gemm_nt_wide only) B_lo exists for columns >= lo_n0 (multiple of 256); 0 = all
-    int k_rev;                   // (gemm_nt_wide only) odd tiles of a workgroup sweep K backwards (see its walk)
-    void *C, *C_lo;
-    int M, N, K;
-    int64_t lda, ldb, ldc;
-    int nh;
-    int64_t sAb, sAh, sBb, sBh, sCb, sCh;
-    const float *bias;
-    int bias_mode, act;
-    float alpha;
-    const float *R;
-    int64_t ldr, r_stride_b;
-    int r_rows;
-    int out_f32, n_store;
-    int tiles_n;
-    int vec_ok;    // C rows are 16-byte (fp32) / 8-byte (16-bit) aligned for 4-column vectors
-    int r_vec;     // residual rows are 16-byte aligned
-    int bias_vec;  // bias is 16-byte aligned
-    // LayerNorm fold (gemm_nt_wide only): producer outputs / consumer inputs, see pio_gemm_t
-    void *X16;
-    int64_t ld16;
-    float *row_part;
-    const float *ln_part, *ln_c;
-    float ln_eps;
-    void *X16_lo;
-    const void *R16_hi, *R16_lo;
-    int *range_flag;  // producer: set to 1 when a row statistic is not finite (the folded stack's fp16 range guard)
-    // consumer: ln_part holds ln_slots (sum, sum of squares) pairs per row (K / 128 from the wide kernel's producer, K / 64
-    // from the small-tile kernels'), ln_inv_k = 1 / K; producer: slot_w = columns per slot (128 wide kernel, 64 small tiles)
-    int ln_slots;
-    float ln_inv_k;
-    int slot_w;
-};
-
 
 // Exact (erf) GELU, gelu(x) = x Phi(x), in eight instruction slots per element: with E = Phi(-|x|) = 0.5 erfc(|x| / sqrt 2)
 //     gelu(x) = max(x, 0) - |x| E        (x >= 0: x (1 - E);  x < 0: x E)
@@ -158,20 +118,18 @@ __device__ __forceinline__ f32x4 load_bias4(const GemmParams &p, int n0) {
     return bias_n;
 }
 
+// The launchers of the kernel families gemm_route picks (grid: GemmRoute.grid_x / grid_y).
 // 256x256-tile kernel (pio_gemm256.hip); `attn` only selects the kernel-name tag.
-void gemm256_launch(const GemmParams &p, int dtype, bool attn, int tiles_m, int tiles_n, int batch, hipStream_t s);
+void gemm256_launch(const GemmParams &p, int dtype, bool attn, dim3 grid, hipStream_t s);
 
-// persistent 256x128-tile streaming kernel (pio_gemm_stream.hip)
-bool gemm_stream_ok(const GemmParams &p, int batch);
-void gemm_stream_launch(const GemmParams &p, int dtype, int batch, hipStream_t s);
+// persistent 256x128-tile streaming kernel (pio_gemm_stream.hip) on G workgroups
+void gemm_stream_launch(const GemmParams &p, int dtype, int batch, int G, hipStream_t s);
 
-// persistent 256x256-tile four-wave kernel (pio_gemm_wide.hip): plain 16-bit-out projections
-bool gemm_wide_ok(const GemmParams &p, int batch);
-void gemm_wide_launch(const GemmParams &p, int dtype, hipStream_t s);
+// persistent 256x256-tile four-wave kernel (pio_gemm_wide.hip) on G workgroups
+void gemm_wide_launch(const GemmParams &p, int dtype, int G, hipStream_t s);
 
 #ifdef PIO_EXPERIMENTS
 // the LayerNorm fold's producer with two 128x256-tile workgroups per CU (tools/experiments/pio_gemm_duo.hip)
-bool gemm_duo_ok(const GemmParams &p, int batch);
 void gemm_duo_launch(const GemmParams &p, int dtype, hipStream_t s);
 #endif
 

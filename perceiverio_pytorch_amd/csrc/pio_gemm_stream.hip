@@ -64,13 +64,12 @@ __device__ int g_smode;  // ablations: bit 0 = no fragment reads / MFMAs, bit 1 
 #define PIO_SSTAMP(i)
 #endif
 
-constexpr int S_BM = 256, S_BN = 128, S_BK = 64, S_NST = 3;
+constexpr int S_NST = 3;                  // (S_BM x S_BN tiles, S_BK-deep stages: pio_gemm_route.h)
 constexpr int S_AB = S_BM * S_BK * 2;     // 32 KiB of A per stage
 constexpr int S_BB = S_BN * S_BK * 2;     // 16 KiB of B per stage
 constexpr int S_STAGE = S_AB + S_BB;      // 48 KiB
 constexpr int S_RING = S_NST * S_STAGE;   // 144 KiB
 constexpr int S_BIAS_W = 768;             // per wave: 3 slots x 64 floats (bias rows of tiles j, j+1, j+2)
-constexpr int S_TAB_N = 256;            // tile-table entries (32 B each): this workgroup's tile list, decoded once
 constexpr int S_TAB = S_RING + 8 * S_BIAS_W;
 constexpr int S_SMEM = S_TAB + S_TAB_N * 32;
 
@@ -524,40 +523,8 @@ extern "C" int pio_debug_stream_stamps(unsigned long long *out16) {
 }
 #endif
 
-static int stream_grid(int64_t total) {  // one workgroup per CU, a multiple of 8 (the XCD count) when possible
-    const int n_cu = cu_budget();
-    int G = (int)(total < n_cu ? total : n_cu);
-    if (G >= 8) G &= ~7;
-    return G;
-}
-
-bool gemm_stream_ok(const GemmParams &p, int batch) {
-    const int nk = p.npass * ((p.K + S_BK - 1) / S_BK);
-    if (nk < 16 || (p.K % S_BK)) return false;
-    if (p.bias_mode > 1 || (p.bias_mode == 1 && !p.bias_vec)) return false;
-    if ((p.N & 3) || (p.n_store & 3) || !p.vec_ok) return false;
-    if (p.act != 0 && p.act != 1) return false;
-    if (p.alpha == 0.0f) return false;
-    // (a residual with a 16-bit result -- the decoder's fc2 leaving y as the operand of the final Linear -- rides the same
-    //  way: the residual is loaded into the vacated accumulators, the output form is the epilogue's business)
-    if (p.R && (!p.r_vec || p.alpha != 1.0f || p.act != 0 || p.r_rows != 0)) return false;
-    // (... as ONE 16-bit array: the hi + lo pair form of that variant spills 11 registers, which the counted waits of this
-    //  kernel cannot carry -- those launches go to gemm_nt_256)
-    if (p.R && !p.out_f32 && p.C_lo) return false;
-    if (p.out_f32 && p.act != 0) return false;
-    if (p.out_f32 && p.C_lo) return false;
-    // per-lane DMA offsets are 32-bit byte offsets inside one (batch, head) slice
-    if (((int64_t)p.M * p.lda + p.K) * 2 >= (1ll << 32) || ((int64_t)p.N * p.ldb + p.K) * 2 >= (1ll << 32)) return false;
-    // the per-workgroup tile list is decoded into an LDS table of S_TAB_N entries
-    const int64_t tiles = (int64_t)((p.M + S_BM - 1) / S_BM) * ((p.n_store + S_BN - 1) / S_BN) * batch;
-    const int G = stream_grid(tiles);
-    if ((tiles + G - 1) / G + 8 > S_TAB_N) return false;
-    return true;
-}
-
-void gemm_stream_launch(const GemmParams &p, int dtype, int batch, hipStream_t s) {
+void gemm_stream_launch(const GemmParams &p, int dtype, int batch, int G, hipStream_t s) {
     const int tiles_m = (p.M + S_BM - 1) / S_BM, tiles_n = (p.n_store + S_BN - 1) / S_BN;
-    const int G = stream_grid((int64_t)tiles_m * tiles_n * batch);
     dim3 grid((unsigned)G, 1, 1), block(512, 1, 1);
 #define PIO_GK(DTV, R, ACT, OUT) hipLaunchKernelGGL((gemm_nt_stream<DTV, R, ACT, OUT>), grid, block, 0, s, p, tiles_m, tiles_n, batch)
 #define PIO_GS(DTV)                                                      \

@@ -41,7 +41,7 @@
 
 namespace pio {
 
-constexpr int W_BM = 256, W_BN = 256, W_BK = 32, W_NST = 4;
+constexpr int W_NST = 4;                 // (W_BM x W_BN tiles, W_BK-deep slices: pio_gemm_route.h)
 constexpr int W_AB = W_BM * W_BK * 2;    // 16 KiB of A per slice
 constexpr int W_STAGE = 2 * W_AB;        // 32 KiB
 constexpr int W_RING = W_NST * W_STAGE;  // 128 KiB
@@ -1022,63 +1022,11 @@ extern "C" int pio_debug_wide_stamps(unsigned long long *out12) {
 }
 #endif
 
-static int wide_grid(int64_t total) {
-    const int n_cu = cu_budget();
-    int G = (int)(total < n_cu ? total : n_cu);
-    if (G >= 8) G &= ~7;
-    return G;
-}
-
-bool gemm_wide_ok(const GemmParams &p, int batch) {
-    if (batch != 1 || p.npass > 3) return false;
-    // a second sweep against B_lo only (weights as hi + lo, single activations) may start at a 256-aligned column; the
-    // sweeps with an A_lo image (split activations: dA1 or dA2) cover every column
-    const bool b_lo_only = p.npass == 2 && p.dA1 == 0;
-    // (the fold forms run the two-way sweep code: B_lo only)
-    if (!b_lo_only && p.npass > 1 && (p.ln_part || p.ln_c || p.R16_hi || p.R16_lo || (p.row_part && !p.R))) return false;
-    if (b_lo_only && (p.dB1 == 0 || p.lo_n0 < 0 || (p.lo_n0 % W_BN))) return false;
-    if (!b_lo_only && p.lo_n0 != 0) return false;
-    if (p.K < 4 * W_BK || (p.K % (2 * W_BK))) return false;
-    if (p.act != 0 && p.act != 1) return false;
-    // the hi + lo pair of the result: the plain 16-bit epilogue only (not the fold forms, not fp32 out)
-    if (p.C_lo && (p.out_f32 || p.ln_part || p.row_part || p.X16 || ((uintptr_t)p.C_lo & 15))) return false;
-    if (p.out_f32 && (p.act != 0 || (p.C && (p.ldc & 3)))) return false;
-    // an fp32 residual: with an fp32 result, or -- the dense decoders' fc2 -- with the hi + lo pair of the result (the
-    // fold producer's epilogue without its statistics: gemm_wide_launch maps C / C_lo onto X16 / X16_lo)
-    const bool pair_res = p.R && !p.out_f32 && p.C_lo && p.C && p.act == 0 && !p.X16 && !p.row_part && !p.ln_part;
-    if (p.R && ((!p.out_f32 && !pair_res) || !p.r_vec || p.r_rows != 0 || (p.ldr & 3))) return false;
-    if (pair_res && (((uintptr_t)p.C & 15) || ((uintptr_t)p.C_lo & 15) || (p.ldc & 7))) return false;
-    if (p.X16 || p.row_part || p.X16_lo || p.R16_hi || p.R16_lo) {  // LayerNorm-fold producer
-        const bool pair_r = p.R16_hi || p.R16_lo;
-        if (!p.X16 || !p.row_part || !p.out_f32 || (p.N & 127) || p.slot_w != 128 || (p.ld16 & 7) || ((uintptr_t)p.X16 & 15) ||
-            ((uintptr_t)p.row_part & 7) || p.ln_part || p.ln_c)
-            return false;
-        if (pair_r ? (!p.R16_hi || !p.R16_lo || p.R || ((uintptr_t)p.R16_hi & 15) || ((uintptr_t)p.R16_lo & 15)) : !p.R)
-            return false;
-        if (((uintptr_t)p.X16_lo & 15) || (!p.C && !p.X16_lo)) return false;
-    }
-    if (p.ln_part || p.ln_c) {  // LayerNorm-fold consumer
-        if (!p.ln_part || !p.ln_c || p.out_f32 || (p.K & 127) || p.K > 1536 || p.ln_slots != p.K / 128 ||
-            (p.ln_slots & 1) || p.alpha != 1.0f || ((uintptr_t)p.ln_c & 15) || ((uintptr_t)p.ln_part & 15))
-            return false;
-    }
-    if (p.bias_mode > 1 || (p.bias_mode == 1 && !p.bias_vec)) return false;
-    if ((p.N & 7) || (p.n_store & 7) || (p.C && ((p.ldc & 7) || ((uintptr_t)p.C & 15)))) return false;
-    if ((p.lda & 7) || (p.ldb & 7) || ((uintptr_t)p.A & 15) || ((uintptr_t)p.B & 15)) return false;
-    if (((int64_t)p.M * p.lda + p.K) * 2 >= (1ll << 32) || ((int64_t)p.N * p.ldb + p.K) * 2 >= (1ll << 32)) return false;
-    return true;
-}
-
-void gemm_wide_launch(const GemmParams &p, int dtype, hipStream_t s) {
+void gemm_wide_launch(const GemmParams &p, int dtype, int G, hipStream_t s) {
     const int tiles_m = (p.M + W_BM - 1) / W_BM, tiles_n = (p.n_store + W_BN - 1) / W_BN;
-    const int G = wide_grid((int64_t)tiles_m * tiles_n);
     dim3 grid((unsigned)G, 1, 1), block(256, 1, 1);
     GemmParams pk = p;
-    {
-        const char *e = getenv("PIO_WIDE_KREV");  // (read per launch: A/B switch for tools/ab_env.py)
-        pk.k_rev = e ? atoi(e) : 0;
-    }
-    const bool pair_res = p.R && !p.out_f32 && p.C_lo;
+    const bool pair_res = gemm_pair_res(p);
     if (pair_res) {   // fp32 residual in, hi + lo pair out: the fold producer's epilogue (<0, 2, 1, 1>) without statistics
         pk.X16 = p.C;
         pk.X16_lo = p.C_lo;

@@ -52,7 +52,7 @@ def run(M, N, K, act, pair_out, resid, iters=20):
 
 
 if "--flow384" in sys.argv:
-    run(182528, 384, 384, 1, True, False)      # fc1 with 322 padded to 384 (PIO_PADC_MIN=256)
+    run(182528, 384, 384, 1, True, False)      # fc1 with 322 padded to 384 (padc: from 256 channels on)
     run(182528, 384, 384, 0, True, True)       # fc2
     run(182528, 512, 384, 0, False, False)     # proj_q
     sys.exit(0)

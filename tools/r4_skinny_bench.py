@@ -1,5 +1,5 @@
 """Dev tool (GPU): the flow decoder's final Linear (182 528 x 328 -> 2, split activations) on the row-per-wave kernel
-against the 128 x 128 tile (PIO_GEMM_SKINNY=0 in a second process)."""
+(automatic choice) against the 128 x 128 tile (pio_gemm_kernel_override(128))."""
 import ctypes as C
 import os
 import sys
@@ -36,9 +36,12 @@ def run(M, N, K, a_lo, iters=50):
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) / iters * 1e3
     gb = M * K * 2 * (2 if a_lo else 1) / us / 1e3
-    print(f"M={M} N={N} K={K} a_lo={a_lo}: {us:8.1f} us  ({gb:7.1f} GB/s of A)  PIO_GEMM_SKINNY={os.environ.get('PIO_GEMM_SKINNY', '1')}", flush=True)
+    print(f"M={M} N={N} K={K} a_lo={a_lo}: {us:8.1f} us  ({gb:7.1f} GB/s of A)  override={OV}", flush=True)
 
 
-run(182528, 2, 328, True)
-run(182528, 2, 328, False)
-run(100352, 3, 512, True)
+for OV in (0, 128):
+    lib.pio_gemm_kernel_override(OV)
+    run(182528, 2, 328, True)
+    run(182528, 2, 328, False)
+    run(100352, 3, 512, True)
+lib.pio_gemm_kernel_override(0)
