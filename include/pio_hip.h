@@ -85,7 +85,14 @@ typedef struct pio_attention_t {
     int32_t act_split; /* 1: activations are carried as hi+lo pairs too (3 MFMA sweeps, ~fp32 products);
                           2: the same for the four projections, but the attention core (Q K^T, softmax, P V) runs
                           single-sweep on the hi halves through the fused kernel wherever one covers the shape (no
-                          score matrix) and returns its output as a pair                                      */
+                          score matrix) and returns its output as a pair;
+                          3: as 2, and Q and K enter the fused core as (hi, lo) pairs: S = Q_hi K_hi + Q_lo K_hi + Q_hi K_lo,
+                          fp32 accumulation, inside the kernel (policy "fp16x3fq").  Pair cores exist for fp16 heads with
+                          dkp <= 32 and dvp <= 160 (cross-attention kernel; key / query mask vectors, key splits) and
+                          (dkp, dvp) in {(32,32), (32,160)} (self-attention kernel, un-masked).  Every other shape -- wide
+                          single heads, the tall-head kernel, the K / V-folded path, bf16 -- has no pair core and runs the
+                          materialised split-operand path of act_split = 1: the request is never served by a single-
+                          operand Q K^T                                                                       */
     pio_linear_t qk;   /* optional (w_hi may be NULL): proj_q and proj_k stacked along the output rows
                           [q rows | k rows], used as ONE GEMM when inputs_q and inputs_k are the same tensor */
     pio_linear_t qkv;  /* optional (w_hi may be NULL): [q rows | k rows | v rows] for self-attention with head widths
@@ -311,6 +318,26 @@ int pio_softmax_rows(const float *S, int64_t lds, void *P, void *P_lo, int64_t l
 int pio_flash_attention(int32_t dtype, int32_t dkp, int32_t dvp, int32_t dk, const void *Q, const void *K, const void *V,
                         void *O, int32_t B, int32_t H, int32_t Tq, int32_t Tk, int64_t ldq, int64_t ldk, int64_t ldv,
                         int64_t ldo, int64_t sQb, int64_t sKb, int64_t sVb, int64_t sOb, int32_t v_rowmajor, void *stream);
+
+/* The fused attention cores with Q and K as 16-bit (hi, lo) PAIRS inside Q K^T (transformer_primitives.py:138-166; with the
+ * mask vectors :168-175 too): S = Q_hi K_hi^T + Q_lo K_hi^T + Q_hi K_lo^T accumulated in fp32 (lo x lo dropped), everything
+ * behind S as in the single-operand kernels (P rounded once).  Arguments as pio_flash_attention plus: Q_lo / K_lo (same
+ * strides as their hi halves; both NULL = the single-operand sibling of the same kernel, for comparisons), O_lo (optional:
+ * the rounding residual of O), kv_mask [B,Tk] / q_mask [B,Tq] (optional uint8 vectors; rows without an attendable key and
+ * rows with q_mask == 0 are written as zeros) and
+ *   core: 0 = by shape -- the self-attention kernel when no mask is given and it covers (dkp, dvp), else the cross-attention
+ *         kernel; 1 = the self-attention kernel (flash_attn_kernel); 2 = the cross-attention kernel (xattn_kernel).
+ * The cross-attention kernel reads V^T only (v_rowmajor == 0, ldv a multiple of 32 with zero-filled columns behind Tk), reads
+ * whole 32-key tiles of K / K_lo (the 31 rows behind key Tk - 1 of the last sample must be readable) and needs
+ * `workspace` (pio_flash_attention_pair_workspace_bytes: key-bit words of a masked launch, fp32 partials of a key split).
+ * Pair operands: fp16, dkp <= 32 -- (32,32) / (32,160) on the self-attention kernel, dvp <= 160 on the cross-attention
+ * kernel; anything else with Q_lo / K_lo is PIO_E_SHAPE (bf16 included). */
+size_t pio_flash_attention_pair_workspace_bytes(int32_t dkp, int32_t dvp, int32_t B, int32_t H, int32_t Tq, int32_t Tk);
+int pio_flash_attention_pair(int32_t dtype, int32_t dkp, int32_t dvp, int32_t dk, const void *Q, const void *Q_lo,
+                             const void *K, const void *K_lo, const void *V, void *O, void *O_lo, int32_t B, int32_t H,
+                             int32_t Tq, int32_t Tk, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t sQb,
+                             int64_t sKb, int64_t sVb, int64_t sOb, int32_t v_rowmajor, const uint8_t *kv_mask,
+                             const uint8_t *q_mask, int32_t core, void *workspace, size_t workspace_bytes, void *stream);
 
 /* --- blocks: the reference's nn.Module.forward calls ------------------------------------------ */
 /* Attention.forward (transformer_primitives.py:90-115 + attend 117-180).  inputs_k and inputs_v must

@@ -173,8 +173,17 @@ static ScoreChunks score_chunks(int B, int H, int Tq, int Tk) {
 
 // true when attention_core will take a fused (score-free) kernel for every call that passes no full mask / bias /
 // probability output: the plans of the encoder / decoder (which never pass those) then carve no score buffers at all
+// act_split == 3 ("x3fq"): Q and K enter the fused core as (hi, lo) pairs.  Pair cores exist for the dk <= 32 fp16 heads
+// (both kernel families); every other shape -- wide single heads, xattn_tall_kernel, the K / V-folded path, bf16 -- takes
+// the MATERIALISED split-operand path, exactly what act_split == 1 runs: a pair request never silently becomes a
+// single-operand Q K^T.
+static bool pair_core_capable(const pio_attention_t &a) {
+    return flash_pair_supported(a.dtype, a.dkp, a.dvp) || xattn_pair_supported(a.dtype, a.dkp, a.dvp);
+}
+
 static bool fused_capable(const pio_attention_t &a, int Tk) {
     const bool cross = xattn_supported(a.dkp, a.dvp) || xtall_supported(a.dkp, a.dvp, Tk);
+    if (a.act_split == 3) return pair_core_capable(a);
     if (a.act_split == 2) return cross;  // split projections, single-sweep fused core
     return !a.act_split && (flash_supported(a.dkp, a.dvp) || cross);
 }
@@ -203,7 +212,7 @@ struct AttnScratch {
         }
         o16 = take_pair(c, (size_t)B * Tq * ldo, sp);
         size_t xb = 0;
-        if (a.act_split != 1) {
+        if (a.act_split != 1 && !(a.act_split == 3 && !pair_core_capable(a))) {
             if (xattn_supported(a.dkp, a.dvp)) xb = xattn_partial_bytes(a.dkp, a.dvp, B, a.heads, Tq, Tk);
             else if (xtall_supported(a.dkp, a.dvp, Tk)) xb = xtall_scratch_bytes(B);
         }
@@ -290,6 +299,7 @@ static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair 
         const int kvp = pad8(a.k_in);
         const bool kv_fold = !qc && kv_fold_enabled() && a.kq.w_hi && a.vo.w_hi && H == 1 && a.k_in == a.v_in && xk.hi == xv.hi &&
                              a.dk == a.k_in && a.dv == a.v_in && a.dkp == kvp && a.dvp == kvp && a.act_split != 1 &&
+                             a.act_split != 3 &&  // (no pair core on the folded path: materialised split-operand path)
                              // (no mask vectors: a row without an attendable key must come out as `final.bias` alone --
                              //  transformer_primitives.py:168-175 -- but the folded bias Wo bv + bo assumes sum(P) = 1)
                              !kv_mask && !q_mask && !full_mask && !attention_bias && !probs_out &&
@@ -363,8 +373,25 @@ static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair 
     //      query tiles (key splits).  Otherwise the materialised path below.
     // act_split == 2 ("x3f"): the projections around the core run with split operands, the core itself single-sweep
     // on the hi halves of q / k / v^T through the fused cross-attention kernel, which returns its output as a pair.
-    const bool single_core = a.act_split == 2;
+    // act_split == 3 ("x3fq"): as 2, with Q and K entering the core as the (hi, lo) pairs the projection GEMMs wrote (C_lo;
+    // a projected-query cache holds both halves too) -- the self-attention kernel for un-masked heads it covers (its pair
+    // instantiations return the output as a pair as well), the cross-attention kernel otherwise.  Without a pair core for
+    // the shape the request falls through to the materialised split-operand path below.
+    const bool pair_core = a.act_split == 3 && pair_core_capable(a);
+    const bool single_core = a.act_split == 2 || pair_core;
     const bool score_free = (!a.act_split || single_core) && !full_mask && !attention_bias && !probs_out;
+    if (score_free && pair_core) {
+        if (!w.q16.lo || !k_lo) return PIO_E_ARG;
+        if (!kv_mask && !q_mask && flash_pair_supported(a.dtype, a.dkp, a.dvp))
+            PIO_TRY(flash_attention_launch(a.dtype, a.dkp, a.dvp, a.dk, w.q16.hi, k_hi, w.vt16.hi, w.o16.hi, B, H, Tq, Tk,
+                                           ldq, ldq, tkv, ldo, q_bcast ? 0 : (int64_t)Tq * ldq, (int64_t)Tk * ldq,
+                                           ldo * tkv, (int64_t)Tq * ldo, false, s, w.q16.lo, k_lo, w.o16.lo));
+        else
+            PIO_TRY(xattn_launch(a.dtype, a.dkp, a.dvp, a.dk, w.q16.hi, k_hi, w.vt16.hi, w.o16.hi, w.o16.lo, B, H, Tq, Tk,
+                                 ldq, ldq, tkv, ldo, q_bcast ? 0 : (int64_t)Tq * ldq, (int64_t)Tk * ldq, ldo * tkv,
+                                 (int64_t)Tq * ldo, kv_mask, q_mask, w.xpart, s, w.q16.lo, k_lo));
+        return linear_fwd(a.o, a.dtype, w.o16, (int64_t)B * Tq, out, nullptr, true, a.out, out_ld, 0, res, s);
+    }
     if (score_free && !single_core && !kv_mask && !q_mask && flash_supported(a.dkp, a.dvp)) {
         PIO_TRY(flash_attention_launch(a.dtype, a.dkp, a.dvp, a.dk, w.q16.hi, k_hi, w.vt16.hi, w.o16.hi, B, H, Tq,
                                        Tk, ldq, ldq, tkv, ldo, q_bcast ? 0 : (int64_t)Tq * ldq, (int64_t)Tk * ldq,

@@ -190,4 +190,30 @@ int pio_flash_attention(int32_t dtype, int32_t dkp, int32_t dvp, int32_t dk, con
                                   v_rowmajor != 0, (hipStream_t)stream);
 }
 
+size_t pio_flash_attention_pair_workspace_bytes(int32_t dkp, int32_t dvp, int32_t B, int32_t H, int32_t Tq, int32_t Tk) {
+    return xattn_supported(dkp, dvp) ? xattn_partial_bytes(dkp, dvp, B, H, Tq, Tk) : 0;
+}
+
+int pio_flash_attention_pair(int32_t dtype, int32_t dkp, int32_t dvp, int32_t dk, const void *Q, const void *Q_lo,
+                             const void *K, const void *K_lo, const void *V, void *O, void *O_lo, int32_t B, int32_t H,
+                             int32_t Tq, int32_t Tk, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t sQb,
+                             int64_t sKb, int64_t sVb, int64_t sOb, int32_t v_rowmajor, const uint8_t *kv_mask,
+                             const uint8_t *q_mask, int32_t core, void *workspace, size_t workspace_bytes, void *stream) {
+    if (dtype != PIO_DT_F16 && dtype != PIO_DT_BF16) return PIO_E_ARG;
+    if (core < 0 || core > 2 || (!Q_lo) != (!K_lo)) return PIO_E_ARG;
+    const bool masked = kv_mask || q_mask;
+    const bool flash = core == 1 || (core == 0 && !masked && flash_supported(dkp, dvp));
+    if (flash) {
+        if (masked) return PIO_E_ARG;  // (the self-attention kernel takes no mask)
+        if (O_lo && !Q_lo) return PIO_E_ARG;  // (its single-operand instantiations write one half)
+        return flash_attention_launch(dtype, dkp, dvp, dk, Q, K, V, O, B, H, Tq, Tk, ldq, ldk, ldv, ldo, sQb, sKb, sVb, sOb,
+                                      v_rowmajor != 0, (hipStream_t)stream, Q_lo, K_lo, O_lo);
+    }
+    if (v_rowmajor) return PIO_E_ARG;  // (the cross-attention kernel reads V^T)
+    if (!xattn_supported(dkp, dvp)) return PIO_E_SHAPE;
+    if (xattn_partial_bytes(dkp, dvp, B, H, Tq, Tk) > workspace_bytes) return PIO_E_WORKSPACE;
+    return xattn_launch(dtype, dkp, dvp, dk, Q, K, V, O, O_lo, B, H, Tq, Tk, ldq, ldk, ldv, ldo, sQb, sKb, sVb, sOb, kv_mask,
+                        q_mask, workspace, (hipStream_t)stream, Q_lo, K_lo);
+}
+
 }  // extern "C"

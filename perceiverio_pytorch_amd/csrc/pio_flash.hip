@@ -14,6 +14,11 @@
 //     XOR swizzle applied on the source address and on the ds_read side (conflict-free K reads, 2-way V^T reads).
 //   * V is consumed K-contiguous (V^T [dv][keys]), which is exactly what the V projection GEMM writes.
 //   * online softmax in base 2 (scale folded into the exponent constant), fp32 statistics and accumulators.
+//   * QK_PAIR (DK = 32, fp16): Q and K arrive as (hi, lo) pairs and S^T = K_lo Q_hi^T + K_hi Q_lo^T + K_hi Q_hi^T,
+//     accumulated in fp32 IN THAT ORDER (the two small products first, the large one last); lo x lo is dropped.  Q_lo is
+//     a second set of register fragments, K_lo a second K tile in every ring stage (same pieces, same swizzle, same
+//     conflict-free reads, same single barrier per tile).  Everything behind S^T is unchanged; the output may leave as a
+//     pair (O_lo: the rounding residual), which the split-operand out projection behind the core consumes.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -35,6 +40,8 @@ struct FlashParams {
     int64_t sQb, sKb, sVb, sOb;  // batch strides (elements); 0 for a batch-invariant Q
     float scale_log2;            // log2(e) / sqrt(dk)
     int o_rows16;                // O rows are 16-byte aligned: the epilogue may store whole 16-byte chunks
+    const void *Q_lo, *K_lo;     // QK_PAIR instantiations only: the rounding residuals of Q / K (same strides)
+    void *O_lo;                  // QK_PAIR instantiations only (optional): o - float(O); the launcher clears o_rows16 with it
 };
 
 static __device__ __attribute__((aligned(16))) uint32_t g_zero_chunk_f[4] = {0, 0, 0, 0};
@@ -61,8 +68,9 @@ __device__ __forceinline__ int vrow_swz(int r) {
 // (two waves per SIMD: one wave's dependent MFMA -> exp2 -> MFMA chain covers the other's) and merge (m, l, O) through
 // LDS at the end.  For the shapes that offer only one 4-wave workgroup per CU: the flow stack (16 heads x 2048 latents:
 // 256 workgroups of ~1 900 cycles per 64-key tile against 256 cycles of MFMAs), small ImageNet batches.
-template <int DT, int DK, int DV, bool VROW, int NW, int KS = 1>
+template <int DT, int DK, int DV, bool VROW, int NW, int KS = 1, bool QK_PAIR = false>
 __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void flash_attn_kernel(const FlashParams p) {
+    static_assert(!QK_PAIR || (DK == 32 && DT == PIO_DT_F16), "pair-operand Q K^T: the DK = 32 fp16 instantiations");
     typedef typename Op<DT>::T T;
     typedef typename Op<DT>::V8 V8;
     typedef typename Op<DT>::V4 V4;
@@ -70,6 +78,7 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void flash_attn_kernel(co
     static_assert(!VROW || DV == 128 || DV == 64 || DV == 32 || DV == 160, "row-major V: swizzles exist for these widths");
     constexpr int KT = 64;                       // keys per tile
     constexpr int K_TILE = KT * DK * 2;          // bytes
+    constexpr int K_STG = QK_PAIR ? 2 * K_TILE : K_TILE;   // K part of a ring stage: the K tile (+ the K_lo tile behind it)
     constexpr int V_TILE = DV * KT * 2;          // bytes
     constexpr int KCPR = DK / 8;                 // 16-byte chunks per K row (4, 8, 16)
     constexpr int KRPB = 16 / KCPR;              // K rows per 256-byte bank row
@@ -81,7 +90,7 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void flash_attn_kernel(co
     static_assert(KS == 1 || ((KS == 2 || KS == 4) && NW == 4 * KS), "key split: KS groups of four waves");
     constexpr int NWQ = NW / KS;                 // waves along the query axis
     constexpr int MRG = KS > 1 ? (KS - 1) * NWQ * 64 * (NDT * 16 + 2) * 4 : 0;   // merge area: (O^T, m, l) of the other key parts
-    constexpr int RING = 2 * KS * (K_TILE + V_TILE), OSTG = NW * 32 * OROW;
+    constexpr int RING = 2 * KS * (K_STG + V_TILE), OSTG = NW * 32 * OROW;
     constexpr int SM0 = RING > OSTG ? RING : OSTG;
     __shared__ __attribute__((aligned(16))) char smem[SM0 > MRG ? SM0 : MRG];
 
@@ -103,16 +112,19 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void flash_attn_kernel(co
     const T *Kg = (const T *)p.K + b * p.sKb + (int64_t)h * DK;
     const T *Vg = (const T *)p.VT + b * p.sVb + (VROW ? (int64_t)h * DV : (int64_t)h * DV * p.ldvt);
     const T *zsrc = (const T *)g_zero_chunk_f;
+    const T *Klg = nullptr;
+    if constexpr (QK_PAIR) Klg = (const T *)p.K_lo + b * p.sKb + (int64_t)h * DK;
 
     V8 qf[NQS];  // Q fragments (B operand), loaded behind the first tile's request: the two latencies overlap
+    V8 ql[QK_PAIR ? NQS : 1];  // QK_PAIR: the Q_lo fragments, same layout
 
     const int ntiles_all = (p.Tk + KT - 1) / KT;
     const int ntiles = ntiles_all / KS;          // (KS == 2: an even tile count -- launcher) tiles of this key half
     const int tile0 = kh * ntiles;               // its first tile
 
     auto stage = [&](int kt, int buf) {          // tile kt of THIS key half, staged by the half's NWQ waves
-        char *kb = smem + (buf * KS + kh) * (K_TILE + V_TILE);
-        char *vb = kb + K_TILE;
+        char *kb = smem + (buf * KS + kh) * (K_STG + V_TILE);
+        char *vb = kb + K_STG;
         const int k0 = (tile0 + kt) * KT;
         // K tile: piece = 64 chunks = 64/KCPR rows
         for (int pc = qb; pc < K_PIECES; pc += NWQ) {
@@ -124,6 +136,10 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void flash_attn_kernel(co
             const T *src = Kg + (int64_t)key * p.ldk + c * 8;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                              (__attribute__((address_space(3))) void *)(kb + pc * 1024), 16, 0, 0);
+            if constexpr (QK_PAIR)   // the K_lo tile: same rows, same chunk order, K_TILE bytes further
+                __builtin_amdgcn_global_load_lds(
+                    (const __attribute__((address_space(1))) void *)(Klg + (int64_t)key * p.ldk + c * 8),
+                    (__attribute__((address_space(3))) void *)(kb + K_TILE + pc * 1024), 16, 0, 0);
         }
         if constexpr (VROW) {
             // row-major V tile [64 keys][DV]: DV / 8 chunks per row, a 1-KiB piece = 64 consecutive chunks
@@ -176,13 +192,18 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void flash_attn_kernel(co
         const T *qrow = Qg + (int64_t)q * p.ldq + 8 * hh;
 #pragma unroll
         for (int s = 0; s < NQS; ++s) qf[s] = *(const V8 *)(qrow + 16 * s);
+        if constexpr (QK_PAIR) {
+            const T *lrow = (const T *)p.Q_lo + b * p.sQb + (int64_t)h * DK + (int64_t)q * p.ldq + 8 * hh;
+#pragma unroll
+            for (int s = 0; s < NQS; ++s) ql[s] = *(const V8 *)(lrow + 16 * s);
+        }
     }
     for (int kt = 0; kt < ntiles; ++kt) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (kt + 1 < ntiles) stage(kt + 1, (kt + 1) & 1);
-        const char *kb = smem + ((kt & 1) * KS + kh) * (K_TILE + V_TILE);
-        const char *vb = kb + K_TILE;
+        const char *kb = smem + ((kt & 1) * KS + kh) * (K_STG + V_TILE);
+        const char *vb = kb + K_STG;
 
         // ---- S^T = K Q^T for the two 32-key halves
         f32x16 sacc[2];
@@ -190,6 +211,23 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void flash_attn_kernel(co
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
             for (int j = 0; j < 16; ++j) sacc[t][j] = 0.f;
+            if constexpr (QK_PAIR) {
+                // the small products first (K_lo Q_hi^T, then K_hi Q_lo^T), the large one last; every K fragment is read
+                // from LDS once
+                V8 kh_f[NQS], kl_f[NQS];
+#pragma unroll
+                for (int s = 0; s < NQS; ++s) {
+                    const int chunk = (2 * s + hh) ^ k_swz;
+                    kh_f[s] = *(const V8 *)(kb + k_off[t] + chunk * 16);
+                    kl_f[s] = *(const V8 *)(kb + K_TILE + k_off[t] + chunk * 16);
+                }
+#pragma unroll
+                for (int s = 0; s < NQS; ++s) sacc[t] = Op<DT>::mfma32(kl_f[s], qf[s], sacc[t]);
+#pragma unroll
+                for (int s = 0; s < NQS; ++s) sacc[t] = Op<DT>::mfma32(kh_f[s], ql[s], sacc[t]);
+#pragma unroll
+                for (int s = 0; s < NQS; ++s) sacc[t] = Op<DT>::mfma32(kh_f[s], qf[s], sacc[t]);
+            } else
 #pragma unroll
             for (int s = 0; s < NQS; ++s) {
                 const int chunk = (2 * s + hh) ^ k_swz;
@@ -363,6 +401,15 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void flash_attn_kernel(co
 #pragma unroll
                 for (int j = 0; j < 4; ++j) o[j] = Op<DT>::from_f32(oacc[d][4 * g4 + j] * inv);
                 *(V4 *)(orow + 32 * d + 8 * g4 + 4 * hh) = o;
+                if constexpr (QK_PAIR) {
+                    if (p.O_lo) {  // the output as a pair: lo = o - float(hi)
+                        V4 l;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            l[j] = Op<DT>::from_f32(oacc[d][4 * g4 + j] * inv - Op<DT>::to_f32(o[j]));
+                        *(V4 *)((T *)p.O_lo + (orow - (T *)p.O) + 32 * d + 8 * g4 + 4 * hh) = l;
+                    }
+                }
             }
     }
 }
@@ -374,6 +421,10 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void flash_attn_kernel(co
 bool flash_supported(int dkp, int dvp) {
     return (dkp == 128 && dvp == 128) || (dkp == 64 && dvp == 64) || (dkp == 32 && dvp == 32) ||
            (dkp == 32 && dvp == 160);
+}
+// pair-operand Q K^T: the DK = 32 instantiations, fp16
+bool flash_pair_supported(int dtype, int dkp, int dvp) {
+    return dtype == PIO_DT_F16 && dkp == 32 && (dvp == 32 || dvp == 160);
 }
 
 #ifdef PIO_EXPERIMENTS
@@ -396,9 +447,14 @@ extern "C" int pio_debug_flash_variant(int which) { return flash_variant_overrid
 // v_rowmajor: VT points at V [B][Tk][.. h*dvp ..] (row stride ldvt) instead of V^T [B][H*dvp][Tk].
 int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const void *Q, const void *K, const void *VT,
                            void *O, int B, int H, int Tq, int Tk, int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo,
-                           int64_t sQb, int64_t sKb, int64_t sVb, int64_t sOb, bool v_rowmajor, hipStream_t s) {
+                           int64_t sQb, int64_t sKb, int64_t sVb, int64_t sOb, bool v_rowmajor, hipStream_t s,
+                           const void *Q_lo, const void *K_lo, void *O_lo) {
     if (!flash_supported(dkp, dvp)) return PIO_E_SHAPE;
     if (!Q || !K || !VT || !O) return PIO_E_ARG;
+    const bool pair = Q_lo || K_lo;  // Q and K as (hi, lo) pairs: both halves or neither; O_lo only with them
+    if ((pair && !(Q_lo && K_lo)) || (O_lo && !pair)) return PIO_E_ARG;
+    if (pair && !flash_pair_supported(dtype, dkp, dvp)) return PIO_E_SHAPE;  // (never a silent single-operand run)
+    if (((uintptr_t)Q_lo & 15) || ((uintptr_t)K_lo & 15) || ((uintptr_t)O_lo & 7)) return PIO_E_ALIGN;
     if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || (int64_t)B * H * ((Tq + 127) / 128) > 0x7fffffffLL) return PIO_E_SHAPE;
     if ((ldq % 8) || (ldk % 8) || (ldvt % 8) || (ldo % 4) || (sQb % 8) || (sKb % 8) || (sVb % 8) || (sOb % 4))
         return PIO_E_ALIGN;
@@ -408,9 +464,10 @@ int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const vo
     // (64-row workgroups for small batches -- B = 1: 64 workgroups instead of 32 -- were measured in round 3: 4.00 ms
     //  against 3.82 ms per B = 1 forward; two waves issuing a whole tile's DMA cost more than the idle CUs: not kept)
     const int nqt = wide ? (Tq + 255) / 256 : (Tq + 127) / 128;
-    const int o_rows16 = (ldo % 8 == 0 && sOb % 8 == 0 && ((uintptr_t)O & 15) == 0) ? 1 : 0;
+    // (an output PAIR leaves through the per-lane 8-byte stores: the staged whole-row epilogue carries one half only)
+    const int o_rows16 = (!O_lo && ldo % 8 == 0 && sOb % 8 == 0 && ((uintptr_t)O & 15) == 0) ? 1 : 0;
     FlashParams p{Q, K, VT, O, Tq, Tk, H, nqt, ldq, ldk, ldvt, ldo, sQb, sKb, sVb, sOb,
-                  1.4426950408889634f / sqrtf((float)dk_logical), o_rows16};
+                  1.4426950408889634f / sqrtf((float)dk_logical), o_rows16, Q_lo, K_lo, O_lo};
     dim3 grid((unsigned)(nqt * B * H), 1, 1);
     dim3 block(wide ? 512 : 256, 1, 1);
     ProfScope prof(PROF_FLASH, 2.0 * B * H * (double)Tq * Tk * (dkp + dvp),
@@ -442,6 +499,28 @@ int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const vo
                         (int64_t)B * H * nqt <= cu_budget();
     // (four key parts = 16 waves per workgroup, four per SIMD: the narrow heads, whose waves need < 128 registers)
     const bool ksplit4 = ksplit && dkp <= 64 && dvp <= 64 && Tk >= 1024 && (Tk % 256) == 0;
+    if (pair) {
+        // the same kernel choice as below, on the QK_PAIR instantiation of each variant
+#define PIO_FLASH_PAIR(DVV, VROWV, NWV, KSV) \
+    hipLaunchKernelGGL((flash_attn_kernel<PIO_DT_F16, 32, DVV, VROWV, NWV, KSV, true>), grid, block, 0, s, p)
+#define PIO_FLASH_PAIR_DV(VROWV, NWV, KSV)                \
+    do {                                                  \
+        if (dvp == 32) PIO_FLASH_PAIR(32, VROWV, NWV, KSV); \
+        else PIO_FLASH_PAIR(160, VROWV, NWV, KSV);        \
+    } while (0)
+        if (ksplit4) {  // (dvp <= 64: the (32, 32) heads)
+            block = dim3(1024, 1, 1);
+            PIO_FLASH_PAIR(32, true, 16, 4);
+        } else if (ksplit) {
+            block = dim3(512, 1, 1);
+            PIO_FLASH_PAIR_DV(true, 8, 2);
+        } else if (v_rowmajor && wide) PIO_FLASH_PAIR_DV(true, 8, 1);
+        else if (v_rowmajor) PIO_FLASH_PAIR_DV(true, 4, 1);
+        else PIO_FLASH_PAIR_DV(false, 4, 1);
+#undef PIO_FLASH_PAIR_DV
+#undef PIO_FLASH_PAIR
+        return launch_status();
+    }
 #ifdef PIO_EXPERIMENTS
     const bool pipe = variant == 1, stagger = variant == 2;
     if (v_rowmajor && Tq >= 256 && Tk % 128 == 0 && pipe && o_rows16) {

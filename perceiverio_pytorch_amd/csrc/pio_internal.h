@@ -117,16 +117,21 @@ int softmax_rows_launch(const float *S, int64_t lds, void *P, void *P_lo, int64_
                         float scale, const uint8_t *kv_mask, const uint8_t *q_mask, const uint8_t *full_mask,
                         const float *bias, int dtype, float *probs_out, hipStream_t s);
 bool flash_supported(int dkp, int dvp);
+// Q / K as (hi, lo) pairs inside the fused cores' Q K^T (S = Q_hi K_hi + Q_lo K_hi + Q_hi K_lo): the dk <= 32 fp16
+// instantiations of both kernel families.  A launch with Q_lo / K_lo on any other shape or dtype is PIO_E_SHAPE.
+bool flash_pair_supported(int dtype, int dkp, int dvp);
+bool xattn_pair_supported(int dtype, int dkp, int dvp);
 int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const void *Q, const void *K, const void *VT,
                            void *O, int B, int H, int Tq, int Tk, int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo,
-                           int64_t sQb, int64_t sKb, int64_t sVb, int64_t sOb, bool v_rowmajor, hipStream_t s);
+                           int64_t sQb, int64_t sKb, int64_t sVb, int64_t sOb, bool v_rowmajor, hipStream_t s,
+                           const void *Q_lo = nullptr, const void *K_lo = nullptr, void *O_lo = nullptr);
 // fused cross-attention (pio_xattn.hip): wide single heads, dv != dk, key / query mask vectors, key splits
 bool xattn_supported(int dkp, int dvp);
 size_t xattn_partial_bytes(int dkp, int dvp, int B, int H, int Tq, int Tk);  // fp32 partials of the key splits (0: none)
 int xattn_launch(int dtype, int dkp, int dvp, int dk_logical, const void *Q, const void *K, const void *VT, void *O,
                  void *O_lo, int B, int H, int Tq, int Tk, int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo, int64_t sQb,
                  int64_t sKb, int64_t sVb, int64_t sOb, const uint8_t *kv_mask, const uint8_t *q_mask, void *partials,
-                 hipStream_t s);
+                 hipStream_t s, const void *Q_lo = nullptr, const void *K_lo = nullptr);
 // fused cross-attention for a head wider than the key axis is long (pio_xtall.hip): Tk <= 512, S computed once per query
 // row and kept in registers (the ImageNet decoder's 1024-wide head over 512 latents)
 bool xtall_supported(int dkp, int dvp, int Tk);

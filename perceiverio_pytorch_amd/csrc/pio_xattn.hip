@@ -26,6 +26,12 @@
 //     as zeros -- the reference's "wipe" (transformer_primitives.py:168-175) -- and so is a row whose query mask is 0.
 //   * nothing is zero-filled in LDS: pad chunks of K beyond dkp meet zero Q fragments, V^T rows beyond dvp feed output
 //     rows that are never stored, keys beyond Tk have p = 0; their sources are clamped to valid (finite) data.
+//   * QK_PAIR (the dk <= 32 instantiations, fp16): Q and K arrive as (hi, lo) pairs and S^T = K_lo Q_hi^T + K_hi Q_lo^T +
+//     K_hi Q_hi^T, accumulated in fp32 IN THAT ORDER (the two small products first, the large one last); lo x lo is
+//     dropped.  Q_lo is a second set of register fragments; K_lo rides in the K tile's own rows: a dk = 32 row uses chunks
+//     0..3 of its 16-chunk (256-byte) LDS row, K_lo goes to logical chunks 4..7 -- same pieces, same swizzle, same
+//     conflict-free ds_read_b128 (k-steps 2 and 3 of the row), no extra LDS, no extra barrier.  Everything behind S^T
+//     (scale, masks, softmax, P rounded once, P V, key splits, the O / O_lo pair, the wipe) is the code above, unchanged.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -53,6 +59,7 @@ struct XattnParams {
     int Tq, Tk, H, nqt, nslice, nsplit, tiles_per_split, dkp, dvp;
     int64_t ldq, ldk, ldvt, ldo, sQb, sKb, sVb, sOb;
     float scale_log2;  // log2(e) / sqrt(dk)
+    const void *Q_lo, *K_lo;  // QK_PAIR instantiations only: the rounding residuals of Q / K (same strides as Q / K)
 };
 
 __device__ __forceinline__ void xattn_dma16(const void *src, void *lds) {
@@ -93,8 +100,9 @@ __device__ __forceinline__ void xa_mfma_a(f32x16 &c, typename Op<DT>::V8 a, type
     else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
 }
 
-template <int DT, int DKL, int DVS>
+template <int DT, int DKL, int DVS, bool QK_PAIR = false>
 __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn_kernel(const XattnParams p) {
+    static_assert(!QK_PAIR || (DKL == 32 && DT == PIO_DT_F16), "pair-operand Q K^T: the dk <= 32 fp16 instantiations");
     typedef typename Op<DT>::T T;
     typedef typename Op<DT>::V8 V8;
     typedef typename Op<DT>::V4 V4;
@@ -151,6 +159,17 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
 #pragma unroll
         for (int s = 0; s < NQS; ++s) qf[s] = (16 * s + 8 * hh < p.dkp) ? *(const V8 *)(qrow + 16 * s) : zero8;
     }
+    V8 ql[QK_PAIR ? NQS : 1];  // QK_PAIR: the Q_lo fragments, same layout
+    const T *Klg = nullptr;
+    if constexpr (QK_PAIR) {
+        Klg = (const T *)p.K_lo + b * p.sKb + (int64_t)h * p.dkp;
+        int q = q0 + r32;
+        q = q < p.Tq ? q : p.Tq - 1;
+        const T *qrow = (const T *)p.Q_lo + b * p.sQb + (int64_t)h * p.dkp + (int64_t)q * p.ldq + 8 * hh;
+        const V8 zero8 = {};
+#pragma unroll
+        for (int s = 0; s < NQS; ++s) ql[s] = (16 * s + 8 * hh < p.dkp) ? *(const V8 *)(qrow + 16 * s) : zero8;
+    }
 
     const int ntiles = (p.Tk + KT - 1) / KT;
     const int t_begin = sp * p.tiles_per_split;
@@ -166,6 +185,7 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
         const int ci = pc * 64 + lane;               // LDS chunk index inside the K tile
         const int row = ci / KCH, pos = ci % KCH;
         int c = (pos & ~15) | ((pos ^ row) & 15);    // the logical chunk stored at this position
+        if constexpr (QK_PAIR) c = (c >= 4 && c < 8) ? c - 4 : c;  // logical chunks 4..7: chunks 0..3 of the K_lo row
         c = c * 8 < p.dkp ? c : (p.dkp >> 3) - 1;    // pad chunks: any finite data (their Q fragment is zero)
         const int key = (row & ~12) | ((row & 4) << 1) | ((row & 8) >> 1);  // tile row -> key: bits 2, 3 swapped
         return (uint32_t)(key * (int)p.ldk + c * 8);
@@ -177,7 +197,18 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
         row = d0 + row < p.dvp ? row : p.dvp - 1 - d0;   // rows beyond dvp: finite data, never stored
         return (uint32_t)(row * (int)p.ldvt + kcol);
     };
+    auto k_from_lo = [&](int pc) -> bool {           // QK_PAIR: this lane's chunk of piece pc comes from K_lo
+        const int ci = pc * 64 + lane;
+        const int row = ci / KCH, pos = ci % KCH;
+        const int c = (pos & ~15) | ((pos ^ row) & 15);
+        return c >= 4 && c < 8;
+    };
     uint32_t koff[KPW], voff[VPW];   // (element offsets < 2^31: launcher)
+    bool klo[QK_PAIR ? KPW : 1];
+    if constexpr (QK_PAIR) {
+#pragma unroll
+        for (int i = 0; i < KPW; ++i) klo[i] = k_from_lo(wave + 4 * i < K_PIECES ? wave + 4 * i : wave);
+    }
 #pragma unroll
     for (int i = 0; i < KPW; ++i) koff[i] = k_source(wave + 4 * i < K_PIECES ? wave + 4 * i : wave);
 #pragma unroll
@@ -189,18 +220,20 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
     // every wave left before the barrier at the top of tile kt.
     char *stage_kb = nullptr, *stage_vb = nullptr;
     int stage_step = 0;
-    const T *stage_k = Kg, *stage_v = Vg;
+    const T *stage_k = Kg, *stage_v = Vg, *stage_kl = Klg;
     auto stage_begin = [&](int kt, int slot, bool real) {
         if (real) {
             stage_kb = smem + slot * STAGE + wave * 1024;
             stage_vb = stage_kb + K_TILE;
             stage_step = 4096;
             stage_k = Kg + (int64_t)kt * KT * p.ldk;
+            if constexpr (QK_PAIR) stage_kl = Klg + (int64_t)kt * KT * p.ldk;
             stage_v = Vg + kt * KT;
         } else {
             stage_kb = stage_vb = smem + SINK + wave * 1024;
             stage_step = 0;
             stage_k = Kg;
+            if constexpr (QK_PAIR) stage_kl = Klg;
             stage_v = Vg;
         }
     };
@@ -213,7 +246,9 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
             asm volatile("" : "+v"(o));
             char *dst = (4 * i + 4 <= K_PIECES || wave + 4 * i < K_PIECES) ? stage_kb + i * stage_step
                                                                           : smem + SINK + wave * 1024;
-            xattn_dma16((const char *)stage_k + 2 * (uint64_t)o, dst);
+            // (QK_PAIR: every piece holds chunks of both halves -- the base is chosen per lane)
+            if constexpr (QK_PAIR) xattn_dma16((const char *)(klo[i] ? stage_kl : stage_k) + 2 * (uint64_t)o, dst);
+            else xattn_dma16((const char *)stage_k + 2 * (uint64_t)o, dst);
         } else {
             constexpr int j = i - KPW;
             uint32_t &o = voff[j];
@@ -282,8 +317,26 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
             for (int j = 0; j < 16; ++j) sacc[j] = 0.f;
         }
         constexpr int RK = NQS < RING ? NQS : RING;
-        V8 kf[RK];
+        V8 kf[QK_PAIR ? 2 * NQS : RK];
         auto k_read = [&](int sx) { return *(const V8 *)(kb + kaddr[sx & 7] + 256 * (sx >> 3)); };
+        if constexpr (QK_PAIR) {
+            // K_hi fragments are k-steps 0 .. NQS-1 of the row, K_lo fragments k-steps NQS .. 2 NQS-1 (chunks 4..7).
+            // Order of the fp32 accumulation: K_lo Q_hi^T, K_hi Q_lo^T (the small products), then K_hi Q_hi^T.
+            static_assert(NQS == 2 && 2 * NQS <= RING, "pair fragments: all four in flight at once");
+#pragma unroll
+            for (int i = 0; i < 2 * NQS; ++i) kf[i] = k_read(i);
+            __builtin_amdgcn_sched_barrier(0);
+            xa_for<0, 3 * NQS>([&](auto JI) {
+                constexpr int j = decltype(JI)::value;
+                constexpr int which = j / NQS, sx = j % NQS;
+                if constexpr (which == 0) sacc = Op<DT>::mfma32(kf[NQS + sx], qf[sx], sacc);
+                else if constexpr (which == 1) sacc = Op<DT>::mfma32(kf[sx], ql[sx], sacc);
+                else sacc = Op<DT>::mfma32(kf[sx], qf[sx], sacc);
+                if constexpr (j < KPW + VPW) stage_piece(std::integral_constant<int, j>{});
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            xa_for<3 * NQS, KPW + VPW>([&](auto PI) { stage_piece(PI); });
+        } else {
 #pragma unroll
         for (int i = 0; i < RK; ++i) kf[i] = k_read(i);
         __builtin_amdgcn_sched_barrier(0);
@@ -297,6 +350,7 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
             __builtin_amdgcn_sched_barrier(0);
         });
         xa_for<NQS, KPW + VPW>([&](auto PI) { stage_piece(PI); });
+        }
         // first V^T fragments: in flight during the softmax arithmetic.  Fragment f = 2 d + s2 (d tile, k-step).
         constexpr int NVF = 2 * NDT, RV = NVF < RING ? NVF : RING;
         V8 vf[RV];
@@ -529,6 +583,11 @@ const XCfg *xattn_cfg(int dkp, int dvp) {
 }  // namespace
 
 bool xattn_supported(int dkp, int dvp) { return xattn_cfg(dkp, dvp) != nullptr; }
+// pair-operand Q K^T: the narrow-head instantiations <32, 96> and <32, 160>, fp16
+bool xattn_pair_supported(int dtype, int dkp, int dvp) {
+    const XCfg *c = xattn_cfg(dkp, dvp);
+    return dtype == PIO_DT_F16 && c && c->dkl == 32;
+}
 
 // key splits for a launch: about one workgroup per CU and resident slot (wide heads hold one workgroup per CU, narrow
 // ones two) when batch x heads x query tiles x slices alone give clearly fewer, each split keeping >= 8 key tiles.
@@ -556,10 +615,14 @@ size_t xattn_partial_bytes(int dkp, int dvp, int B, int H, int Tq, int Tk) {
 int xattn_launch(int dtype, int dkp, int dvp, int dk_logical, const void *Q, const void *K, const void *VT, void *O,
                  void *O_lo, int B, int H, int Tq, int Tk, int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo, int64_t sQb,
                  int64_t sKb, int64_t sVb, int64_t sOb, const uint8_t *kv_mask, const uint8_t *q_mask, void *partials,
-                 hipStream_t s) {
+                 hipStream_t s, const void *Q_lo, const void *K_lo) {
     const XCfg *c = xattn_cfg(dkp, dvp);
     if (!c) return PIO_E_SHAPE;
     if (!Q || !K || !VT || !O) return PIO_E_ARG;
+    const bool pair = Q_lo || K_lo;  // Q and K as (hi, lo) pairs: both halves or neither
+    if (pair && !(Q_lo && K_lo)) return PIO_E_ARG;
+    if (pair && !xattn_pair_supported(dtype, dkp, dvp)) return PIO_E_SHAPE;  // (never a silent single-operand run)
+    if (((uintptr_t)Q_lo & 15) || ((uintptr_t)K_lo & 15)) return PIO_E_ALIGN;
     if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || (dkp & 7) || (dvp & 7)) return PIO_E_SHAPE;
     if ((ldq % 8) || (ldk % 8) || (ldvt % 8) || (ldo % 4) || (sQb % 8) || (sKb % 8) || (sVb % 8) || (sOb % 4))
         return PIO_E_ALIGN;
@@ -577,6 +640,7 @@ int xattn_launch(int dtype, int dkp, int dvp, int dk_logical, const void *Q, con
     if (nwg > 0x7fffffffLL) return PIO_E_SHAPE;
     XattnParams p{};
     p.Q = Q; p.K = K; p.VT = VT; p.O = O; p.O_lo = O_lo;
+    p.Q_lo = Q_lo; p.K_lo = K_lo;
     p.key_bits = kv_mask ? (const uint32_t *)partials : nullptr;
     p.part_o = (float *)((char *)partials + keybits_bytes(B, Tk));
     p.part_ml = nsplit > 1 ? p.part_o + (size_t)B * H * nsplit * Tq * dvp : nullptr;
@@ -600,7 +664,9 @@ int xattn_launch(int dtype, int dkp, int dvp, int dk_logical, const void *Q, con
         if (dtype == PIO_DT_F16) hipLaunchKernelGGL((xattn_kernel<PIO_DT_F16, DKLV, DVSV>), grid, block, 0, s, p); \
         else hipLaunchKernelGGL((xattn_kernel<PIO_DT_BF16, DKLV, DVSV>), grid, block, 0, s, p);               \
     } while (0)
-        if (c->dkl == 32 && c->dvs == 96) PIO_XA(32, 96);
+        if (pair && c->dvs == 96) hipLaunchKernelGGL((xattn_kernel<PIO_DT_F16, 32, 96, true>), grid, block, 0, s, p);
+        else if (pair) hipLaunchKernelGGL((xattn_kernel<PIO_DT_F16, 32, 160, true>), grid, block, 0, s, p);
+        else if (c->dkl == 32 && c->dvs == 96) PIO_XA(32, 96);
         else if (c->dkl == 32) PIO_XA(32, 160);
         else if (c->dkl == 128) PIO_XA(128, 128);
         else if (c->dkl == 352) PIO_XA(352, 352);

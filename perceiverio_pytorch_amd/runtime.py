@@ -32,6 +32,12 @@ _POLICIES = {"fp16": (L.PIO_DT_F16, 0, False), "fp16x2s": (L.PIO_DT_F16, 1, Fals
              # x3f: every GEMM with split operands as x3, but the attention core (Q K^T, softmax, P V) single-sweep on
              # the fused kernels (q / k / v / p rounded once; the core's output leaves as a pair): no score matrix
              "fp16x3f": (L.PIO_DT_F16, 3, True), "bf16x3f": (L.PIO_DT_BF16, 3, True),
+             # x3fq: "x3f" with Q and K entering the fused core as (hi, lo) pairs -- S = Q_hi K_hi + Q_lo K_hi + Q_hi K_lo
+             # inside the kernel (pio_attention_t.act_split = 3): the one rounding "x3f" leaves in front of the exponent is
+             # gone, still no score matrix.  For models whose logits are large (trained LayerNorm gains: |s| ~ 10-15).
+             # Pair cores exist for fp16 heads of dk <= 32; any other shape runs the materialised path of "x3" (fp16 only:
+             # there is no bf16 pair core, hence no "bf16x3fq")
+             "fp16x3fq": (L.PIO_DT_F16, 3, True),
              # x2af: split ACTIVATIONS against single weights (A_hi B^T + A_lo B^T: two sweeps) around a single-sweep
              # fused attention core -- for decoders whose error is dominated by the rounding of wide-range inputs
              # (Fourier / position features of dense outputs), at 2/3 of the x3f cost
@@ -54,7 +60,8 @@ _POLICIES = {"fp16": (L.PIO_DT_F16, 0, False), "fp16x2s": (L.PIO_DT_F16, 1, Fals
 # weights split under the fine policies (beside the level of _POLICIES): Attention: proj_v, final; MLP: fc1, fc2; decoder:
 # final_layer; heads behind the decoder (hip_linear): post
 _FINE_SPLIT = {"fp16x2o": {"final"}, "fp16x2v": {"proj_v"}, "fp16x2afo": {"final", "final_layer", "post"}}
-_FUSED_CORE = {"fp16x3f", "bf16x3f", "fp16x2af", "fp16x2afo"}
+_FUSED_CORE = {"fp16x3f", "bf16x3f", "fp16x2af", "fp16x2afo", "fp16x3fq"}
+_PAIR_CORE = {"fp16x3fq"}      # ... of which: Q / K as pairs inside the core's Q K^T
 _BLOCK_FEEDBACK = {"fp16sd"}
 _policy = os.environ.get("PIO_PRECISION", "fp16x3")
 if _policy not in _POLICIES:
@@ -187,6 +194,19 @@ def policy_fine_split(name: Optional[str] = None) -> set:
 def policy_core_single(name: Optional[str] = None) -> bool:
     """True for the "x3f" policies: split operands in the projections, single-sweep fused attention core."""
     return (name or _policy) in _FUSED_CORE
+
+
+def policy_core_pair(name: Optional[str] = None) -> bool:
+    """True for "fp16x3fq": a fused-core policy whose core takes Q and K as (hi, lo) pairs (act_split = 3)."""
+    return (name or _policy) in _PAIR_CORE
+
+
+def attention_act_split(name: Optional[str] = None) -> int:
+    """pio_attention_t.act_split of a policy: 0 single activations, 1 split everywhere (materialised core), 2 split
+    projections around the single-operand fused core, 3 the same with pair-operand Q K^T in the core."""
+    if not _POLICIES[name or _policy][2]:
+        return 0
+    return 3 if policy_core_pair(name) else 2 if policy_core_single(name) else 1
 
 
 def policy_block_feedback(name: Optional[str] = None) -> bool:

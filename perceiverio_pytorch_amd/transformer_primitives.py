@@ -149,7 +149,7 @@ class Attention(_HipModule):
         dk, dv = self._qk_channels_per_head, self._v_channels_per_head
         d = L.Attention(q.desc, k.desc, v.desc, o.desc, H, dk, dv, R.pad8(dk), R.pad8(dv),
                         self.proj_q.in_features, self.proj_k.in_features, self.proj_v.in_features,
-                        self.final.out_features, dtype, (2 if R.policy_core_single() else 1) if split else 0)
+                        self.final.out_features, dtype, R.attention_act_split())
         keep = [q, k, v, o]
         # K / V projection fold of a single-head cross-attend (pio_attention_t.kq / vo; SURVEY.md section 7 "legal algebraic
         # restructurings", reference :93-95,138,163): q (x Wk^T + bk)^T = (q Wk) x^T + const and

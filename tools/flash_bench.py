@@ -1,5 +1,7 @@
 """Dev tool (GPU): device time of the fused SELF-attention kernel on the hot shape (B x 512 latents x 8 heads of 128,
-V row-major out of the fused q|k|v GEMM).  PIO_FLASH_PIPE=0 selects the lock-step 8-wave kernel for comparison."""
+V row-major out of the fused q|k|v GEMM).  PIO_FLASH_PIPE=0 selects the lock-step 8-wave kernel for comparison.
+--pair: the language model's stack shape instead (B x 256 latents x 8 heads of (32, 160)) under "fp16x3fq" -- the pair-operand
+flash_attn_kernel<32,160> -- and under "fp16x3f" (single-operand xattn_kernel<32,160>), B = 2 and 100."""
 import ctypes as C
 import os
 import sys
@@ -15,10 +17,14 @@ from perceiverio_pytorch_amd.transformer_primitives import SelfAttention  # noqa
 def main():
     lib = P.lib()
     dev = torch.device("cuda:0")
-    P.set_precision_policy("fp16")
-    for B, T in ((32, 512), (32, 1024), (4, 512)):
-        m = SelfAttention(1024, widening_factor=1, num_heads=8).to(dev).eval()
-        x = torch.randn(B, T, 1024, device=dev)
+    pair = "--pair" in sys.argv
+    runs = ([(B, 256, 1280, pol) for B in (2, 100) for pol in ("fp16x3f", "fp16x3fq")] if pair
+            else [(B, T, 1024, "fp16") for B, T in ((32, 512), (32, 1024), (4, 512))])
+    for B, T, D, policy in runs:
+        P.set_precision_policy(policy)
+        m = (SelfAttention(D, widening_factor=1, num_heads=8, qk_channels=256) if pair
+             else SelfAttention(D, widening_factor=1, num_heads=8)).to(dev).eval()
+        x = torch.randn(B, T, D, device=dev)
         with torch.no_grad():
             for _ in range(3):
                 y = m(x)
@@ -31,7 +37,7 @@ def main():
             lib.pio_prof_end(ms, fl, by, ln)
         us = ms[5] / n * 1e3
         print("   per class us per forward:", {k: round(ms[k] / n * 1e3, 1) for k in range(9) if ms[k] > 0}, flush=True)
-        print(f"B={B} T={T}: fused self-attention {us:8.1f} us ({fl[5] / n / (us * 1e-6) / 1e12:7.1f} algorithmic "
+        print(f"[{policy}] B={B} T={T} D={D}: fused self-attention {us:8.1f} us ({fl[5] / n / (us * 1e-6) / 1e12:7.1f} algorithmic "
               f"TFLOP/s, {ln[5] // n} launches) PIO_FLASH_PIPE={os.environ.get('PIO_FLASH_PIPE', '1')} "
               f"checksum {float(y.double().abs().mean()):.6f}", flush=True)
 

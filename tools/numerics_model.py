@@ -12,11 +12,15 @@ import perceiver_oracle as O  # noqa: E402
 
 
 class Rounder:
-    def __init__(self, dtype="f16", points=None, w_passes=2, fold=False):
+    def __init__(self, dtype="f16", points=None, w_passes=2, fold=False, pair=()):
         self.dtype = dtype
         self.points = points  # None = all
         self.w_passes = w_passes
         self.fold = fold      # self-attend LayerNorms folded into the consuming GEMM
+        # rounding points carried as a 16-bit PAIR, hi + r16(x - hi), instead of one rounding: ("q", "k") models the
+        # pair-operand Q K^T of the fused cores (policy "fp16x3fq"; the dropped lo x lo term is 2^-22 relative and not
+        # modelled), ("q", "k", "v", "p") the all-pair materialised core of "fp16x3"
+        self.pair = set(pair)
 
     def r16(self, x):
         if self.dtype == "f16":
@@ -30,7 +34,10 @@ class Rounder:
     def __call__(self, x, tag):
         if self.points is not None and tag not in self.points:
             return x
-        return self.r16(x)
+        hi = self.r16(x)
+        if tag in self.pair:
+            return hi + self.r16(x - hi)
+        return hi
 
     def weight(self, w):
         if self.points is not None and "w" not in self.points:
@@ -46,9 +53,14 @@ def lin(x, p, name, rd):
 
 
 def attention(p, xq, xkv, H, rd, mask=None, qk3=False):
-    q = rd(lin(xq, p, "proj_q", rd), "q")
-    k = rd(lin(xkv, p, "proj_k", rd), "k")
-    v = rd(lin(xkv, p, "proj_v", rd), "v")
+    return lin(core(lin(xq, p, "proj_q", rd), lin(xkv, p, "proj_k", rd), lin(xkv, p, "proj_v", rd), H, rd, mask), p,
+               "final", rd)
+
+
+def core(q, k, v, H, rd, mask=None):
+    """The attention core alone, as the fused kernels see it: q [B,Tq,H*dk], k [B,Tk,H*dk], v [B,Tk,H*dv] in float64 (the
+    projections' fp32 results), mask [B,Tq,Tk] or None -> o [B,Tq,H*dv].  Rounding points q, k, v, p, o."""
+    q, k, v = rd(q, "q"), rd(k, "k"), rd(v, "v")
     B, Tq, qk = q.shape
     Tk = k.shape[1]
     dk, dv = qk // H, v.shape[2] // H
@@ -62,7 +74,7 @@ def attention(p, xq, xkv, H, rd, mask=None, qk3=False):
     o = rd((pr @ vh).transpose(0, 2, 1, 3).reshape(B, Tq, H * dv), "o")
     if mask is not None:
         o = np.where(np.all(mask == 0, axis=2, keepdims=True), 0.0, o)
-    return lin(o, p, "final", rd)
+    return o
 
 
 def mlp(p, x, rd):
@@ -155,6 +167,11 @@ if __name__ == "__main__":
     c64 = lambda d: {k: a.astype(np.float64) for k, a in d.items()}  # noqa: E731
     ref = O.encode_decode(c64(p_enc), c64(p_dec), x.astype(np.float64), qtab.astype(np.float64), **kw)
     allp = ["ln", "q", "k", "v", "p", "o", "h", "y", "w"]
+    if "--pair" in sys.argv:   # one rounding of q / k against the (hi, lo) pair of the pair-operand fused cores
+        for pair in ((), ("q", "k")):
+            y = encode_decode(p_enc, p_dec, x, qtab, Rounder("f16", None, 2, pair=pair), **kw)
+            print(f"{name} f16 w_passes=2 pair={pair}: relL2=%.2e max=%.2e" % O.rel_errors(y, ref), flush=True)
+        sys.exit(0)
     if "--fold" in sys.argv:
         for fold in (False, True):
             y = encode_decode(p_enc, p_dec, x, qtab, Rounder("f16", None, 1, fold=fold), **kw)

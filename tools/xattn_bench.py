@@ -1,4 +1,6 @@
-"""Dev tool (GPU): device time of the fused cross-attention kernel alone (profiler class 5) at the shipped shapes."""
+"""Dev tool (GPU): device time of the fused cross-attention kernel alone (profiler class 5) at the shipped shapes.
+--pair: under "fp16x3fq" (Q / K as pairs inside the core) with "fp16x3f" (its single-operand sibling) beside it;
+--batch N: that batch instead of the table's (profiles/qk_pair.json: language_enc / language_dec / language_sa at 2 and 100)."""
 import ctypes as C
 import os
 import sys
@@ -24,15 +26,23 @@ SHAPES = {  # name: heads, dk, dv, B, Tq, Tk, q_in, kv_in, broadcast q
     # it there) -- for comparison with flash_attn_kernel on the same shape ("sa_flash")
     "sa_xattn": (8, 128, 128, 32, 512, 512, 1024, 1024, False),
     "sa_flash": (8, 128, 128, 32, 512, 512, 1024, 1024, False),
+    # the language model's latent self-attend: flash_attn_kernel<32,160> under "fp16x3fq", xattn_kernel<32,160> under "fp16x3f"
+    "language_sa": (8, 32, 160, 32, 256, 256, 1280, 1280, False),
 }
 
 
 def main():
     lib = P.lib()
     dev = torch.device("cuda:0")
-    P.set_precision_policy("fp16")
-    for name in (sys.argv[1:] or SHAPES):
+    argv = [a for a in sys.argv[1:] if not a.startswith("--")]
+    pair = "--pair" in sys.argv
+    batch = int(sys.argv[sys.argv.index("--batch") + 1]) if "--batch" in sys.argv else None
+    if batch is not None:
+        argv.remove(str(batch))
+    for name, policy in [(n, p) for n in (argv or SHAPES) for p in (("fp16x3f", "fp16x3fq") if pair else ("fp16",))]:
+        P.set_precision_policy(policy)
         H, dk, dv, B, Tq, Tk, q_in, kv_in, bc = SHAPES[name]
+        B = batch or B
         m = Attention(q_in, kv_in, kv_in, num_heads=H, qk_out_channels=H * dk, v_out_channels=H * dv,
                       output_channels=q_in).to(dev).eval()
         xq = torch.randn(1 if bc else B, Tq, q_in, device=dev)
@@ -59,7 +69,7 @@ def main():
         ms = (C.c_double * 9)(); fl = (C.c_double * 9)(); by = (C.c_double * 9)(); ln = (C.c_int64 * 9)()
         lib.pio_prof_end(ms, fl, by, ln)
         us = ms[5] / n * 1e3
-        print(f"{name:16s} H={H} dk={dk} dv={dv} B={B} Tq={Tq} Tk={Tk}: fused attention {us:9.1f} us "
+        print(f"{name:16s} [{policy}] H={H} dk={dk} dv={dv} B={B} Tq={Tq} Tk={Tk}: fused attention {us:9.1f} us "
               f"({fl[5] / n / (us * 1e-6) / 1e12:7.1f} algorithmic TFLOP/s, {ln[5] // n} launches); all kernels "
               f"{sum(ms) / n * 1e3:9.1f} us", flush=True)
 
