@@ -171,32 +171,16 @@ static ScoreChunks score_chunks(int B, int H, int Tq, int Tk) {
     return c;
 }
 
-// true when attention_core will take a fused (score-free) kernel for every call that passes no full mask / bias /
-// probability output: the plans of the encoder / decoder (which never pass those) then carve no score buffers at all
-// act_split == 3 ("x3fq"): Q and K enter the fused core as (hi, lo) pairs.  Pair cores exist for the dk <= 32 fp16 heads
-// (both kernel families); every other shape -- wide single heads, xattn_tall_kernel, the K / V-folded path, bf16 -- takes
-// the MATERIALISED split-operand path, exactly what act_split == 1 runs: a pair request never silently becomes a
-// single-operand Q K^T.
-static bool pair_core_capable(const pio_attention_t &a) {
-    return flash_pair_supported(a.dtype, a.dkp, a.dvp) || xattn_pair_supported(a.dtype, a.dkp, a.dvp);
-}
-
-static bool fused_capable(const pio_attention_t &a, int Tk) {
-    const bool cross = xattn_supported(a.dkp, a.dvp) || xtall_supported(a.dkp, a.dvp, Tk);
-    if (a.act_split == 3) return pair_core_capable(a);
-    if (a.act_split == 2) return cross;  // split projections, single-sweep fused core
-    return !a.act_split && (flash_supported(a.dkp, a.dvp) || cross);
-}
-
 struct AttnScratch {
     Pair q16, k16, vt16, p16, o16;
     float *scores;
-    void *xpart;  // fp32 partials of the fused cross-attention's key splits
-    // need_scores = false: the caller guarantees a fused kernel (fused_capable and no full mask / bias / probabilities)
-    void carve(Carver &c, const pio_attention_t &a, int Bq, int B, int Tq, int Tk, bool need_scores = true) {
+    void *xpart;  // key bits / fp32 split partials of the fused cross-attention cores
+    // lean: the caller never passes a full mask / bias / probability output: no score buffers where attn_plan has a fused core
+    void carve(Carver &c, const pio_attention_t &a, int Bq, int B, int Tq, int Tk, bool lean = false) {
         const int64_t ldq = (int64_t)a.heads * a.dkp, ldo = (int64_t)a.heads * a.dvp, tkp = pad8(Tk);
         const int64_t tkv = round_up(Tk, 32);  // V^T row pitch: whole 32-key tiles, zero padded (pio_xattn.hip)
         const bool sp = a.act_split != 0;
+        const AttnRoute plan = attn_plan(a, B, Bq, Tq, Tk, lean);
         q16 = take_pair(c, (size_t)Bq * Tq * ldq, sp);
         // (the fused cross-attention kernel reads whole 32-key tiles: up to 31 rows behind key Tk - 1 of the last
         //  sample.  They only have to be readable -- their scores are masked by assignment -- and they are: vt16 and
@@ -205,18 +189,13 @@ struct AttnScratch {
         vt16 = take_pair(c, (size_t)B * ldo * tkv, sp);
         scores = nullptr;
         p16 = Pair();
-        if (need_scores) {
+        if (plan.need_scores) {
             const ScoreChunks ch = score_chunks(B, a.heads, Tq, Tk);
             scores = (float *)c.take((size_t)ch.b_chunk * a.heads * ch.q_chunk * (int64_t)Tk * 4);
             p16 = take_pair(c, (size_t)ch.b_chunk * a.heads * ch.q_chunk * tkp, sp);
         }
         o16 = take_pair(c, (size_t)B * Tq * ldo, sp);
-        size_t xb = 0;
-        if (a.act_split != 1 && !(a.act_split == 3 && !pair_core_capable(a))) {
-            if (xattn_supported(a.dkp, a.dvp)) xb = xattn_partial_bytes(a.dkp, a.dvp, B, a.heads, Tq, Tk);
-            else if (xtall_supported(a.dkp, a.dvp, Tk)) xb = xtall_scratch_bytes(B);
-        }
-        xpart = xb ? c.take(xb) : nullptr;
+        xpart = plan.xpart_bytes ? c.take(plan.xpart_bytes) : nullptr;
     }
 };
 
@@ -245,185 +224,18 @@ struct QCache {
     bool valid;   // false: compute into `pair`; true: `pair` holds the projection -- skip LayerNorm_q and proj_q
 };
 
-static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair xk, Pair xv, int B, int Tq, int Tk,
-                          const uint8_t *kv_mask, const uint8_t *q_mask, const uint8_t *full_mask,
-                          const float *attention_bias, const Residual *res, float *out, float *probs_out,
-                          AttnScratch &w, hipStream_t s, const LnFold *fold_in = nullptr,
-                          const LnFold *fold_out = nullptr, int64_t out_ld = 0, const QCache *qc = nullptr) {
-    if (!out_ld) out_ld = a.out;  // row pitch of `out` (>= a.out; an internal buffer may round it up: pitch4)
-    PIO_TRY(check_attention(a));
-    if (qc) {
-        if (!qc->pair.hi || (a.act_split && !qc->pair.lo)) return PIO_E_ARG;
-        w.q16 = qc->pair;  // (the plan's own q16 carve stays unused)
-    }
+// Materialised attention (steps 4-6) on the projected q / k (t) and w.vt16, in passes of (b_chunk samples) x (q_chunk
+// query rows) so that the score matrix held at once stays below kScoreCapBytes.  Row chunks inside a sample only happen
+// with b_chunk == 1 (mask pointers then move with the sample and the row).
+static int materialised_core(const pio_attention_t &a, const AttnOperands &t, bool q_bcast, int B, int Tq, int Tk,
+                             const uint8_t *kv_mask, const uint8_t *q_mask, const uint8_t *full_mask,
+                             const float *attention_bias, float *probs_out, AttnScratch &w, hipStream_t s) {
     const int H = a.heads;
-    const int64_t hdk = (int64_t)H * a.dkp, ldo = (int64_t)H * a.dvp, tkp = pad8(Tk), tkv = round_up(Tk, 32);
-    const int Bq = q_bcast ? 1 : B;
-
-    // 0: the fully fused self-attention form: ONE GEMM over the stacked [q | k | v] weight image, then the fused
-    //    attention kernel reading V row-major (transposed LDS reads).  Needs: same input for q, k and v, single-
-    //    sweep operands everywhere, head widths the fused kernel covers, nothing that wants the score matrix, and the
-    //    q16 | k16 | vt16 scratch regions holding one [rows, H*(2 dk + dv)] matrix.
-    {
-        const int64_t ld3 = 2 * hdk + ldo;  // one row of [q | k | v]
-        // (a q|k|v image whose V rows alone carry a lo half -- policies "x2s" / "x2w" -- is taken only inside the
-        //  LayerNorm fold, where the wide GEMM kernel, which honours pio_linear_t.lo_row0, is guaranteed)
-        const pio_linear_t &qkv_used = (fold_in && fold_in->in_part) ? *fold_in->w : a.qkv;
-        const bool qkv_lo_ok = !qkv_used.w_lo || (fold_in && fold_in->in_part && qkv_used.lo_row0 == 2 * hdk);
-        const bool fuse_qkv = !qc && a.qkv.w_hi && qkv_lo_ok && !a.act_split && !q_bcast && xq.hi == xk.hi &&
-                              xk.hi == xv.hi && Tq == Tk && flash_supported(a.dkp, a.dvp) && a.qkv.n == ld3 &&
-                              !kv_mask && !q_mask && !full_mask && !attention_bias && !probs_out &&
-                              // (q16, k16, vt16 are consecutive carves: together they hold the [rows, ld3] matrix)
-                              (char *)w.q16.hi < (char *)w.k16.hi && (char *)w.k16.hi < (char *)w.vt16.hi &&
-                              (size_t)((char *)w.vt16.hi - (char *)w.q16.hi) + (size_t)B * ldo * tkv * 2 >=
-                                  (size_t)B * Tq * ld3 * 2;
-        if (fuse_qkv) {
-            PIO_TRY(linear_fwd(a.qkv, a.dtype, xq, (int64_t)B * Tq, w.q16.hi, nullptr, false, 0, ld3, 0, nullptr, s,
-                               fold_in));
-            const char *base = (const char *)w.q16.hi;
-            PIO_TRY(flash_attention_launch(a.dtype, a.dkp, a.dvp, a.dk, base, base + hdk * 2, base + 2 * hdk * 2,
-                                           w.o16.hi, B, H, Tq, Tk, ld3, ld3, ld3, ldo, (int64_t)Tq * ld3,
-                                           (int64_t)Tk * ld3, (int64_t)Tk * ld3, (int64_t)Tq * ldo, true, s));
-            return linear_fwd(a.o, a.dtype, w.o16, (int64_t)B * Tq, out, nullptr, true, a.out, out_ld, 0, res, s,
-                              fold_out);
-        }
-        if (fold_in || fold_out) return PIO_E_SHAPE;  // the fold is wired into the fused q|k|v form only
-    }
-
-    // 0b: K / V projection fold of a single-head cross-attend over many keys (pio_attention_t.kq / vo):
-    //     scores = (Q Wk) x^T (+ a per-query constant the softmax cancels), output = (P x)(Wo Wv)^T + (Wo bv + bo).  The fused
-    //     kernel reads the LayerNorm'd input array itself as K and its transpose as V^T: the two [keys, C] x [C, C]
-    //     projection GEMMs and their 16-bit round trip are gone; what is left per call is Q' = Q Wk (query rows only),
-    //     one 16-bit transpose of the inputs and the out projection over K = C.
-    {
-        const int kvp = pad8(a.k_in);
-        const bool kv_fold = !qc && kv_fold_enabled() && a.kq.w_hi && a.vo.w_hi && H == 1 && a.k_in == a.v_in && xk.hi == xv.hi &&
-                             a.dk == a.k_in && a.dv == a.v_in && a.dkp == kvp && a.dvp == kvp && a.act_split != 1 &&
-                             a.act_split != 3 &&  // (no pair core on the folded path: materialised split-operand path)
-                             // (no mask vectors: a row without an attendable key must come out as `final.bias` alone --
-                             //  transformer_primitives.py:168-175 -- but the folded bias Wo bv + bo assumes sum(P) = 1)
-                             !kv_mask && !q_mask && !full_mask && !attention_bias && !probs_out &&
-                             (xattn_supported(kvp, kvp) || xtall_supported(kvp, kvp, Tk)) &&
-                             a.kq.k == hdk && a.kq.n == kvp && a.vo.k == kvp && (int64_t)B * Tk >= 4 * (int64_t)Bq * Tq &&
-                             !fold_in && !fold_out;
-        if (kv_fold) {
-            const bool single_core = a.act_split == 2;
-            // Q = LN_q(xq) Wq^T + bq (as always), then Q' = Q Wk into the (otherwise unused) k16 scratch
-            PIO_TRY(linear_fwd(a.q, a.dtype, xq, (int64_t)Bq * Tq, w.q16.hi, w.q16.lo, false, 0, hdk, 0, nullptr, s));
-            PIO_TRY(linear_fwd(a.kq, a.dtype, w.q16, (int64_t)Bq * Tq, w.k16.hi, w.k16.lo, false, 0, kvp, 0, nullptr, s));
-            const int64_t ldx = padc(a.k_in);      // row pitch of the LayerNorm'd inputs
-            PIO_TRY(transpose16_launch(xk.hi, ldx, B, Tk, kvp, w.vt16.hi, tkv, s));
-            if (xattn_supported(kvp, kvp))
-                PIO_TRY(xattn_launch(a.dtype, kvp, kvp, a.dk, w.k16.hi, xk.hi, w.vt16.hi, w.o16.hi,
-                                     single_core ? w.o16.lo : nullptr, B, H, Tq, Tk, kvp, ldx, tkv, kvp,
-                                     q_bcast ? 0 : (int64_t)Tq * kvp, (int64_t)Tk * ldx, (int64_t)kvp * tkv,
-                                     (int64_t)Tq * kvp, kv_mask, q_mask, w.xpart, s));
-            else  // (a head wider than the tiled kernel covers over <= 512 keys: the ImageNet decoder)
-                PIO_TRY(xtall_launch(a.dtype, kvp, kvp, a.dk, w.k16.hi, xk.hi, w.vt16.hi, w.o16.hi,
-                                     single_core ? w.o16.lo : nullptr, B, H, Tq, Tk, kvp, ldx, tkv, kvp,
-                                     q_bcast ? 0 : (int64_t)Tq * kvp, (int64_t)Tk * ldx, (int64_t)kvp * tkv,
-                                     (int64_t)Tq * kvp, kv_mask, q_mask, w.xpart, s));
-            return linear_fwd(a.vo, a.dtype, w.o16, (int64_t)B * Tq, out, nullptr, true, a.out, out_ld, 0, res, s);
-        }
-    }
-
-    // 1/2: Q and K projections (transformer_primitives.py:93-94), head-padded columns.  When both read the same
-    //      16-bit input (self-attention) they are ONE GEMM over the stacked [q rows | k rows] weight image: the
-    //      q16 / k16 scratch regions are adjacent, the fused output uses them as one [rows, 2*H*dkp] matrix.
-    const bool fuse_qk = !qc && a.qk.w_hi && !a.act_split && !q_bcast && xq.hi == xk.hi && Tq == Tk &&
-                         (char *)w.q16.hi + (size_t)B * Tq * hdk * 2 <= (char *)w.k16.hi && a.qk.n == 2 * hdk;
-    const int64_t ldq = fuse_qk ? 2 * hdk : hdk;
-    const void *k_hi = fuse_qk ? (const void *)((const char *)w.q16.hi + hdk * 2) : w.k16.hi;
-    const void *k_lo = fuse_qk ? nullptr : w.k16.lo;
-    if (fuse_qk) {
-        PIO_TRY(linear_fwd(a.qk, a.dtype, xq, (int64_t)B * Tq, w.q16.hi, nullptr, false, 0, ldq, 0, nullptr, s));
-    } else {
-        if (!(qc && qc->valid))
-            PIO_TRY(linear_fwd(a.q, a.dtype, xq, (int64_t)Bq * Tq, w.q16.hi, w.q16.lo, false, 0, ldq, 0, nullptr, s));
-        PIO_TRY(linear_fwd(a.k, a.dtype, xk, (int64_t)B * Tk, w.k16.hi, w.k16.lo, false, 0, ldq, 0, nullptr, s));
-    }
-
-    // 3: V^T[b] = Wv * X_v[b]^T + bv (transformer_primitives.py:95) produced directly in the K-contiguous layout
-    //    the P*V product wants; the weight is the A operand (batch stride 0), bias is per output ROW.
-    {
-        pio_gemm_t g = gemm_defaults(a.dtype);
-        g.A = a.v.w_hi;
-        g.A_lo = a.v.w_lo;
-        g.B = xv.hi;
-        g.B_lo = xv.lo;
-        g.C = w.vt16.hi;
-        g.C_lo = w.vt16.lo;
-        g.M = a.v.n;
-        g.N = Tk;
-        g.K = a.v.k;
-        g.lda = a.v.k;
-        g.ldb = a.v.k;
-        g.ldc = tkv;
-        g.batch = B;
-        g.sBb = (int64_t)Tk * a.v.k;
-        g.sCb = ldo * tkv;
-        g.bias = a.v.bias;
-        g.bias_mode = a.v.bias ? 2 : 0;
-        g.n_store = (int)tkv;  // columns [Tk, tkv) are written as zeros
-        PIO_TRY(gemm_nt_launch(g, s));
-    }
-    // 4-6 fused when nothing needs the score matrix (no full mask / bias / return_matrix) and the operands are
-    //      single-sweep: the self-attention kernel (pio_flash.hip) for un-masked attention with its head widths, the
-    //      cross-attention kernel (pio_xattn.hip) for key / query mask VECTORS, wide single heads, dv != dk and few
-    //      query tiles (key splits).  Otherwise the materialised path below.
-    // act_split == 2 ("x3f"): the projections around the core run with split operands, the core itself single-sweep
-    // on the hi halves of q / k / v^T through the fused cross-attention kernel, which returns its output as a pair.
-    // act_split == 3 ("x3fq"): as 2, with Q and K entering the core as the (hi, lo) pairs the projection GEMMs wrote (C_lo;
-    // a projected-query cache holds both halves too) -- the self-attention kernel for un-masked heads it covers (its pair
-    // instantiations return the output as a pair as well), the cross-attention kernel otherwise.  Without a pair core for
-    // the shape the request falls through to the materialised split-operand path below.
-    const bool pair_core = a.act_split == 3 && pair_core_capable(a);
-    const bool single_core = a.act_split == 2 || pair_core;
-    const bool score_free = (!a.act_split || single_core) && !full_mask && !attention_bias && !probs_out;
-    if (score_free && pair_core) {
-        if (!w.q16.lo || !k_lo) return PIO_E_ARG;
-        if (!kv_mask && !q_mask && flash_pair_supported(a.dtype, a.dkp, a.dvp))
-            PIO_TRY(flash_attention_launch(a.dtype, a.dkp, a.dvp, a.dk, w.q16.hi, k_hi, w.vt16.hi, w.o16.hi, B, H, Tq, Tk,
-                                           ldq, ldq, tkv, ldo, q_bcast ? 0 : (int64_t)Tq * ldq, (int64_t)Tk * ldq,
-                                           ldo * tkv, (int64_t)Tq * ldo, false, s, w.q16.lo, k_lo, w.o16.lo));
-        else
-            PIO_TRY(xattn_launch(a.dtype, a.dkp, a.dvp, a.dk, w.q16.hi, k_hi, w.vt16.hi, w.o16.hi, w.o16.lo, B, H, Tq, Tk,
-                                 ldq, ldq, tkv, ldo, q_bcast ? 0 : (int64_t)Tq * ldq, (int64_t)Tk * ldq, ldo * tkv,
-                                 (int64_t)Tq * ldo, kv_mask, q_mask, w.xpart, s, w.q16.lo, k_lo));
-        return linear_fwd(a.o, a.dtype, w.o16, (int64_t)B * Tq, out, nullptr, true, a.out, out_ld, 0, res, s);
-    }
-    if (score_free && !single_core && !kv_mask && !q_mask && flash_supported(a.dkp, a.dvp)) {
-        PIO_TRY(flash_attention_launch(a.dtype, a.dkp, a.dvp, a.dk, w.q16.hi, k_hi, w.vt16.hi, w.o16.hi, B, H, Tq,
-                                       Tk, ldq, ldq, tkv, ldo, q_bcast ? 0 : (int64_t)Tq * ldq, (int64_t)Tk * ldq,
-                                       ldo * tkv, (int64_t)Tq * ldo, false, s));
-        return linear_fwd(a.o, a.dtype, w.o16, (int64_t)B * Tq, out, nullptr, true, a.out, out_ld, 0, res, s);
-    }
-    if (score_free && xattn_supported(a.dkp, a.dvp)) {
-        PIO_TRY(xattn_launch(a.dtype, a.dkp, a.dvp, a.dk, w.q16.hi, k_hi, w.vt16.hi, w.o16.hi,
-                             single_core ? w.o16.lo : nullptr, B, H, Tq, Tk, ldq, ldq,
-                             tkv, ldo, q_bcast ? 0 : (int64_t)Tq * ldq, (int64_t)Tk * ldq, ldo * tkv, (int64_t)Tq * ldo,
-                             kv_mask, q_mask, w.xpart, s));
-        return linear_fwd(a.o, a.dtype, w.o16, (int64_t)B * Tq, out, nullptr, true, a.out, out_ld, 0, res, s);
-    }
-    if (score_free && xtall_supported(a.dkp, a.dvp, Tk)) {
-        // a head wider than the tiled kernel covers, over at most 512 keys (the ImageNet decoder: 1024 channels x 512
-        // latents): the score row of a query stays in registers, S is computed once
-        PIO_TRY(xtall_launch(a.dtype, a.dkp, a.dvp, a.dk, w.q16.hi, k_hi, w.vt16.hi, w.o16.hi,
-                             single_core ? w.o16.lo : nullptr, B, H, Tq, Tk, ldq, ldq, tkv, ldo,
-                             q_bcast ? 0 : (int64_t)Tq * ldq, (int64_t)Tk * ldq, ldo * tkv, (int64_t)Tq * ldo, kv_mask,
-                             q_mask, w.xpart, s));
-        return linear_fwd(a.o, a.dtype, w.o16, (int64_t)B * Tq, out, nullptr, true, a.out, out_ld, 0, res, s);
-    }
-    if (!w.scores) return PIO_E_WORKSPACE;  // (the plan promised a fused kernel)
-    // Materialised path, in passes of (b_chunk samples) x (q_chunk query rows) so that the score matrix held at once
-    // stays below kScoreCapBytes.  Row chunks inside a sample only happen with b_chunk == 1 (mask pointers then move
-    // with the sample and the row).
+    const int64_t ldq = t.ldq, ldo = (int64_t)H * a.dvp, tkp = pad8(Tk), tkv = round_up(Tk, 32);
     const ScoreChunks ch = score_chunks(B, H, Tq, Tk);
-    if ((full_mask || attention_bias || probs_out) && (ch.b_chunk != B || ch.q_chunk != Tq)) {
-        // full masks / biases / probability outputs are [B,H,Tq,Tk]-sized themselves: callers that pass them have
-        // the memory; run them in one pass per sample
-        if (ch.q_chunk != Tq) return PIO_E_WORKSPACE;
-    }
+    // full masks / biases / probability outputs are [B,H,Tq,Tk]-sized themselves: callers that pass them have the memory;
+    // they run in one pass per sample
+    if ((full_mask || attention_bias || probs_out) && ch.q_chunk != Tq) return PIO_E_WORKSPACE;
     for (int b0 = 0; b0 < B; b0 += ch.b_chunk) {
         const int nb = b0 + ch.b_chunk <= B ? ch.b_chunk : B - b0;
         for (int r0 = 0; r0 < Tq; r0 += ch.q_chunk) {
@@ -433,10 +245,10 @@ static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair 
             // 4: S[b,h] = Q[b,h] K[b,h]^T (transformer_primitives.py:138), fp32 scores
             {
                 pio_gemm_t g = gemm_defaults(a.dtype);
-                g.A = (const char *)w.q16.hi + qoff * 2;
-                g.A_lo = w.q16.lo ? (const char *)w.q16.lo + qoff * 2 : nullptr;
-                g.B = (const char *)k_hi + koff * 2;
-                g.B_lo = k_lo ? (const char *)k_lo + koff * 2 : nullptr;
+                g.A = (const char *)t.Q + qoff * 2;
+                g.A_lo = t.Q_lo ? (const char *)t.Q_lo + qoff * 2 : nullptr;
+                g.B = (const char *)t.K + koff * 2;
+                g.B_lo = t.K_lo ? (const char *)t.K_lo + koff * 2 : nullptr;
                 g.C = w.scores;
                 g.M = nr;
                 g.N = Tk;
@@ -446,9 +258,9 @@ static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair 
                 g.ldc = Tk;
                 g.batch = nb * H;
                 g.nh = H;
-                g.sAb = q_bcast ? 0 : (int64_t)Tq * ldq;
+                g.sAb = t.sQb;
                 g.sAh = a.dkp;
-                g.sBb = (int64_t)Tk * ldq;
+                g.sBb = t.sKb;
                 g.sBh = a.dkp;
                 g.sCb = (int64_t)H * nr * Tk;
                 g.sCh = (int64_t)nr * Tk;
@@ -495,8 +307,121 @@ static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair 
             }
         }
     }
-    // 7: final projection (+ residual) (transformer_primitives.py:110; SelfAttention :290, CrossAttention :396-399)
-    return linear_fwd(a.o, a.dtype, w.o16, (int64_t)B * Tq, out, nullptr, true, a.out, out_ld, 0, res, s);
+    return PIO_OK;
+}
+
+// One route (attn_route, pio_attn_route.h), then: the projections it names, one core launch, the out projection.
+static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair xk, Pair xv, int B, int Tq, int Tk,
+                          const uint8_t *kv_mask, const uint8_t *q_mask, const uint8_t *full_mask,
+                          const float *attention_bias, const Residual *res, float *out, float *probs_out,
+                          AttnScratch &w, hipStream_t s, const LnFold *fold_in = nullptr,
+                          const LnFold *fold_out = nullptr, int64_t out_ld = 0, const QCache *qc = nullptr) {
+    if (!out_ld) out_ld = a.out;  // row pitch of `out` (>= a.out; an internal buffer may round it up: pitch4)
+    PIO_TRY(check_attention(a));
+    if (qc) {
+        if (!qc->pair.hi || (a.act_split && !qc->pair.lo)) return PIO_E_ARG;
+        w.q16 = qc->pair;  // (the plan's own q16 carve stays unused)
+    }
+    const int H = a.heads;
+    const int64_t hdk = (int64_t)H * a.dkp, ldo = (int64_t)H * a.dvp, ld3 = 2 * hdk + ldo, tkv = round_up(Tk, 32);
+    const int Bq = q_bcast ? 1 : B;
+    AttnCall call = {};
+    call.B = B; call.Bq = Bq; call.Tq = Tq; call.Tk = Tk; call.q_bcast = q_bcast; call.same_qk = xq.hi == xk.hi;
+    call.same_kv = xk.hi == xv.hi; call.kv_fold_on = kv_fold_enabled();
+    call.kv_mask = kv_mask; call.q_mask = q_mask; call.full_mask = full_mask; call.bias = attention_bias;
+    call.probs = probs_out; call.qcache = qc; call.fold_in = fold_in; call.fold_out = fold_out;
+    call.fold_qkv = (fold_in && fold_in->in_part) ? fold_in->w : nullptr;
+    // (q16, k16, vt16 are consecutive carves: together they hold the [rows, ld3] matrix of the q|k|v form, q16 | k16 the
+    //  [rows, 2 hdk] one of the q|k form)
+    call.qkv_adjacent = (char *)w.q16.hi < (char *)w.k16.hi && (char *)w.k16.hi < (char *)w.vt16.hi &&
+                        (size_t)((char *)w.vt16.hi - (char *)w.q16.hi) + (size_t)B * ldo * tkv * 2 >= (size_t)B * Tq * ld3 * 2;
+    call.qk_adjacent = (char *)w.q16.hi + (size_t)B * Tq * hdk * 2 <= (char *)w.k16.hi;
+    const AttnRoute r = attn_route(a, call);
+    if (r.err != PIO_OK) return r.err;
+    if (r.qk_pair && (!w.q16.lo || !w.k16.lo)) return PIO_E_ARG;
+    if (r.need_scores && !w.scores) return PIO_E_WORKSPACE;  // (the plan promised a fused kernel)
+    const bool kv_fold = r.core == AttnCore::KVFOLD_XATTN || r.core == AttnCore::KVFOLD_XTALL;
+    const int64_t sQ = q_bcast ? 0 : 1;  // batch-invariant queries: batch stride 0
+
+    // Projections (transformer_primitives.py:93-95), head-padded columns; t: the operands they leave for the core
+    AttnOperands t = {};
+    t.O = w.o16.hi;
+    t.O_lo = r.out_pair ? w.o16.lo : nullptr;
+    if (r.core == AttnCore::QKV_FLASH) {
+        // ONE GEMM over the stacked [q | k | v] weight image; the core reads V row-major (transposed LDS reads)
+        PIO_TRY(linear_fwd(a.qkv, a.dtype, xq, (int64_t)B * Tq, w.q16.hi, nullptr, false, 0, ld3, 0, nullptr, s, fold_in));
+        const char *base = (const char *)w.q16.hi;
+        t.Q = base; t.K = base + hdk * 2; t.VT = base + 2 * hdk * 2;
+        t.ldq = t.ldk = t.ldvt = ld3; t.ldo = ldo;
+        t.sQb = t.sKb = t.sVb = (int64_t)Tq * ld3; t.sOb = (int64_t)Tq * ldo;
+    } else if (kv_fold) {
+        // K / V projection fold (pio_attention_t.kq / vo): the fused kernel reads the LayerNorm'd input
+        // array itself as K and its transpose as V^T.  Per call: Q = LN_q(xq) Wq^T + bq (as always), Q' = Q Wk into the
+        // (otherwise unused) k16 scratch, one 16-bit transpose of the inputs and the out projection (Wo Wv) over K = C.
+        const int64_t kvp = a.dkp, ldx = padc(a.k_in);  // ldx: row pitch of the LayerNorm'd inputs
+        PIO_TRY(linear_fwd(a.q, a.dtype, xq, (int64_t)Bq * Tq, w.q16.hi, w.q16.lo, false, 0, hdk, 0, nullptr, s));
+        PIO_TRY(linear_fwd(a.kq, a.dtype, w.q16, (int64_t)Bq * Tq, w.k16.hi, w.k16.lo, false, 0, kvp, 0, nullptr, s));
+        PIO_TRY(transpose16_launch(xk.hi, ldx, B, Tk, (int)kvp, w.vt16.hi, tkv, s));
+        t.Q = w.k16.hi; t.K = xk.hi; t.VT = w.vt16.hi;
+        t.ldq = kvp; t.ldk = ldx; t.ldvt = tkv; t.ldo = kvp;
+        t.sQb = sQ * Tq * kvp; t.sKb = (int64_t)Tk * ldx; t.sVb = kvp * tkv; t.sOb = (int64_t)Tq * kvp;
+    } else {
+        // Q and K: one GEMM over the stacked [q rows | k rows] image (the adjacent q16 / k16 regions as one
+        // [rows, 2*H*dkp] matrix) when the route says so, else one each (a valid query cache holds Q already)
+        const int64_t ldq = r.fuse_qk ? 2 * hdk : hdk;
+        if (r.fuse_qk) {
+            PIO_TRY(linear_fwd(a.qk, a.dtype, xq, (int64_t)B * Tq, w.q16.hi, nullptr, false, 0, ldq, 0, nullptr, s));
+        } else {
+            if (!(qc && qc->valid))
+                PIO_TRY(linear_fwd(a.q, a.dtype, xq, (int64_t)Bq * Tq, w.q16.hi, w.q16.lo, false, 0, ldq, 0, nullptr, s));
+            PIO_TRY(linear_fwd(a.k, a.dtype, xk, (int64_t)B * Tk, w.k16.hi, w.k16.lo, false, 0, ldq, 0, nullptr, s));
+        }
+        // V^T[b] = Wv * X_v[b]^T + bv produced directly in the K-contiguous layout the P*V product wants; the weight is
+        // the A operand (batch stride 0), bias is per output ROW.
+        pio_gemm_t g = gemm_defaults(a.dtype);
+        g.A = a.v.w_hi;
+        g.A_lo = a.v.w_lo;
+        g.B = xv.hi;
+        g.B_lo = xv.lo;
+        g.C = w.vt16.hi;
+        g.C_lo = w.vt16.lo;
+        g.M = a.v.n;
+        g.N = Tk;
+        g.K = a.v.k;
+        g.lda = a.v.k;
+        g.ldb = a.v.k;
+        g.ldc = tkv;
+        g.batch = B;
+        g.sBb = (int64_t)Tk * a.v.k;
+        g.sCb = ldo * tkv;
+        g.bias = a.v.bias;
+        g.bias_mode = a.v.bias ? 2 : 0;
+        g.n_store = (int)tkv;  // columns [Tk, tkv) are written as zeros
+        PIO_TRY(gemm_nt_launch(g, s));
+        t.Q = w.q16.hi; t.K = r.fuse_qk ? (const char *)w.q16.hi + hdk * 2 : w.k16.hi; t.VT = w.vt16.hi;
+        if (r.qk_pair) { t.Q_lo = w.q16.lo; t.K_lo = w.k16.lo; }
+        t.ldq = t.ldk = ldq; t.ldvt = tkv; t.ldo = ldo;
+        t.sQb = sQ * Tq * ldq; t.sKb = (int64_t)Tk * ldq; t.sVb = ldo * tkv; t.sOb = (int64_t)Tq * ldo;
+    }
+
+    switch (r.core) {
+    case AttnCore::QKV_FLASH: case AttnCore::PAIR_FLASH: case AttnCore::FLASH:
+        PIO_TRY(flash_attention_launch(a.dtype, a.dkp, a.dvp, a.dk, t, B, H, Tq, Tk, r.core == AttnCore::QKV_FLASH, s));
+        break;
+    case AttnCore::KVFOLD_XATTN: case AttnCore::PAIR_XATTN: case AttnCore::XATTN:
+        PIO_TRY(xattn_launch(a.dtype, a.dkp, a.dvp, a.dk, t, B, H, Tq, Tk, kv_mask, q_mask, w.xpart, s));
+        break;
+    case AttnCore::KVFOLD_XTALL: case AttnCore::XTALL:
+        PIO_TRY(xtall_launch(a.dtype, a.dkp, a.dvp, a.dk, t, B, H, Tq, Tk, kv_mask, q_mask, w.xpart, s));
+        break;
+    case AttnCore::MATERIALISED:
+        PIO_TRY(materialised_core(a, t, q_bcast, B, Tq, Tk, kv_mask, q_mask, full_mask, attention_bias, probs_out, w, s));
+        break;
+    }
+    // final projection (+ residual) (transformer_primitives.py:110; SelfAttention :290, CrossAttention :396-399); behind
+    // the K / V fold it is Wo Wv
+    return linear_fwd(kv_fold ? a.vo : a.o, a.dtype, w.o16, (int64_t)B * Tq, out, nullptr, true, a.out, out_ld, 0, res, s,
+                      fold_out);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -575,7 +500,7 @@ struct SelfPlan {
         x16 = take_pair(c, (size_t)rows * cmax, sa.attn.act_split || sa.mlp.act_split);
         h16 = take_pair(c, (size_t)rows * padc(sa.mlp.hidden), sa.mlp.act_split != 0);
         x1 = (float *)c.take((size_t)rows * sa.attn.out * 4);
-        core.carve(c, sa.attn, B, B, N, N, !(lean && fused_capable(sa.attn, N)));
+        core.carve(c, sa.attn, B, B, N, N, lean);
         if (sa.fold.qkv.w_hi && sa.fold.fc1.w_hi) {
             // The residual GEMMs (out, fc2) read the residual pair and write the result pair element for element from
             // the same lane (load, add, store), and their A operand is another array (attention output / hidden
@@ -771,7 +696,7 @@ struct CrossPlan {
         kv16 = take_pair(c, (size_t)B * Tk * padc(ca.attn.k_in), ca.attn.act_split != 0);
         h16 = take_pair(c, (size_t)rows * padc(ca.mlp.hidden), ca.mlp.act_split != 0);
         x1 = (float *)c.take((size_t)rows * pitch4(ca.attn.out) * 4);
-        core.carve(c, ca.attn, Bq, B, Tq, Tk, !(lean && fused_capable(ca.attn, Tk)));
+        core.carve(c, ca.attn, Bq, B, Tq, Tk, lean);
         return c.off;
     }
 };

@@ -186,8 +186,8 @@ int pio_flash_attention(int32_t dtype, int32_t dkp, int32_t dvp, int32_t dk, con
                         void *O, int32_t B, int32_t H, int32_t Tq, int32_t Tk, int64_t ldq, int64_t ldk, int64_t ldv,
                         int64_t ldo, int64_t sQb, int64_t sKb, int64_t sVb, int64_t sOb, int32_t v_rowmajor, void *stream) {
     if (dtype != PIO_DT_F16 && dtype != PIO_DT_BF16) return PIO_E_ARG;
-    return flash_attention_launch(dtype, dkp, dvp, dk, Q, K, V, O, B, H, Tq, Tk, ldq, ldk, ldv, ldo, sQb, sKb, sVb, sOb,
-                                  v_rowmajor != 0, (hipStream_t)stream);
+    const AttnOperands t = {Q, nullptr, K, nullptr, V, O, nullptr, ldq, ldk, ldv, ldo, sQb, sKb, sVb, sOb};
+    return flash_attention_launch(dtype, dkp, dvp, dk, t, B, H, Tq, Tk, v_rowmajor != 0, (hipStream_t)stream);
 }
 
 size_t pio_flash_attention_pair_workspace_bytes(int32_t dkp, int32_t dvp, int32_t B, int32_t H, int32_t Tq, int32_t Tk) {
@@ -201,19 +201,18 @@ int pio_flash_attention_pair(int32_t dtype, int32_t dkp, int32_t dvp, int32_t dk
                              const uint8_t *q_mask, int32_t core, void *workspace, size_t workspace_bytes, void *stream) {
     if (dtype != PIO_DT_F16 && dtype != PIO_DT_BF16) return PIO_E_ARG;
     if (core < 0 || core > 2 || (!Q_lo) != (!K_lo)) return PIO_E_ARG;
+    const AttnOperands t = {Q, Q_lo, K, K_lo, V, O, O_lo, ldq, ldk, ldv, ldo, sQb, sKb, sVb, sOb};
     const bool masked = kv_mask || q_mask;
-    const bool flash = core == 1 || (core == 0 && !masked && flash_supported(dkp, dvp));
-    if (flash) {
+    // core 0: what attention_core's route takes for the shape (fused_core, pio_attn_route.h), short of the tall-head kernel
+    if (core == 1 || (core == 0 && fused_core(dkp, dvp, Tk, masked, true) == AttnCore::FLASH)) {
         if (masked) return PIO_E_ARG;  // (the self-attention kernel takes no mask)
         if (O_lo && !Q_lo) return PIO_E_ARG;  // (its single-operand instantiations write one half)
-        return flash_attention_launch(dtype, dkp, dvp, dk, Q, K, V, O, B, H, Tq, Tk, ldq, ldk, ldv, ldo, sQb, sKb, sVb, sOb,
-                                      v_rowmajor != 0, (hipStream_t)stream, Q_lo, K_lo, O_lo);
+        return flash_attention_launch(dtype, dkp, dvp, dk, t, B, H, Tq, Tk, v_rowmajor != 0, (hipStream_t)stream);
     }
     if (v_rowmajor) return PIO_E_ARG;  // (the cross-attention kernel reads V^T)
     if (!xattn_supported(dkp, dvp)) return PIO_E_SHAPE;
     if (xattn_partial_bytes(dkp, dvp, B, H, Tq, Tk) > workspace_bytes) return PIO_E_WORKSPACE;
-    return xattn_launch(dtype, dkp, dvp, dk, Q, K, V, O, O_lo, B, H, Tq, Tk, ldq, ldk, ldv, ldo, sQb, sKb, sVb, sOb, kv_mask,
-                        q_mask, workspace, (hipStream_t)stream, Q_lo, K_lo);
+    return xattn_launch(dtype, dkp, dvp, dk, t, B, H, Tq, Tk, kv_mask, q_mask, workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -418,15 +418,6 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void flash_attn_kernel(co
 #include "../../tools/experiments/pio_flash_variants.inc"
 #endif
 
-bool flash_supported(int dkp, int dvp) {
-    return (dkp == 128 && dvp == 128) || (dkp == 64 && dvp == 64) || (dkp == 32 && dvp == 32) ||
-           (dkp == 32 && dvp == 160);
-}
-// pair-operand Q K^T: the DK = 32 instantiations, fp16
-bool flash_pair_supported(int dtype, int dkp, int dvp) {
-    return dtype == PIO_DT_F16 && dkp == 32 && (dvp == 32 || dvp == 160);
-}
-
 #ifdef PIO_EXPERIMENTS
 // (experiments build only) variant of the row-major-V kernel: 0 = lock-step waves (flash_attn_kernel, the shipped one),
 // 1 = one wave per SIMD with the softmax in the MFMAs' shadow (flash_attn_pipe_kernel), 2 = two staggered wave groups
@@ -444,142 +435,77 @@ int flash_variant_override(int which) {
 extern "C" int pio_debug_flash_variant(int which) { return flash_variant_override(which); }
 #endif
 
-// v_rowmajor: VT points at V [B][Tk][.. h*dvp ..] (row stride ldvt) instead of V^T [B][H*dvp][Tk].
-int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const void *Q, const void *K, const void *VT,
-                           void *O, int B, int H, int Tq, int Tk, int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo,
-                           int64_t sQb, int64_t sKb, int64_t sVb, int64_t sOb, bool v_rowmajor, hipStream_t s,
-                           const void *Q_lo, const void *K_lo, void *O_lo) {
+// The instantiation flash_route names: (V^T, 4, 1), (row, 4, 1), (row, 8, 1), (row, 8, 2) for every head shape, and
+// (row, 16, 4) for the narrow heads.
+template <int DT, int DK, int DV, bool PAIR>
+static void flash_launch(const FlashRoute &r, dim3 grid, hipStream_t s, const FlashParams &p) {
+    void (*k)(FlashParams) = flash_attn_kernel<DT, DK, DV, false, 4, 1, PAIR>;
+    if (r.v_rowmajor) k = flash_attn_kernel<DT, DK, DV, true, 4, 1, PAIR>;
+    if (r.NW == 8) k = r.KS == 2 ? flash_attn_kernel<DT, DK, DV, true, 8, 2, PAIR> : flash_attn_kernel<DT, DK, DV, true, 8, 1, PAIR>;
+    if constexpr (DK <= 64 && DV <= 64)
+        if (r.NW == 16) k = flash_attn_kernel<DT, DK, DV, true, 16, 4, PAIR>;
+    hipLaunchKernelGGL(k, grid, dim3(r.threads), 0, s, p);
+}
+// ... over the operand dtype and, on the DK = 32 fp16 heads, the pair-operand (QK_PAIR) instantiations
+template <int DK, int DV>
+static void flash_launch_dt(int dtype, bool pair, const FlashRoute &r, dim3 grid, hipStream_t s, const FlashParams &p) {
+    if constexpr (DK == 32)
+        if (pair) return flash_launch<PIO_DT_F16, DK, DV, true>(r, grid, s, p);
+    if (dtype == PIO_DT_F16) flash_launch<PIO_DT_F16, DK, DV, false>(r, grid, s, p);
+    else flash_launch<PIO_DT_BF16, DK, DV, false>(r, grid, s, p);
+}
+
+int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const AttnOperands &t, int B, int H, int Tq, int Tk,
+                           bool v_rowmajor, hipStream_t s) {
     if (!flash_supported(dkp, dvp)) return PIO_E_SHAPE;
-    if (!Q || !K || !VT || !O) return PIO_E_ARG;
-    const bool pair = Q_lo || K_lo;  // Q and K as (hi, lo) pairs: both halves or neither; O_lo only with them
-    if ((pair && !(Q_lo && K_lo)) || (O_lo && !pair)) return PIO_E_ARG;
+    if (attn_operands_present(t) != PIO_OK) return PIO_E_ARG;
+    const bool pair = t.Q_lo != nullptr;  // Q and K as (hi, lo) pairs; O_lo only with them
+    if (t.O_lo && !pair) return PIO_E_ARG;
     if (pair && !flash_pair_supported(dtype, dkp, dvp)) return PIO_E_SHAPE;  // (never a silent single-operand run)
-    if (((uintptr_t)Q_lo & 15) || ((uintptr_t)K_lo & 15) || ((uintptr_t)O_lo & 7)) return PIO_E_ALIGN;
     if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || (int64_t)B * H * ((Tq + 127) / 128) > 0x7fffffffLL) return PIO_E_SHAPE;
-    if ((ldq % 8) || (ldk % 8) || (ldvt % 8) || (ldo % 4) || (sQb % 8) || (sKb % 8) || (sVb % 8) || (sOb % 4))
-        return PIO_E_ALIGN;
-    if (((uintptr_t)Q & 15) || ((uintptr_t)K & 15) || ((uintptr_t)VT & 15) || ((uintptr_t)O & 7)) return PIO_E_ALIGN;
-    // 256-row workgroups when that still gives every CU a workgroup (row-major-V flagship path only)
-    const bool wide = v_rowmajor && Tq >= 256 && (int64_t)B * H * ((Tq + 255) / 256) >= 256;
-    // (64-row workgroups for small batches -- B = 1: 64 workgroups instead of 32 -- were measured in round 3: 4.00 ms
-    //  against 3.82 ms per B = 1 forward; two waves issuing a whole tile's DMA cost more than the idle CUs: not kept)
-    const int nqt = wide ? (Tq + 255) / 256 : (Tq + 127) / 128;
+    if (attn_operands_aligned(t) != PIO_OK) return PIO_E_ALIGN;
+    static const bool ksplit_on = [] {
+        const char *e = getenv("PIO_FLASH_KSPLIT");
+        return !e || atoi(e) != 0;
+    }();
+    const FlashRoute r = flash_route(dkp, dvp, B, H, Tq, Tk, v_rowmajor, ksplit_on, cu_budget());
     // (an output PAIR leaves through the per-lane 8-byte stores: the staged whole-row epilogue carries one half only)
-    const int o_rows16 = (!O_lo && ldo % 8 == 0 && sOb % 8 == 0 && ((uintptr_t)O & 15) == 0) ? 1 : 0;
-    FlashParams p{Q, K, VT, O, Tq, Tk, H, nqt, ldq, ldk, ldvt, ldo, sQb, sKb, sVb, sOb,
-                  1.4426950408889634f / sqrtf((float)dk_logical), o_rows16, Q_lo, K_lo, O_lo};
-    dim3 grid((unsigned)(nqt * B * H), 1, 1);
-    dim3 block(wide ? 512 : 256, 1, 1);
+    const int o_rows16 = (!t.O_lo && t.ldo % 8 == 0 && t.sOb % 8 == 0 && ((uintptr_t)t.O & 15) == 0) ? 1 : 0;
+    FlashParams p{t.Q, t.K, t.VT, t.O, Tq, Tk, H, r.nqt, t.ldq, t.ldk, t.ldvt, t.ldo, t.sQb, t.sKb, t.sVb, t.sOb,
+                  1.4426950408889634f / sqrtf((float)dk_logical), o_rows16, t.Q_lo, t.K_lo, t.O_lo};
+    dim3 grid((unsigned)(r.nqt * B * H), 1, 1);
     ProfScope prof(PROF_FLASH, 2.0 * B * H * (double)Tq * Tk * (dkp + dvp),
                    2.0 * B * H * ((double)Tq * (dkp + dvp) + (double)Tk * (dkp + dvp)), s);
-#define PIO_FLASH(DTV, DKV, DVV) hipLaunchKernelGGL((flash_attn_kernel<DTV, DKV, DVV, false, 4>), grid, block, 0, s, p)
-#define PIO_FLASH_DT(DKV, DVV)                                         \
-    do {                                                               \
-        if (dtype == PIO_DT_F16) PIO_FLASH(PIO_DT_F16, DKV, DVV);      \
-        else PIO_FLASH(PIO_DT_BF16, DKV, DVV);                         \
-    } while (0)
+    int variant = 0;
 #ifdef PIO_EXPERIMENTS
-    const int variant = flash_variant_override(-2);   // (experiments build: pio_debug_flash_variant / env PIO_FLASH_VARIANT)
-#else
-    const int variant = 0;
+    variant = flash_variant_override(-2);   // (experiments build: pio_debug_flash_variant / env PIO_FLASH_VARIANT)
 #endif
     static const bool debug = [] {
         const char *e = getenv("PIO_FLASH_DEBUG");
         return e && atoi(e) != 0;
     }();
     if (debug)
-        fprintf(stderr, "[pio] fused attention B=%d H=%d Tq=%d Tk=%d dkp=%d dvp=%d v_rowmajor=%d wide=%d variant=%d\n", B, H,
-                Tq, Tk, dkp, dvp, (int)v_rowmajor, (int)wide, variant);
-    // key split over two wave groups (KS = 2): when the launch offers at most one 128-row workgroup per CU
-    static const bool ksplit_on = [] {
-        const char *e = getenv("PIO_FLASH_KSPLIT");
-        return !e || atoi(e) != 0;
-    }();
-    const bool ksplit = ksplit_on && v_rowmajor && !wide && Tk >= 256 && (Tk % 128) == 0 &&
-                        (int64_t)B * H * nqt <= cu_budget();
-    // (four key parts = 16 waves per workgroup, four per SIMD: the narrow heads, whose waves need < 128 registers)
-    const bool ksplit4 = ksplit && dkp <= 64 && dvp <= 64 && Tk >= 1024 && (Tk % 256) == 0;
-    if (pair) {
-        // the same kernel choice as below, on the QK_PAIR instantiation of each variant
-#define PIO_FLASH_PAIR(DVV, VROWV, NWV, KSV) \
-    hipLaunchKernelGGL((flash_attn_kernel<PIO_DT_F16, 32, DVV, VROWV, NWV, KSV, true>), grid, block, 0, s, p)
-#define PIO_FLASH_PAIR_DV(VROWV, NWV, KSV)                \
-    do {                                                  \
-        if (dvp == 32) PIO_FLASH_PAIR(32, VROWV, NWV, KSV); \
-        else PIO_FLASH_PAIR(160, VROWV, NWV, KSV);        \
-    } while (0)
-        if (ksplit4) {  // (dvp <= 64: the (32, 32) heads)
-            block = dim3(1024, 1, 1);
-            PIO_FLASH_PAIR(32, true, 16, 4);
-        } else if (ksplit) {
-            block = dim3(512, 1, 1);
-            PIO_FLASH_PAIR_DV(true, 8, 2);
-        } else if (v_rowmajor && wide) PIO_FLASH_PAIR_DV(true, 8, 1);
-        else if (v_rowmajor) PIO_FLASH_PAIR_DV(true, 4, 1);
-        else PIO_FLASH_PAIR_DV(false, 4, 1);
-#undef PIO_FLASH_PAIR_DV
-#undef PIO_FLASH_PAIR
-        return launch_status();
-    }
+        fprintf(stderr, "[pio] fused attention B=%d H=%d Tq=%d Tk=%d dkp=%d dvp=%d v_rowmajor=%d NW=%d KS=%d variant=%d\n", B,
+                H, Tq, Tk, dkp, dvp, (int)v_rowmajor, r.NW, r.KS, variant);
 #ifdef PIO_EXPERIMENTS
-    const bool pipe = variant == 1, stagger = variant == 2;
-    if (v_rowmajor && Tq >= 256 && Tk % 128 == 0 && pipe && o_rows16) {
+    if (!pair && v_rowmajor && Tq >= 256 && Tk % 128 == 0 && variant == 1 && o_rows16) {
         FlashParams pp = p;
         pp.nqt = (Tq + 255) / 256;
         dim3 pgrid((unsigned)(pp.nqt * B * H), 1, 1);
         if (dtype == PIO_DT_F16) hipLaunchKernelGGL((flash_attn_pipe_kernel<PIO_DT_F16>), pgrid, dim3(256), 0, s, pp);
         else hipLaunchKernelGGL((flash_attn_pipe_kernel<PIO_DT_BF16>), pgrid, dim3(256), 0, s, pp);
-    } else if (v_rowmajor && wide && stagger) {
-        if (dtype == PIO_DT_F16) hipLaunchKernelGGL((flash_attn_stag_kernel<PIO_DT_F16>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((flash_attn_stag_kernel<PIO_DT_BF16>), grid, block, 0, s, p);
-    } else
+        return launch_status();
+    }
+    if (!pair && r.NW == 8 && r.KS == 1 && variant == 2) {
+        if (dtype == PIO_DT_F16) hipLaunchKernelGGL((flash_attn_stag_kernel<PIO_DT_F16>), grid, dim3(512), 0, s, p);
+        else hipLaunchKernelGGL((flash_attn_stag_kernel<PIO_DT_BF16>), grid, dim3(512), 0, s, p);
+        return launch_status();
+    }
 #endif
-    if (ksplit4) {
-        block = dim3(1024, 1, 1);
-        if (dkp == 64) {
-            if (dtype == PIO_DT_F16) hipLaunchKernelGGL((flash_attn_kernel<PIO_DT_F16, 64, 64, true, 16, 4>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((flash_attn_kernel<PIO_DT_BF16, 64, 64, true, 16, 4>), grid, block, 0, s, p);
-        } else {
-            if (dtype == PIO_DT_F16) hipLaunchKernelGGL((flash_attn_kernel<PIO_DT_F16, 32, 32, true, 16, 4>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((flash_attn_kernel<PIO_DT_BF16, 32, 32, true, 16, 4>), grid, block, 0, s, p);
-        }
-    } else if (ksplit) {
-        block = dim3(512, 1, 1);
-#define PIO_FLASH_KS(DKV, DVV)                                                                                        \
-    do {                                                                                                              \
-        if (dtype == PIO_DT_F16)                                                                                      \
-            hipLaunchKernelGGL((flash_attn_kernel<PIO_DT_F16, DKV, DVV, true, 8, 2>), grid, block, 0, s, p);          \
-        else hipLaunchKernelGGL((flash_attn_kernel<PIO_DT_BF16, DKV, DVV, true, 8, 2>), grid, block, 0, s, p);        \
-    } while (0)
-        if (dkp == 128 && dvp == 128) PIO_FLASH_KS(128, 128);
-        else if (dkp == 64 && dvp == 64) PIO_FLASH_KS(64, 64);
-        else if (dkp == 32 && dvp == 32) PIO_FLASH_KS(32, 32);
-        else PIO_FLASH_KS(32, 160);
-#undef PIO_FLASH_KS
-    } else if (v_rowmajor) {
-#define PIO_FLASH_ROW(DKV, DVV)                                                                                        \
-    do {                                                                                                               \
-        if (wide) {                                                                                                    \
-            if (dtype == PIO_DT_F16)                                                                                   \
-                hipLaunchKernelGGL((flash_attn_kernel<PIO_DT_F16, DKV, DVV, true, 8>), grid, block, 0, s, p);          \
-            else hipLaunchKernelGGL((flash_attn_kernel<PIO_DT_BF16, DKV, DVV, true, 8>), grid, block, 0, s, p);        \
-        } else {                                                                                                       \
-            if (dtype == PIO_DT_F16)                                                                                   \
-                hipLaunchKernelGGL((flash_attn_kernel<PIO_DT_F16, DKV, DVV, true, 4>), grid, block, 0, s, p);          \
-            else hipLaunchKernelGGL((flash_attn_kernel<PIO_DT_BF16, DKV, DVV, true, 4>), grid, block, 0, s, p);        \
-        }                                                                                                              \
-    } while (0)
-        if (dkp == 128 && dvp == 128) PIO_FLASH_ROW(128, 128);
-        else if (dkp == 64 && dvp == 64) PIO_FLASH_ROW(64, 64);
-        else if (dkp == 32 && dvp == 32) PIO_FLASH_ROW(32, 32);
-        else PIO_FLASH_ROW(32, 160);
-#undef PIO_FLASH_ROW
-    } else if (dkp == 128 && dvp == 128) PIO_FLASH_DT(128, 128);
-    else if (dkp == 64 && dvp == 64) PIO_FLASH_DT(64, 64);
-    else if (dkp == 32 && dvp == 32) PIO_FLASH_DT(32, 32);
-    else PIO_FLASH_DT(32, 160);
-#undef PIO_FLASH_DT
-#undef PIO_FLASH
+    if (dkp == 128) flash_launch_dt<128, 128>(dtype, pair, r, grid, s, p);
+    else if (dkp == 64) flash_launch_dt<64, 64>(dtype, pair, r, grid, s, p);
+    else if (dvp == 32) flash_launch_dt<32, 32>(dtype, pair, r, grid, s, p);
+    else flash_launch_dt<32, 160>(dtype, pair, r, grid, s, p);
     return launch_status();
 }
 

@@ -6,6 +6,7 @@
 #include <stddef.h>
 
 #include "../../include/pio_hip.h"
+#include "pio_attn_route.h"
 
 namespace pio {
 
@@ -116,30 +117,15 @@ bool ln_fold_enabled();
 int softmax_rows_launch(const float *S, int64_t lds, void *P, void *P_lo, int64_t ldp, int B, int H, int Tq, int Tk,
                         float scale, const uint8_t *kv_mask, const uint8_t *q_mask, const uint8_t *full_mask,
                         const float *bias, int dtype, float *probs_out, hipStream_t s);
-bool flash_supported(int dkp, int dvp);
-// Q / K as (hi, lo) pairs inside the fused cores' Q K^T (S = Q_hi K_hi + Q_lo K_hi + Q_hi K_lo): the dk <= 32 fp16
-// instantiations of both kernel families.  A launch with Q_lo / K_lo on any other shape or dtype is PIO_E_SHAPE.
-bool flash_pair_supported(int dtype, int dkp, int dvp);
-bool xattn_pair_supported(int dtype, int dkp, int dvp);
-int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const void *Q, const void *K, const void *VT,
-                           void *O, int B, int H, int Tq, int Tk, int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo,
-                           int64_t sQb, int64_t sKb, int64_t sVb, int64_t sOb, bool v_rowmajor, hipStream_t s,
-                           const void *Q_lo = nullptr, const void *K_lo = nullptr, void *O_lo = nullptr);
-// fused cross-attention (pio_xattn.hip): wide single heads, dv != dk, key / query mask vectors, key splits
-bool xattn_supported(int dkp, int dvp);
-size_t xattn_partial_bytes(int dkp, int dvp, int B, int H, int Tq, int Tk);  // fp32 partials of the key splits (0: none)
-int xattn_launch(int dtype, int dkp, int dvp, int dk_logical, const void *Q, const void *K, const void *VT, void *O,
-                 void *O_lo, int B, int H, int Tq, int Tk, int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo, int64_t sQb,
-                 int64_t sKb, int64_t sVb, int64_t sOb, const uint8_t *kv_mask, const uint8_t *q_mask, void *partials,
-                 hipStream_t s, const void *Q_lo = nullptr, const void *K_lo = nullptr);
-// fused cross-attention for a head wider than the key axis is long (pio_xtall.hip): Tk <= 512, S computed once per query
-// row and kept in registers (the ImageNet decoder's 1024-wide head over 512 latents)
-bool xtall_supported(int dkp, int dvp, int Tk);
-size_t xtall_scratch_bytes(int B);  // key-bit words of a masked launch
-int xtall_launch(int dtype, int dkp, int dvp, int dk_logical, const void *Q, const void *K, const void *VT, void *O,
-                 void *O_lo, int B, int H, int Tq, int Tk, int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo, int64_t sQb,
-                 int64_t sKb, int64_t sVb, int64_t sOb, const uint8_t *kv_mask, const uint8_t *q_mask, void *scratch,
-                 hipStream_t s);
+// The fused attention cores on one operand bundle (AttnOperands; shape tables and routing: pio_attn_route.h).
+// v_rowmajor: t.VT points at V [B][Tk][.. h*dvp ..] (row stride ldvt) instead of V^T [B][H*dvp][Tk].
+int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const AttnOperands &t, int B, int H, int Tq, int Tk,
+                           bool v_rowmajor, hipStream_t s);
+// scratch: xattn_partial_bytes / xtall_scratch_bytes of the launch (key bits of a masked launch, split partials)
+int xattn_launch(int dtype, int dkp, int dvp, int dk_logical, const AttnOperands &t, int B, int H, int Tq, int Tk,
+                 const uint8_t *kv_mask, const uint8_t *q_mask, void *scratch, hipStream_t s);
+int xtall_launch(int dtype, int dkp, int dvp, int dk_logical, const AttnOperands &t, int B, int H, int Tq, int Tk,
+                 const uint8_t *kv_mask, const uint8_t *q_mask, void *scratch, hipStream_t s);
 // eval BatchNorm -> ReLU -> 3x3/2 SAME max-pool -> channels-last tokens (tail of Conv2DDownsample)
 int bn_relu_pool_nhwc_launch(const float *x, const float *scale, const float *shift, float *y, int B, int C, int H, int W,
                              int pad_top, int pad_left, hipStream_t s);

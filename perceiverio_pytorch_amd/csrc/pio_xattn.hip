@@ -561,73 +561,27 @@ __global__ __launch_bounds__(256) void xattn_reduce_kernel(const float *part_o, 
     if (O_lo) *(V4 *)((T *)O_lo + off) = l;
 }
 
-// ---- host side -------------------------------------------------------------------------------------------------
-namespace {
-struct XCfg {
-    int dkl, dvs;
-};
-// the kernel instantiations, narrowest first
-// (the sliced <352,192> / <512,256> instantiations of round 2 became unreachable when the single-pass <352,352> /
-// <512,512> ones were put in front of them in round 3 -- first match wins -- and are gone)
-constexpr XCfg kCfgs[] = {{32, 96}, {32, 160}, {128, 128}, {352, 352}, {512, 512}, {704, 256}};
-
-const XCfg *xattn_cfg(int dkp, int dvp) {
-    for (const XCfg &c : kCfgs) {
-        if (dkp > c.dkl) continue;
-        // a head wider than one slice is cut into dv slices (each recomputes S): only where Q + O do not fit otherwise
-        const bool sliced = c.dkl >= 352;
-        if (dvp <= c.dvs || (sliced && dvp <= c.dkl)) return &c;
-    }
-    return nullptr;
-}
-}  // namespace
-
-bool xattn_supported(int dkp, int dvp) { return xattn_cfg(dkp, dvp) != nullptr; }
-// pair-operand Q K^T: the narrow-head instantiations <32, 96> and <32, 160>, fp16
-bool xattn_pair_supported(int dtype, int dkp, int dvp) {
-    const XCfg *c = xattn_cfg(dkp, dvp);
-    return dtype == PIO_DT_F16 && c && c->dkl == 32;
+// ---- host side (shape tables, key splits and scratch sizes: pio_attn_route.h) ---------------------------------------
+// the instantiation of one XCfg: operand dtype and, on the DKL = 32 fp16 heads, the pair-operand (QK_PAIR) form
+template <int DKL, int DVS>
+static void xattn_launch_dt(int dtype, bool pair, dim3 grid, hipStream_t s, const XattnParams &p) {
+    void (*k)(XattnParams) = dtype == PIO_DT_F16 ? xattn_kernel<PIO_DT_F16, DKL, DVS> : xattn_kernel<PIO_DT_BF16, DKL, DVS>;
+    if constexpr (DKL == 32)
+        if (pair) k = xattn_kernel<PIO_DT_F16, DKL, DVS, true>;
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, p);
 }
 
-// key splits for a launch: about one workgroup per CU and resident slot (wide heads hold one workgroup per CU, narrow
-// ones two) when batch x heads x query tiles x slices alone give clearly fewer, each split keeping >= 8 key tiles.
-// The partials cost HBM traffic (4 dv bytes per query row and split, written and read back): no more splits than that.
-int xattn_splits(int dkp, int dvp, int B, int H, int Tq, int Tk) {
-    const XCfg *c = xattn_cfg(dkp, dvp);
-    if (!c) return 1;
-    const int nslice = (dvp + c->dvs - 1) / c->dvs;
-    const int64_t base = (int64_t)B * H * ((Tq + 127) / 128) * nslice;
-    const int ntiles = (Tk + 31) / 32;
-    const int64_t target = (c->dkl <= 128 && c->dvs <= 160) ? 512 : 256;
-    if (base * 5 >= target * 4 || ntiles < 16) return 1;
-    int64_t s = (target + base - 1) / base;
-    if (s > ntiles / 8) s = ntiles / 8;
-    return s < 1 ? 1 : (int)s;
-}
-
-// scratch of one launch: the key-bit words of a masked launch [B][ntiles], then the fp32 partials of the key splits
-static size_t keybits_bytes(int B, int Tk) { return ((size_t)B * ((Tk + 31) / 32) * 4 + 255) & ~(size_t)255; }
-size_t xattn_partial_bytes(int dkp, int dvp, int B, int H, int Tq, int Tk) {
-    const int s = xattn_splits(dkp, dvp, B, H, Tq, Tk);
-    return keybits_bytes(B, Tk) + (s <= 1 ? 0 : (size_t)B * H * s * Tq * ((size_t)dvp * 4 + 8) + 512);
-}
-
-int xattn_launch(int dtype, int dkp, int dvp, int dk_logical, const void *Q, const void *K, const void *VT, void *O,
-                 void *O_lo, int B, int H, int Tq, int Tk, int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo, int64_t sQb,
-                 int64_t sKb, int64_t sVb, int64_t sOb, const uint8_t *kv_mask, const uint8_t *q_mask, void *partials,
-                 hipStream_t s, const void *Q_lo, const void *K_lo) {
+int xattn_launch(int dtype, int dkp, int dvp, int dk_logical, const AttnOperands &t, int B, int H, int Tq, int Tk,
+                 const uint8_t *kv_mask, const uint8_t *q_mask, void *partials, hipStream_t s) {
     const XCfg *c = xattn_cfg(dkp, dvp);
     if (!c) return PIO_E_SHAPE;
-    if (!Q || !K || !VT || !O) return PIO_E_ARG;
-    const bool pair = Q_lo || K_lo;  // Q and K as (hi, lo) pairs: both halves or neither
-    if (pair && !(Q_lo && K_lo)) return PIO_E_ARG;
+    if (attn_operands_present(t) != PIO_OK) return PIO_E_ARG;
+    const bool pair = t.Q_lo != nullptr;  // Q and K as (hi, lo) pairs
     if (pair && !xattn_pair_supported(dtype, dkp, dvp)) return PIO_E_SHAPE;  // (never a silent single-operand run)
-    if (((uintptr_t)Q_lo & 15) || ((uintptr_t)K_lo & 15)) return PIO_E_ALIGN;
     if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || (dkp & 7) || (dvp & 7)) return PIO_E_SHAPE;
-    if ((ldq % 8) || (ldk % 8) || (ldvt % 8) || (ldo % 4) || (sQb % 8) || (sKb % 8) || (sVb % 8) || (sOb % 4))
-        return PIO_E_ALIGN;
-    if (((uintptr_t)Q & 15) || ((uintptr_t)K & 15) || ((uintptr_t)VT & 15) || ((uintptr_t)O & 7) || ((uintptr_t)O_lo & 7))
-        return PIO_E_ALIGN;
+    if (attn_operands_aligned(t) != PIO_OK) return PIO_E_ALIGN;
+    const int64_t ldk = t.ldk, ldvt = t.ldvt, ldo = t.ldo, sOb = t.sOb;
+    void *const O = t.O, *const O_lo = t.O_lo;
     if (ldvt < 8 || 32 * ldk >= (1ll << 31) || (int64_t)dvp * ldvt >= (1ll << 31)) return PIO_E_SHAPE;
     const int nslice = (dvp + c->dvs - 1) / c->dvs;
     const int nqt = (Tq + 127) / 128;
@@ -639,49 +593,33 @@ int xattn_launch(int dtype, int dkp, int dvp, int dk_logical, const void *Q, con
     const int64_t nwg = (int64_t)B * H * nqt * nslice * nsplit;
     if (nwg > 0x7fffffffLL) return PIO_E_SHAPE;
     XattnParams p{};
-    p.Q = Q; p.K = K; p.VT = VT; p.O = O; p.O_lo = O_lo;
-    p.Q_lo = Q_lo; p.K_lo = K_lo;
+    p.Q = t.Q; p.K = t.K; p.VT = t.VT; p.O = O; p.O_lo = O_lo;
+    p.Q_lo = t.Q_lo; p.K_lo = t.K_lo;
     p.key_bits = kv_mask ? (const uint32_t *)partials : nullptr;
     p.part_o = (float *)((char *)partials + keybits_bytes(B, Tk));
     p.part_ml = nsplit > 1 ? p.part_o + (size_t)B * H * nsplit * Tq * dvp : nullptr;
     p.q_mask = q_mask;
     p.Tq = Tq; p.Tk = Tk; p.H = H; p.nqt = nqt; p.nslice = nslice; p.nsplit = nsplit; p.tiles_per_split = tps;
     p.dkp = dkp; p.dvp = dvp;
-    p.ldq = ldq; p.ldk = ldk; p.ldvt = ldvt; p.ldo = ldo; p.sQb = sQb; p.sKb = sKb; p.sVb = sVb; p.sOb = sOb;
+    p.ldq = t.ldq; p.ldk = ldk; p.ldvt = ldvt; p.ldo = ldo; p.sQb = t.sQb; p.sKb = t.sKb; p.sVb = t.sVb; p.sOb = sOb;
     p.scale_log2 = 1.4426950408889634f / sqrtf((float)dk_logical);
     dim3 grid((unsigned)nwg, 1, 1), block(256, 1, 1);
-    if (kv_mask) {
-        const int64_t words = (int64_t)B * ntiles;
-        hipLaunchKernelGGL(xattn_keybits_kernel, dim3((unsigned)((words + 7) / 8)), block, 0, s, kv_mask,
-                           (uint32_t *)partials, Tk, ntiles, words);
-    }
+    if (kv_mask) xattn_keybits_launch(kv_mask, (uint32_t *)partials, B, Tk, ntiles, s);
     {
         // S recomputed per dv slice counts once: algorithmic flops of the reference formulation
         ProfScope prof(PROF_FLASH, 2.0 * B * H * (double)Tq * Tk * (dkp + dvp),
                        2.0 * B * H * ((double)Tq * (dkp + dvp) + (double)Tk * (dkp + dvp)), s);
-#define PIO_XA(DKLV, DVSV)                                                                                   \
-    do {                                                                                                     \
-        if (dtype == PIO_DT_F16) hipLaunchKernelGGL((xattn_kernel<PIO_DT_F16, DKLV, DVSV>), grid, block, 0, s, p); \
-        else hipLaunchKernelGGL((xattn_kernel<PIO_DT_BF16, DKLV, DVSV>), grid, block, 0, s, p);               \
-    } while (0)
-        if (pair && c->dvs == 96) hipLaunchKernelGGL((xattn_kernel<PIO_DT_F16, 32, 96, true>), grid, block, 0, s, p);
-        else if (pair) hipLaunchKernelGGL((xattn_kernel<PIO_DT_F16, 32, 160, true>), grid, block, 0, s, p);
-        else if (c->dkl == 32 && c->dvs == 96) PIO_XA(32, 96);
-        else if (c->dkl == 32) PIO_XA(32, 160);
-        else if (c->dkl == 128) PIO_XA(128, 128);
-        else if (c->dkl == 352) PIO_XA(352, 352);
-        else if (c->dkl == 512) PIO_XA(512, 512);
-        else PIO_XA(704, 256);
-#undef PIO_XA
+        if (c->dkl == 32 && c->dvs == 96) xattn_launch_dt<32, 96>(dtype, pair, grid, s, p);
+        else if (c->dkl == 32) xattn_launch_dt<32, 160>(dtype, pair, grid, s, p);
+        else if (c->dkl == 128) xattn_launch_dt<128, 128>(dtype, pair, grid, s, p);
+        else if (c->dkl == 352) xattn_launch_dt<352, 352>(dtype, pair, grid, s, p);
+        else if (c->dkl == 512) xattn_launch_dt<512, 512>(dtype, pair, grid, s, p);
+        else xattn_launch_dt<704, 256>(dtype, pair, grid, s, p);
         if (nsplit > 1) {
             const int64_t total = (int64_t)B * H * Tq * (dvp / 4);
-            dim3 rgrid((unsigned)((total + 255) / 256), 1, 1);
-            if (dtype == PIO_DT_F16)
-                hipLaunchKernelGGL((xattn_reduce_kernel<PIO_DT_F16>), rgrid, block, 0, s, p.part_o, p.part_ml, O, O_lo,
-                                   q_mask, H, nsplit, Tq, dvp, ldo, sOb, total);
-            else
-                hipLaunchKernelGGL((xattn_reduce_kernel<PIO_DT_BF16>), rgrid, block, 0, s, p.part_o, p.part_ml, O, O_lo,
-                                   q_mask, H, nsplit, Tq, dvp, ldo, sOb, total);
+            auto reduce = dtype == PIO_DT_F16 ? xattn_reduce_kernel<PIO_DT_F16> : xattn_reduce_kernel<PIO_DT_BF16>;
+            hipLaunchKernelGGL(reduce, dim3((unsigned)((total + 255) / 256)), block, 0, s, p.part_o, p.part_ml, O, O_lo, q_mask,
+                               H, nsplit, Tq, dvp, ldo, sOb, total);
         }
     }
     return launch_status();

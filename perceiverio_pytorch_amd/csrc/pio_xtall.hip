@@ -55,7 +55,6 @@ struct XtallParams {
     float scale_log2;
 };
 
-constexpr int T_NKB = 16;                 // key blocks of 32: the kernel always covers 512 keys
 constexpr int T_STAGE = 40 * 1024;        // K [512][64 B] + Q [128][64 B]; phase B: V^T [256][128 B]
 constexpr int T_QOFF = 32 * 1024;
 constexpr int T_NST = 3;
@@ -446,36 +445,26 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-bool xtall_supported(int dkp, int dvp, int Tk) {
-    return Tk >= 1 && Tk <= 32 * T_NKB && dkp >= 64 && (dkp % 32) == 0 && dvp >= 256 && (dvp % 256) == 0;
-}
-
-size_t xtall_scratch_bytes(int B) { return ((size_t)B * T_NKB * 4 + 255) & ~(size_t)255; }
-
 void xattn_keybits_launch(const uint8_t *kv_mask, uint32_t *bits, int B, int Tk, int ntiles, hipStream_t s);
 
-int xtall_launch(int dtype, int dkp, int dvp, int dk_logical, const void *Q, const void *K, const void *VT, void *O,
-                 void *O_lo, int B, int H, int Tq, int Tk, int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo, int64_t sQb,
-                 int64_t sKb, int64_t sVb, int64_t sOb, const uint8_t *kv_mask, const uint8_t *q_mask, void *scratch,
-                 hipStream_t s) {
-    if (!xtall_supported(dkp, dvp, Tk)) return PIO_E_SHAPE;
-    if (!Q || !K || !VT || !O) return PIO_E_ARG;
+int xtall_launch(int dtype, int dkp, int dvp, int dk_logical, const AttnOperands &t, int B, int H, int Tq, int Tk,
+                 const uint8_t *kv_mask, const uint8_t *q_mask, void *scratch, hipStream_t s) {
+    if (!xtall_supported(dkp, dvp, Tk) || t.Q_lo) return PIO_E_SHAPE;  // (no pair-operand instantiation)
+    if (attn_operands_present(t) != PIO_OK) return PIO_E_ARG;
     if (B <= 0 || H <= 0 || Tq <= 0) return PIO_E_SHAPE;
-    if ((ldq % 8) || (ldk % 8) || (ldvt % 8) || (ldo % 4) || (sQb % 8) || (sKb % 8) || (sVb % 8) || (sOb % 4))
-        return PIO_E_ALIGN;
-    if (((uintptr_t)Q & 15) || ((uintptr_t)K & 15) || ((uintptr_t)VT & 15) || ((uintptr_t)O & 7) || ((uintptr_t)O_lo & 7))
-        return PIO_E_ALIGN;
+    if (attn_operands_aligned(t) != PIO_OK) return PIO_E_ALIGN;
+    const int64_t ldq = t.ldq, ldk = t.ldk, ldvt = t.ldvt;
     if (ldvt < 64 || (int64_t)Tk * ldk >= (1ll << 31) || (int64_t)Tq * ldq >= (1ll << 31) || 256 * ldvt >= (1ll << 31))
         return PIO_E_SHAPE;
     if (kv_mask && !scratch) return PIO_E_WORKSPACE;
     XtallParams p{};
-    p.Q = Q; p.K = K; p.VT = VT; p.O = O; p.O_lo = O_lo;
+    p.Q = t.Q; p.K = t.K; p.VT = t.VT; p.O = t.O; p.O_lo = t.O_lo;
     p.q_mask = q_mask;
     p.key_bits = kv_mask ? (const uint32_t *)scratch : nullptr;
     p.Tq = Tq; p.Tk = Tk; p.H = H; p.nqt = (Tq + 127) / 128; p.dkp = dkp; p.dvp = dvp;
     p.nka = dkp / 32;
     p.npass = dvp / 256;
-    p.ldq = ldq; p.ldk = ldk; p.ldvt = ldvt; p.ldo = ldo; p.sQb = sQb; p.sKb = sKb; p.sVb = sVb; p.sOb = sOb;
+    p.ldq = ldq; p.ldk = ldk; p.ldvt = ldvt; p.ldo = t.ldo; p.sQb = t.sQb; p.sKb = t.sKb; p.sVb = t.sVb; p.sOb = t.sOb;
     p.scale_log2 = 1.4426950408889634f / sqrtf((float)dk_logical);
     const int64_t nwg = (int64_t)B * H * p.nqt;
     if (nwg > 0x7fffffffLL) return PIO_E_SHAPE;
