@@ -11,8 +11,8 @@
  *   - plain C, no torch / HIP types in signatures: `stream` is a hipStream_t passed as void*.
  *   - every pointer is a DEVICE pointer owned by the caller; compute calls allocate and free nothing and
  *     keep no state between calls => they are thread-safe per (stream, workspace).  The only process-wide
- *     mutable state is opt-in tooling, none of it thread-safe: the per-launch profiler (pio_prof_*) and the
- *     A/B switches pio_ln_fold_enable / pio_gemm_kernel_override / pio_set_cu_budget (set them before
+ *     mutable state is opt-in tooling, none of it thread-safe: the per-launch profiler (pio_prof_*), the logit
+ *     probe (pio_logit_probe_*) and the A/B switches pio_ln_fold_enable / pio_gemm_kernel_override / pio_set_cu_budget (set them before
  *     concurrent use).
  *   - scratch memory is caller-provided: query pio_*_workspace_bytes() first.
  *   - tensors at the boundary are float32, last dimension contiguous; batch / row strides are given
@@ -177,6 +177,34 @@ int pio_prof_begin(int32_t max_records);
  * (2*M*N*K per product, extra precision sweeps not counted), algorithmic bytes, launch count.
  * Arrays have PIO_PROF_CLASSES entries (any may be NULL).  Returns the number of records or <0. */
 int pio_prof_end(double *ms, double *flops, double *bytes, int64_t *launches);
+
+/* --- logit probe: how large are the attention logits? (calibration tooling, NOT thread-safe, off by default) ------ */
+/* The fused attention cores round q and k once to the 16-bit operand dtype in front of Q K^T: delta s ~ |s| 2^-11 in the
+ * exponent (fp16).  Whether a checkpoint needs the pair-operand policy "fp16x3fq" depends on how large |s| gets; these
+ * calls measure it.
+ *
+ * pio_qk_logit_absmax: *absmax = max(*absmax, max |q_i . k_j| / sqrt(dk)) over all batches, heads, query rows i < Tq and
+ * keys j < Tk of one attention call, leaving out rows with q_mask[b][i] == 0, keys with kv_mask[b][j] == 0 and positions
+ * with full_mask[b][i][j] == 0 (each mask optional).  Q / K: 16-bit operands in the layout the fused cores read,
+ * [B][T][.. h*dkp ..], row pitches ldq / ldk and batch strides sQb / sKb in elements (sQb = 0: batch-invariant queries);
+ * both may be columns of one stacked q|k|v buffer.  fp32 accumulation; nothing behind row T - 1 or channel dkp - 1 is read.
+ * A non-finite product reports +inf.  `absmax` is ONE device float the caller zeroed (results of several calls max-merge).
+ * No score matrix, no workspace.  PIO_E_SHAPE: dkp % 8 != 0, dk outside [1, dkp], a row pitch below H * dkp;
+ * PIO_E_ALIGN: pointers not 16-byte / pitches and strides not 8-element aligned; PIO_E_ARG: NULL operand, unknown dtype. */
+int pio_qk_logit_absmax(int32_t dtype, int32_t dkp, int32_t dk, const void *Q, const void *K, int32_t B, int32_t H,
+                        int32_t Tq, int32_t Tk, int64_t ldq, int64_t ldk, int64_t sQb, int64_t sKb, const uint8_t *kv_mask,
+                        const uint8_t *q_mask, const uint8_t *full_mask, float *absmax, void *stream);
+/* Process-wide switch (modelled on pio_prof_begin / pio_prof_end): while active, EVERY attention call of the block entry
+ * points (pio_attention_fwd ... pio_encoder_fwd / pio_decoder_fwd) runs pio_qk_logit_absmax once, on the call's stream,
+ * over the operands its core is about to exponentiate and with the call's masks -- whichever route the call takes (stacked
+ * q|k|v buffer; K / V fold: Q Wk against the LayerNorm'd inputs, without the per-row constant q . bk that softmax cancels;
+ * pair cores: hi halves; tall-head; materialised) -- and writes records[n++].  The attention bias is not part of the
+ * figure.  `records`: caller-zeroed device buffer of max_records floats, alive until pio_logit_probe_end.  Routing, the
+ * workspace sizes and every result are unchanged; with the probe inactive nothing extra is launched. */
+int pio_logit_probe_begin(float *records, int32_t max_records);
+/* Stop; returns the number of attention calls seen since begin (calls past max_records are counted, not recorded; 0 when
+ * the probe was not active).  Does not synchronise: the records are complete once the streams used have drained. */
+int pio_logit_probe_end(void);
 
 /* --- LayerNorm fold of the SelfAttention blocks (pio_ln_fold_t), for tests and A/B benchmarks ------ */
 /* 0: never; 1: where it pays (default; env PIO_LN_FOLD gives the initial value) -- blocks of >= 6144 rows (env

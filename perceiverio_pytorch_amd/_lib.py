@@ -99,6 +99,10 @@ SIGNATURES = {
     "pio_error_string": (C.c_char_p, [C.c_int]),
     "pio_prof_begin": (C.c_int, [_i32]),
     "pio_prof_end": (C.c_int, [P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_int64)]),
+    "pio_qk_logit_absmax": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _vp, _vp,
+                                      _vp, _vp, _vp]),
+    "pio_logit_probe_begin": (C.c_int, [_vp, _i32]),
+    "pio_logit_probe_end": (C.c_int, []),
     "pio_pad8": (_i32, [_i32]),
     "pio_padc": (_i32, [_i32]),
     "pio_gemm_kernel_override": (C.c_int, [C.c_int]),

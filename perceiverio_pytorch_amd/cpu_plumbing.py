@@ -15,6 +15,8 @@ import math
 import torch
 import torch.nn.functional as F
 
+from . import probe as LP
+
 
 def attention(m, xq, xk, xv, attention_mask=None, attention_bias=None, return_matrix=False):
     """Attention.forward (:90-180): projections, per-head scaled dot product (the bias is added BEFORE the scale),
@@ -25,6 +27,7 @@ def attention(m, xq, xk, xv, attention_mask=None, attention_bias=None, return_ma
     q = m.proj_q(xq).reshape(B, Tq, H, -1).permute(0, 2, 1, 3)
     k = m.proj_k(xk).reshape(B, Tk, H, -1).permute(0, 2, 1, 3)
     v = m.proj_v(xv).reshape(B, Tk, H, -1).permute(0, 2, 1, 3)
+    LP.record_cpu(q, k, attention_mask)                  # (no-op unless a logit_probe() is active)
     s = q @ k.transpose(-1, -2)
     if attention_bias is not None:
         s = s + attention_bias
@@ -76,10 +79,12 @@ def encoder(m, inputs, latents, input_mask=None):
     if input_mask is not None:
         ones = torch.ones(latents.shape[:2], dtype=torch.bool, device=latents.device)
         mask = _outer_mask(ones, input_mask.bool())
-    z = cross_attention(m.cross_attend, latents, inputs, mask)
-    for _ in range(m._num_blocks):
-        for sa in m.self_attends:
-            z = self_attention(sa, z)
+    with LP.part("cross"):
+        z = cross_attention(m.cross_attend, latents, inputs, mask)
+    with LP.part("stack"):
+        for _ in range(m._num_blocks):
+            for sa in m.self_attends:
+                z = self_attention(sa, z)
     return z
 
 
@@ -89,5 +94,6 @@ def decoder(m, query, latents, query_mask=None):
     if query_mask is not None:
         ones = torch.ones(latents.shape[:2], dtype=torch.bool, device=latents.device)
         mask = _outer_mask(query_mask.bool(), ones)
-    y = cross_attention(m.decoding_cross_attn, query, latents, mask)
+    with LP.part("decoder"):
+        y = cross_attention(m.decoding_cross_attn, query, latents, mask)
     return m.final_layer(y) if m._final_project else y

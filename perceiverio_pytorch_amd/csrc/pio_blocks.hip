@@ -404,6 +404,10 @@ static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair 
         t.sQb = sQ * Tq * ldq; t.sKb = (int64_t)Tk * ldq; t.sVb = ldo * tkv; t.sOb = (int64_t)Tq * ldo;
     }
 
+    // logit probe (pio_logit_probe_begin; tooling, off by default): the operands the core is about to exponentiate --
+    // hi halves, without the bias -- under the call's masks
+    if (logit_probe_active())
+        PIO_TRY(logit_probe_record(a.dtype, a.dkp, a.dk, t, B, H, Tq, Tk, kv_mask, q_mask, full_mask, s));
     switch (r.core) {
     case AttnCore::QKV_FLASH: case AttnCore::PAIR_FLASH: case AttnCore::FLASH:
         PIO_TRY(flash_attention_launch(a.dtype, a.dkp, a.dvp, a.dk, t, B, H, Tq, Tk, r.core == AttnCore::QKV_FLASH, s));

@@ -112,6 +112,17 @@ int pio_prof_end(double *ms, double *flops, double *bytes, int64_t *launches) {
     return n;
 }
 
+int pio_logit_probe_begin(float *records, int32_t max_records) { return logit_probe_begin(records, max_records); }
+
+int pio_logit_probe_end(void) { return logit_probe_end(); }
+
+int pio_qk_logit_absmax(int32_t dtype, int32_t dkp, int32_t dk, const void *Q, const void *K, int32_t B, int32_t H,
+                        int32_t Tq, int32_t Tk, int64_t ldq, int64_t ldk, int64_t sQb, int64_t sKb, const uint8_t *kv_mask,
+                        const uint8_t *q_mask, const uint8_t *full_mask, float *absmax, void *stream) {
+    return qk_absmax_launch(dtype, dkp, dk, Q, K, B, H, Tq, Tk, ldq, ldk, sQb, sKb, kv_mask, q_mask, full_mask, absmax,
+                            (hipStream_t)stream);
+}
+
 int pio_version(void) { return PIO_VERSION; }
 
 int pio_arch_ok(void) {

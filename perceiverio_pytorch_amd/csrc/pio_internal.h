@@ -126,6 +126,17 @@ int xattn_launch(int dtype, int dkp, int dvp, int dk_logical, const AttnOperands
                  const uint8_t *kv_mask, const uint8_t *q_mask, void *scratch, hipStream_t s);
 int xtall_launch(int dtype, int dkp, int dvp, int dk_logical, const AttnOperands &t, int B, int H, int Tq, int Tk,
                  const uint8_t *kv_mask, const uint8_t *q_mask, void *scratch, hipStream_t s);
+// Logit probe (pio_qkprobe.hip; tooling, off by default): max |q_i . k_j| / sqrt(dk) over the attendable positions of
+// one attention call, max-merged into *absmax.  logit_probe_record: what attention_core calls while the probe is active
+// (record n++ of pio_logit_probe_begin's buffer).
+int qk_absmax_launch(int dtype, int dkp, int dk, const void *Q, const void *K, int B, int H, int Tq, int Tk, int64_t ldq,
+                     int64_t ldk, int64_t sQb, int64_t sKb, const uint8_t *kv_mask, const uint8_t *q_mask,
+                     const uint8_t *full_mask, float *absmax, hipStream_t s);
+bool logit_probe_active();
+int logit_probe_record(int dtype, int dkp, int dk, const AttnOperands &t, int B, int H, int Tq, int Tk,
+                       const uint8_t *kv_mask, const uint8_t *q_mask, const uint8_t *full_mask, hipStream_t s);
+int logit_probe_begin(float *records, int max_records);
+int logit_probe_end();
 // eval BatchNorm -> ReLU -> 3x3/2 SAME max-pool -> channels-last tokens (tail of Conv2DDownsample)
 int bn_relu_pool_nhwc_launch(const float *x, const float *scale, const float *shift, float *y, int B, int C, int H, int W,
                              int pad_top, int pad_left, hipStream_t s);

@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import probe as LP
 from . import runtime as R
 from .position_encoding import TrainablePositionEncoding
 from .transformer_primitives import CrossAttention, SelfAttention, lecun_normal_, make_cross_attention_mask  # noqa: F401
@@ -119,6 +120,7 @@ class PerceiverEncoder(nn.Module):
             ws = R.workspace(dev, lib.pio_encoder_workspace_bytes(cross, layers, Lyr, B, M, N))
             # (the un-folded repeat of the range guard is a PER-CALL option: no process state changes around the call)
             opts = L.CallOpts(1 if self._range_fallback else 0, 0)
+            LP.expect("cross", *["stack"] * (Lyr * self._num_blocks))    # (one attention call per block, this order)
             with R.on_device(dev):
                 L.check(lib.pio_encoder_fwd_opts(cross, layers, Lyr, self._num_blocks, int(per_block), R.tensor3(x),
                                                  tail3, R.tensor3(z0), im_ptr, out.data_ptr(), ws.data_ptr(),
@@ -137,6 +139,7 @@ class PerceiverEncoder(nn.Module):
         for side in sides:                   # every slice starts behind the work already queued on `cur` ...
             side.wait_stream(cur)
         for i, side in enumerate(sides):
+            LP.expect("cross", *["stack"] * (Lyr * self._num_blocks))
             with R.on_device(dev), torch.cuda.stream(side):
                 xs, zs = x[i * bs:(i + 1) * bs], z0[i * bs:(i + 1) * bs]
                 ws = R.workspace(dev, lib.pio_encoder_workspace_bytes(cross, layers, Lyr, bs, M, N))
@@ -289,6 +292,7 @@ class PerceiverDecoder(nn.Module):
                 qhi = q_cache["hi"].data_ptr()
                 qlo = q_cache["lo"].data_ptr() if q_cache["lo"] is not None else None
                 valid = 1 if q_cache["valid"] else 0
+        LP.expect("decoder")
         with R.on_device(dev):
             if query_tail is not None:
                 L.check(lib.pio_decoder_fwd_split(cross, fin_ptr, out_ch, R.tensor3(q), R.tensor3(query_tail), R.tensor3(z),

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import probe as LP
 from . import runtime as R
 
 
@@ -228,6 +229,7 @@ class Attention(_HipModule):
         nbytes = lib.pio_attention_workspace_bytes(d, B, Tq, Tk)
         ws = R.workspace(dev, nbytes)
         tq, tk, tv = R.tensor3(xq), R.tensor3(xk), R.tensor3(xv)
+        LP.expect("attention")
         with R.on_device(dev):
             L.check(lib.pio_attention_fwd(d, tq, tk, tv, None, None, fm_ptr,
                                           bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
@@ -422,6 +424,7 @@ class SelfAttention(_HipModule):
         out = torch.empty((B, N, D), dtype=torch.float32, device=dev)
         probs = torch.empty((B, H, N, N), dtype=torch.float32, device=dev) if return_matrix else None
         ws = R.workspace(dev, lib.pio_self_attention_workspace_bytes(d, B, N))
+        LP.expect("attention")
         with R.on_device(dev):
             L.check(lib.pio_self_attention_fwd(d, R.tensor3(x), None, None, fm_ptr,
                                                bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
@@ -504,6 +507,7 @@ class CrossAttention(_HipModule):
         out = torch.empty((B, Tq, Cq), dtype=torch.float32, device=dev)
         probs = torch.empty((B, H, Tq, Tk), dtype=torch.float32, device=dev) if return_matrix else None
         ws = R.workspace(dev, lib.pio_cross_attention_workspace_bytes(d, B, Tq, Tk))
+        LP.expect("attention")
         with R.on_device(dev):
             L.check(lib.pio_cross_attention_fwd(d, R.tensor3(xq), R.tensor3(xkv), None, None, fm_ptr,
                                                 bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
