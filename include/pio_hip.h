@@ -18,7 +18,8 @@
  *   - tensors at the boundary are float32, last dimension contiguous; batch / row strides are given
  *     in ELEMENTS (a batch stride of 0 is a broadcast view, e.g. the latent table of
  *     position_encoding.py:117-121).
- *   - masks are uint8 (0 = masked out), the storage of torch.bool.
+ *   - masks are uint8, the storage of torch.bool: a mask byte is true iff non-zero (0 = masked out; 1, 2, 0x80, 0xFF
+ *     all attend).
  *   - return value: PIO_OK (0) or a negative PIO_E_* code; no exceptions cross the ABI.
  *   - matrix operands inside the library are fp16 (default) or bf16 with fp32 accumulation;
  *     LayerNorm, softmax, bias, GELU and the residual stream are fp32.
@@ -261,7 +262,9 @@ int pio_layernorm_cast(const pio_tensor3_t *x, const pio_layernorm_t *ln, void *
 /* The same LayerNorm over the channel-wise CONCATENATION [x1 | x2] of two arrays, never materialised: x1 [B,T,C1],
  * x2 [B,T,C2] or ONE batch-invariant table [1,T,C2] (x2->B == 1); ln->c == C1 + C2; C1, C2 even, rows 8-byte aligned.
  * Replaces torch.cat([features, position_features], -1) of preprocessors.py:176-200 followed by layer_norm_kv
- * (transformer_primitives.py:379); bit-identical to pio_layernorm_cast of the concatenated array. */
+ * (transformer_primitives.py:379); bit-identical to pio_layernorm_cast of the concatenated array wherever that call runs
+ * its 8-byte-lane kernel, whose arithmetic this one restates (a width that is no multiple of 4, or rows that are only
+ * 8-byte aligned); a 16-byte-lane kernel sums in another order and may differ in the last bit of the fp32 statistics. */
 int pio_layernorm_cast_cat(const pio_tensor3_t *x1, const pio_tensor3_t *x2, const pio_layernorm_t *ln, void *y,
                            void *y_lo, int32_t c_pad, int32_t dtype, void *stream);
 

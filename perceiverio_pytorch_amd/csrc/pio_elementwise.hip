@@ -682,8 +682,8 @@ __global__ __launch_bounds__(256) void softmax_rows_reg_kernel(const SoftmaxPara
                 const f32x4 bv = *(const f32x4 *)(bi + kc);
                 v[j] += bv;
             }
-            uint32_t mk = 0x01010101u;
-            if (km) mk &= *(const uint32_t *)(km + kc);
+            uint32_t mk = 0x01010101u;   // one byte per key: true iff non-zero, like every other mask test
+            if (km) mk = *(const uint32_t *)(km + kc);
             if (fm) {
                 const uint32_t f = *(const uint32_t *)(fm + kc);
                 mk = ((mk & 0xffu) && (f & 0xffu) ? 1u : 0u) | ((mk & 0xff00u) && (f & 0xff00u) ? 0x100u : 0u) |
