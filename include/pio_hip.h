@@ -357,10 +357,15 @@ int pio_flash_attention(int32_t dtype, int32_t dkp, int32_t dvp, int32_t dk, con
  * the rounding residual of O), kv_mask [B,Tk] / q_mask [B,Tq] (optional uint8 vectors; rows without an attendable key and
  * rows with q_mask == 0 are written as zeros) and
  *   core: 0 = by shape -- the self-attention kernel when no mask is given and it covers (dkp, dvp), else the cross-attention
- *         kernel; 1 = the self-attention kernel (flash_attn_kernel); 2 = the cross-attention kernel (xattn_kernel).
+ *         kernel; 1 = the self-attention kernel (flash_attn_kernel); 2 = the cross-attention kernel (xattn_kernel);
+ *         3 = the tall-head kernel (xattn_tall_kernel: Tk <= 512, dkp >= 64 a multiple of 32, dvp a multiple of 256) with the
+ *         operands of core 2 -- V^T (ldv >= 64, finite columns behind Tk), mask vectors, `workspace`, O_lo allowed, no
+ *         Q_lo / K_lo -- PIO_E_SHAPE for any other shape, PIO_E_WORKSPACE below its key-bit words.  Core 0 never picks it.
  * The cross-attention kernel reads V^T only (v_rowmajor == 0, ldv a multiple of 32 with zero-filled columns behind Tk), reads
  * whole 32-key tiles of K / K_lo (the 31 rows behind key Tk - 1 of the last sample must be readable) and needs
- * `workspace` (pio_flash_attention_pair_workspace_bytes: key-bit words of a masked launch, fp32 partials of a key split).
+ * `workspace` (pio_flash_attention_pair_workspace_bytes: key-bit words of a masked launch, fp32 partials of a key split;
+ * for a shape only the tall-head kernel covers its key-bit words, for a shape both kernels cover the larger of the two, so
+ * that the figure serves whichever core is named).
  * Pair operands: fp16, dkp <= 32 -- (32,32) / (32,160) on the self-attention kernel, dvp <= 160 on the cross-attention
  * kernel; anything else with Q_lo / K_lo is PIO_E_SHAPE (bf16 included). */
 size_t pio_flash_attention_pair_workspace_bytes(int32_t dkp, int32_t dvp, int32_t B, int32_t H, int32_t Tq, int32_t Tk);
