@@ -12,7 +12,7 @@
  *   - every pointer is a DEVICE pointer owned by the caller; compute calls allocate and free nothing and
  *     keep no state between calls => they are thread-safe per (stream, workspace).  The only process-wide
  *     mutable state is opt-in tooling, none of it thread-safe: the per-launch profiler (pio_prof_*), the logit
- *     probe (pio_logit_probe_*) and the A/B switches pio_ln_fold_enable / pio_gemm_kernel_override / pio_set_cu_budget (set them before
+ *     probe (pio_logit_probe_*), the range probe (pio_range_probe_*) and the A/B switches pio_ln_fold_enable / pio_gemm_kernel_override / pio_set_cu_budget (set them before
  *     concurrent use).
  *   - scratch memory is caller-provided: query pio_*_workspace_bytes() first.
  *   - tensors at the boundary are float32, last dimension contiguous; batch / row strides are given
@@ -206,6 +206,50 @@ int pio_logit_probe_begin(float *records, int32_t max_records);
 /* Stop; returns the number of attention calls seen since begin (calls past max_records are counted, not recorded; 0 when
  * the probe was not active).  Does not synchronise: the records are complete once the streams used have drained. */
 int pio_logit_probe_end(void);
+
+/* --- range probe: do the 16-bit operands fit their dtype? (calibration tooling, NOT thread-safe, off by default) ---- */
+/* Every matrix operand inside the library is 16-bit; with fp16 anything beyond 65 504 becomes inf.  Only the LayerNorm-
+ * folded stack has a device-side guard (pio_ln_fold_t.range_flag); these calls measure every other 16-bit buffer, so that
+ * a caller can tell which part of a model needs a bf16 policy.
+ *
+ * pio_absmax16: *absmax = max(*absmax, max |float(x[b][r][c])|) over b < batch, r < rows, c < cols.  x: 16-bit operands
+ * (PIO_DT_F16 / PIO_DT_BF16), row pitch ld and batch stride stride_b in ELEMENTS; stride_b = 0 means one batch is read.
+ * A non-finite element (NaN, +-inf) reports +inf.  `absmax` is ONE device float the caller zeroed (results of several
+ * calls max-merge).  Nothing behind column cols - 1 of a row, behind the last row or in front of x is read, whatever the
+ * alignment of x (2 bytes suffice) and the pitch.  No workspace.  PIO_E_ARG: NULL pointer, unknown dtype; PIO_E_SHAPE: a
+ * negative extent, cols > ld with rows > 1; PIO_E_ALIGN: x not 2-byte / absmax not 4-byte aligned.  Empty extents are
+ * PIO_OK and leave *absmax unchanged. */
+int pio_absmax16(int32_t dtype, const void *x, int64_t rows, int32_t cols, int64_t ld, int32_t batch, int64_t stride_b,
+                 float *absmax, void *stream);
+/* What a record of the range probe measured ... */
+enum {
+    PIO_RK_CAST = 0,   /* LayerNorm+cast or plain-cast output (the two-source form included)                        */
+    PIO_RK_Q = 1,      /* projected queries; a stacked q|k or q|k|v GEMM is ONE record over the whole stacked width    */
+    PIO_RK_K = 2,      /* projected keys                                                                               */
+    PIO_RK_V = 3,      /* projected values (as V^T)                                                                    */
+    PIO_RK_ATTN = 4,   /* output of the attention core (the materialised route's P V product as well)                  */
+    PIO_RK_HIDDEN = 5, /* fc1 + GELU                                                                                   */
+    PIO_RK_STREAM = 6  /* the LayerNorm fold's 16-bit residual stream X16, and a decoder's y16 in front of its final Linear */
+};
+/* ... and the part of the model it belongs to (pio_range_probe_mark) */
+enum { PIO_RP_ATTENTION = 0, PIO_RP_CROSS = 1, PIO_RP_STACK = 2, PIO_RP_DECODER = 3 };
+/* Process-wide switch (modelled on pio_logit_probe_begin / _end; the two probes may be active together): while active,
+ * EVERY 16-bit activation buffer produced inside the block entry points (pio_attention_fwd, pio_mlp_fwd ...
+ * pio_encoder_fwd_* / pio_decoder_fwd_*) gets one pio_absmax16 on the call's stream, right behind its producer, into
+ * records[n++]; the library keeps (part, kind) of every record on the host.  Hi halves only (a lo residual is below one
+ * ulp of its hi half); the probabilities P (at most 1), a projected-query cache that is read but not written, and the
+ * transposed copy of the LayerNorm'd inputs a K / V-folded cross-attend makes produce no record.  `records`: caller-zeroed
+ * device buffer of max_records floats, alive until pio_range_probe_end.  Routing, the workspace sizes and every result are
+ * unchanged; with the probe inactive nothing extra is launched.  Not capturable (host-side state). */
+int pio_range_probe_begin(float *records, int32_t max_records);
+/* Host-side label of the records that follow: a PIO_RP_* (PIO_E_ARG otherwise); PIO_RP_ATTENTION after begin.  The
+ * encoder entry points run the cross-attend and the stack in one call: they mark PIO_RP_STACK behind the cross-attend
+ * themselves and restore the caller's part when they return.  Without an active probe the call does nothing. */
+int pio_range_probe_mark(int32_t part);
+/* Stop; returns the number of records seen since begin (records past max_records are counted, not recorded; 0 when the
+ * probe was not active) and fills parts[i] / kinds[i] (HOST arrays of `cap` entries, either may be NULL) for the recorded
+ * ones.  Does not synchronise: the figures are complete once the streams used have drained. */
+int pio_range_probe_end(int32_t *parts, int32_t *kinds, int32_t cap);
 
 /* --- LayerNorm fold of the SelfAttention blocks (pio_ln_fold_t), for tests and A/B benchmarks ------ */
 /* 0: never; 1: where it pays (default; env PIO_LN_FOLD gives the initial value) -- blocks of >= 6144 rows (env

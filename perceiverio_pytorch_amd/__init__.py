@@ -3,6 +3,7 @@ behind a C-ABI (include/pio_hip.h), exposed through the reference's own nn.Modul
 from .runtime import (get_backend, get_precision_policy, invalidate_packed_weights, set_backend,  # noqa: F401
                       set_precision_policy)
 from ._lib import PioError, build, lib  # noqa: F401
-from .probe import logit_probe, recommend_precision_policy  # noqa: F401
+from .probe import (logit_probe, range_probe, recommend_operand_dtype,  # noqa: F401
+                    recommend_precision_policy)
 
 __version__ = "0.1.0"

@@ -103,6 +103,10 @@ SIGNATURES = {
                                       _vp, _vp, _vp]),
     "pio_logit_probe_begin": (C.c_int, [_vp, _i32]),
     "pio_logit_probe_end": (C.c_int, []),
+    "pio_absmax16": (C.c_int, [_i32, _vp, _i64, _i32, _i64, _i32, _i64, _vp, _vp]),
+    "pio_range_probe_begin": (C.c_int, [_vp, _i32]),
+    "pio_range_probe_mark": (C.c_int, [_i32]),
+    "pio_range_probe_end": (C.c_int, [P(_i32), P(_i32), _i32]),
     "pio_pad8": (_i32, [_i32]),
     "pio_padc": (_i32, [_i32]),
     "pio_gemm_kernel_override": (C.c_int, [C.c_int]),

@@ -18,7 +18,22 @@ import torch.nn.functional as F
 from . import probe as LP
 
 
+# Range probe (probe.record_range_cpu; a no-op unless a range_probe() is active): the tensors below are the ones whose
+# 16-bit images the HIP backend measures, with the same kinds in the same order (un-stacked: q, k and v are one record
+# each here).
+
+
 def attention(m, xq, xk, xv, attention_mask=None, attention_bias=None, return_matrix=False):
+    """Attention.forward on raw inputs: the library casts them to 16-bit operands first (one cast for k and v when they
+    are the same tensor)."""
+    LP.record_range_cpu("cast", xq)
+    LP.record_range_cpu("cast", xk)
+    if xv is not xk:
+        LP.record_range_cpu("cast", xv)
+    return _attention(m, xq, xk, xv, attention_mask, attention_bias, return_matrix)
+
+
+def _attention(m, xq, xk, xv, attention_mask=None, attention_bias=None, return_matrix=False):
     """Attention.forward (:90-180): projections, per-head scaled dot product (the bias is added BEFORE the scale),
     mask to -1e30, softmax, P V, rows without an attendable key wiped to zero, final projection."""
     H = m._num_heads
@@ -27,6 +42,9 @@ def attention(m, xq, xk, xv, attention_mask=None, attention_bias=None, return_ma
     q = m.proj_q(xq).reshape(B, Tq, H, -1).permute(0, 2, 1, 3)
     k = m.proj_k(xk).reshape(B, Tk, H, -1).permute(0, 2, 1, 3)
     v = m.proj_v(xv).reshape(B, Tk, H, -1).permute(0, 2, 1, 3)
+    LP.record_range_cpu("q", q)
+    LP.record_range_cpu("k", k)
+    LP.record_range_cpu("v", v)
     LP.record_cpu(q, k, attention_mask)                  # (no-op unless a logit_probe() is active)
     s = q @ k.transpose(-1, -2)
     if attention_bias is not None:
@@ -39,29 +57,47 @@ def attention(m, xq, xk, xv, attention_mask=None, attention_bias=None, return_ma
     if attention_mask is not None:
         live = attention_mask.any(dim=2)
         o = torch.where(live[:, :, None], o, torch.zeros_like(o))
+    LP.record_range_cpu("attn", o)
     out = m.final(o)
     return (p, out) if return_matrix else out
 
 
 def mlp(m, x):
-    return m.dropout(m.fc2(F.gelu(m.fc1(x))))           # exact (erf) GELU, :212-216
+    """MLP.forward on a raw input: the library casts it to a 16-bit operand first."""
+    LP.record_range_cpu("cast", x)
+    return _mlp(m, x)
+
+
+def _mlp(m, x):
+    h = F.gelu(m.fc1(x))                                # exact (erf) GELU, :212-216
+    LP.record_range_cpu("hidden", h)
+    return m.dropout(m.fc2(h))
 
 
 def self_attention(m, x, attention_mask=None, attention_bias=None, return_matrix=False):
-    r = attention(m.attention, *(3 * (m.layer_norm1(x),)), attention_mask, attention_bias, return_matrix)
+    n1 = m.layer_norm1(x)
+    LP.record_range_cpu("cast", n1)
+    r = _attention(m.attention, n1, n1, n1, attention_mask, attention_bias, return_matrix)
     probs, a = r if return_matrix else (None, r)
     x = x + m.dropout(a)                                # (:289-290)
-    x = x + mlp(m.mlp, m.layer_norm2(x))
+    n2 = m.layer_norm2(x)
+    LP.record_range_cpu("cast", n2)
+    x = x + _mlp(m.mlp, n2)
     return (probs, x) if return_matrix else x
 
 
 def cross_attention(m, xq, xkv, attention_mask=None, attention_bias=None, return_matrix=False):
     kv = m.layer_norm_kv(xkv)
-    r = attention(m.attention, m.layer_norm_q(xq), kv, kv, attention_mask, attention_bias, return_matrix)
+    LP.record_range_cpu("cast", kv)
+    nq = m.layer_norm_q(xq)
+    LP.record_range_cpu("cast", nq)
+    r = _attention(m.attention, nq, kv, kv, attention_mask, attention_bias, return_matrix)
     probs, a = r if return_matrix else (None, r)
     a = m.dropout(a)                                    # (:390)
     x = xq + a if m._use_query_residual else a
-    x = x + mlp(m.mlp, m.layer_norm2(x))
+    n2 = m.layer_norm2(x)
+    LP.record_range_cpu("cast", n2)
+    x = x + _mlp(m.mlp, n2)
     return (probs, x) if return_matrix else x
 
 
@@ -96,4 +132,6 @@ def decoder(m, query, latents, query_mask=None):
         mask = _outer_mask(query_mask.bool(), ones)
     with LP.part("decoder"):
         y = cross_attention(m.decoding_cross_attn, query, latents, mask)
+        if m._final_project:
+            LP.record_range_cpu("stream", y)            # (the 16-bit y16 in front of the final Linear)
     return m.final_layer(y) if m._final_project else y

@@ -20,6 +20,14 @@ namespace pio {
         if (_e != PIO_OK) return _e;   \
     } while (0)
 
+// Range probe (pio_range_probe_begin; tooling, off by default): one pio_absmax16 over the hi half of a 16-bit activation
+// buffer, right behind its producer.  kind: PIO_RK_*; the extent is (batch x) rows x cols with row pitch ld.
+#define PIO_RANGE(kind, dtype, ptr, rows, cols, ld, batch, stride_b, stream) \
+    do {                                                                      \
+        if (range_probe_active())                                             \
+            PIO_TRY(range_probe_record(kind, dtype, ptr, rows, cols, ld, batch, stride_b, stream)); \
+    } while (0)
+
 struct Pair {  // a 16-bit operand and its optional rounding residual
     void *hi = nullptr, *lo = nullptr;
 };
@@ -135,8 +143,11 @@ static int linear_fwd(const pio_linear_t &lin_plain, int dtype, Pair x, int64_t 
     return gemm_nt_launch(g, s);
 }
 
-static int cast_pair(const pio_tensor3_t &x, const pio_layernorm_t *ln, Pair y, int c_pad, int dtype, hipStream_t s) {
-    return layernorm_cast_launch(x, ln, y.hi, y.lo, c_pad, dtype, s);
+static int cast_pair(const pio_tensor3_t &x, const pio_layernorm_t *ln, Pair y, int c_pad, int dtype, hipStream_t s,
+                     int range_kind = PIO_RK_CAST) {
+    PIO_TRY(layernorm_cast_launch(x, ln, y.hi, y.lo, c_pad, dtype, s));
+    PIO_RANGE(range_kind, dtype, y.hi, (int64_t)x.B * x.T, x.C, c_pad, 1, 0, s);
+    return PIO_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -350,6 +361,7 @@ static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair 
     if (r.core == AttnCore::QKV_FLASH) {
         // ONE GEMM over the stacked [q | k | v] weight image; the core reads V row-major (transposed LDS reads)
         PIO_TRY(linear_fwd(a.qkv, a.dtype, xq, (int64_t)B * Tq, w.q16.hi, nullptr, false, 0, ld3, 0, nullptr, s, fold_in));
+        PIO_RANGE(PIO_RK_Q, a.dtype, w.q16.hi, (int64_t)B * Tq, ld3, ld3, 1, 0, s);
         const char *base = (const char *)w.q16.hi;
         t.Q = base; t.K = base + hdk * 2; t.VT = base + 2 * hdk * 2;
         t.ldq = t.ldk = t.ldvt = ld3; t.ldo = ldo;
@@ -360,7 +372,9 @@ static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair 
         // (otherwise unused) k16 scratch, one 16-bit transpose of the inputs and the out projection (Wo Wv) over K = C.
         const int64_t kvp = a.dkp, ldx = padc(a.k_in);  // ldx: row pitch of the LayerNorm'd inputs
         PIO_TRY(linear_fwd(a.q, a.dtype, xq, (int64_t)Bq * Tq, w.q16.hi, w.q16.lo, false, 0, hdk, 0, nullptr, s));
+        PIO_RANGE(PIO_RK_Q, a.dtype, w.q16.hi, (int64_t)Bq * Tq, hdk, hdk, 1, 0, s);
         PIO_TRY(linear_fwd(a.kq, a.dtype, w.q16, (int64_t)Bq * Tq, w.k16.hi, w.k16.lo, false, 0, kvp, 0, nullptr, s));
+        PIO_RANGE(PIO_RK_Q, a.dtype, w.k16.hi, (int64_t)Bq * Tq, kvp, kvp, 1, 0, s);  // (Q Wk: the core's query operand)
         PIO_TRY(transpose16_launch(xk.hi, ldx, B, Tk, (int)kvp, w.vt16.hi, tkv, s));
         t.Q = w.k16.hi; t.K = xk.hi; t.VT = w.vt16.hi;
         t.ldq = kvp; t.ldk = ldx; t.ldvt = tkv; t.ldo = kvp;
@@ -371,10 +385,14 @@ static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair 
         const int64_t ldq = r.fuse_qk ? 2 * hdk : hdk;
         if (r.fuse_qk) {
             PIO_TRY(linear_fwd(a.qk, a.dtype, xq, (int64_t)B * Tq, w.q16.hi, nullptr, false, 0, ldq, 0, nullptr, s));
+            PIO_RANGE(PIO_RK_Q, a.dtype, w.q16.hi, (int64_t)B * Tq, ldq, ldq, 1, 0, s);
         } else {
-            if (!(qc && qc->valid))
+            if (!(qc && qc->valid)) {
                 PIO_TRY(linear_fwd(a.q, a.dtype, xq, (int64_t)Bq * Tq, w.q16.hi, w.q16.lo, false, 0, ldq, 0, nullptr, s));
+                PIO_RANGE(PIO_RK_Q, a.dtype, w.q16.hi, (int64_t)Bq * Tq, ldq, ldq, 1, 0, s);
+            }
             PIO_TRY(linear_fwd(a.k, a.dtype, xk, (int64_t)B * Tk, w.k16.hi, w.k16.lo, false, 0, ldq, 0, nullptr, s));
+            PIO_RANGE(PIO_RK_K, a.dtype, w.k16.hi, (int64_t)B * Tk, ldq, ldq, 1, 0, s);
         }
         // V^T[b] = Wv * X_v[b]^T + bv produced directly in the K-contiguous layout the P*V product wants; the weight is
         // the A operand (batch stride 0), bias is per output ROW.
@@ -398,6 +416,7 @@ static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair 
         g.bias_mode = a.v.bias ? 2 : 0;
         g.n_store = (int)tkv;  // columns [Tk, tkv) are written as zeros
         PIO_TRY(gemm_nt_launch(g, s));
+        PIO_RANGE(PIO_RK_V, a.dtype, w.vt16.hi, ldo, Tk, tkv, B, ldo * tkv, s);
         t.Q = w.q16.hi; t.K = r.fuse_qk ? (const char *)w.q16.hi + hdk * 2 : w.k16.hi; t.VT = w.vt16.hi;
         if (r.qk_pair) { t.Q_lo = w.q16.lo; t.K_lo = w.k16.lo; }
         t.ldq = t.ldk = ldq; t.ldvt = tkv; t.ldo = ldo;
@@ -422,10 +441,14 @@ static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair 
         PIO_TRY(materialised_core(a, t, q_bcast, B, Tq, Tk, kv_mask, q_mask, full_mask, attention_bias, probs_out, w, s));
         break;
     }
+    PIO_RANGE(PIO_RK_ATTN, a.dtype, w.o16.hi, (int64_t)B * Tq, t.ldo, t.ldo, 1, 0, s);
     // final projection (+ residual) (transformer_primitives.py:110; SelfAttention :290, CrossAttention :396-399); behind
     // the K / V fold it is Wo Wv
-    return linear_fwd(kv_fold ? a.vo : a.o, a.dtype, w.o16, (int64_t)B * Tq, out, nullptr, true, a.out, out_ld, 0, res, s,
-                      fold_out);
+    PIO_TRY(linear_fwd(kv_fold ? a.vo : a.o, a.dtype, w.o16, (int64_t)B * Tq, out, nullptr, true, a.out, out_ld, 0, res, s,
+                       fold_out));
+    if (fold_out && fold_out->out16)
+        PIO_RANGE(PIO_RK_STREAM, a.dtype, fold_out->out16, (int64_t)B * Tq, a.out, fold_out->ld16, 1, 0, s);
+    return PIO_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -440,10 +463,17 @@ static int mlp_core(const pio_mlp_t &m, Pair x, int64_t rows, Pair h, const Resi
     if (!out_ld) out_ld = m.out;
     if (m.fc1.k != padc(m.in) || m.fc1.n != padc(m.hidden) || m.fc2.k != m.fc1.n) return PIO_E_SHAPE;
     PIO_TRY(linear_fwd(m.fc1, m.dtype, x, rows, h.hi, h.lo, false, 0, m.fc1.n, 1, nullptr, s, fold_in));
-    if (out16)
-        return linear_fwd(m.fc2, m.dtype, h, rows, out16->hi, out16->lo, false, 0, padc(m.out), 0, res, s, nullptr,
-                          padc(m.out));
-    return linear_fwd(m.fc2, m.dtype, h, rows, out, nullptr, true, m.out, out_ld, 0, res, s, fold_out);
+    PIO_RANGE(PIO_RK_HIDDEN, m.dtype, h.hi, rows, m.hidden, m.fc1.n, 1, 0, s);
+    if (out16) {
+        PIO_TRY(linear_fwd(m.fc2, m.dtype, h, rows, out16->hi, out16->lo, false, 0, padc(m.out), 0, res, s, nullptr,
+                           padc(m.out)));
+        PIO_RANGE(PIO_RK_STREAM, m.dtype, out16->hi, rows, m.out, padc(m.out), 1, 0, s);
+        return PIO_OK;
+    }
+    PIO_TRY(linear_fwd(m.fc2, m.dtype, h, rows, out, nullptr, true, m.out, out_ld, 0, res, s, fold_out));
+    if (fold_out && fold_out->out16)
+        PIO_RANGE(PIO_RK_STREAM, m.dtype, fold_out->out16, rows, m.out, fold_out->ld16, 1, 0, s);
+    return PIO_OK;
 }
 
 // ======================================================================================================
@@ -639,6 +669,7 @@ static int self_attention_run(const pio_self_attention_t &sa, const pio_tensor3_
         if (!(carry && carry->x == x.data && carry->x16 == p.x16.hi && carry->part == p.part_a)) {
             if (carry && !carry->f32_valid) return PIO_E_ARG;  // (the stack decides the fold for all its blocks)
             PIO_TRY(rowstats_cast_launch(x.data, rows, x.C, slot_w, p.x16.hi, p.lo_a, p.part_a, sa.attn.dtype, s));
+            PIO_RANGE(PIO_RK_STREAM, sa.attn.dtype, p.x16.hi, rows, x.C, x.C, 1, 0, s);
         }
         const Pair xa = {p.x16.hi, nullptr};
         LnFold f_qkv, f_out, f_fc1, f_fc2;
@@ -723,16 +754,18 @@ static int cross_attention_run(const pio_cross_attention_t &ca, const pio_tensor
     if (ca.attn.out != q_c || ca.mlp.in != q_c || ca.mlp.out != q_c) return PIO_E_SHAPE;
     if (iq_tail && (ca.use_query_residual || qc || p.q_bcast)) return PIO_E_ARG;  // (the rows themselves are needed then)
     // layer_norm_kv, layer_norm_q  (transformer_primitives.py:379-380)
-    if (ikv_tail)
+    if (ikv_tail) {
         PIO_TRY(layernorm_cast_cat_launch(ikv, *ikv_tail, ca.ln_kv, p.kv16.hi, p.kv16.lo, padc(kv_c), ca.attn.dtype, s));
-    else
+        PIO_RANGE(PIO_RK_CAST, ca.attn.dtype, p.kv16.hi, (int64_t)B * Tk, kv_c, padc(kv_c), 1, 0, s);
+    } else
         PIO_TRY(cast_pair(ikv, &ca.ln_kv, p.kv16, padc(ikv.C), ca.attn.dtype, s));
     const pio_tensor3_t q1 = p.q_bcast ? first_batch(iq) : iq;
     const Pair qa = pair_if(p.q16, ca.attn.act_split);
     if (qc && ca.use_query_residual) return PIO_E_ARG;  // (the query rows themselves are needed then)
-    if (iq_tail)
+    if (iq_tail) {
         PIO_TRY(layernorm_cast_cat_launch(iq, *iq_tail, ca.ln_q, qa.hi, qa.lo, padc(q_c), ca.attn.dtype, s));
-    else if (!(qc && qc->valid)) PIO_TRY(cast_pair(q1, &ca.ln_q, qa, padc(q_c), ca.attn.dtype, s));
+        PIO_RANGE(PIO_RK_CAST, ca.attn.dtype, qa.hi, rows, q_c, padc(q_c), 1, 0, s);
+    } else if (!(qc && qc->valid)) PIO_TRY(cast_pair(q1, &ca.ln_q, qa, padc(q_c), ca.attn.dtype, s));
     const Residual rq = residual_of(iq);
     PIO_TRY(attention_core(ca.attn, qa, p.q_bcast, p.kv16, p.kv16, B, Tq, Tk, kv_mask, q_mask, full_mask,
                            attention_bias, ca.use_query_residual ? &rq : nullptr, p.x1, probs_out, p.core, s, nullptr,
@@ -744,6 +777,21 @@ static int cross_attention_run(const pio_cross_attention_t &ca, const pio_tensor
     const Residual r1 = residual_of(t1);
     return mlp_core(ca.mlp, qm, rows, p.h16, &r1, out, s, nullptr, nullptr, out_ld, out16);
 }
+
+// Range probe: the part label (pio_range_probe_mark) an entry point changes on its way, restored when it returns.
+struct RangePart {
+    bool changed = false;
+    int prev = 0;
+    void set(int part) {
+        if (!range_probe_active()) return;
+        const int was = range_probe_mark(part);
+        if (!changed) prev = was;
+        changed = true;
+    }
+    ~RangePart() {
+        if (changed) range_probe_mark(prev);
+    }
+};
 
 struct DecoderPlan {
     CrossPlan cp;
@@ -921,6 +969,7 @@ int pio_encoder_fwd_opts(const pio_cross_attention_t *cross, const pio_self_atte
     const int B = inputs->B, M = inputs->T, N = latents->T, D = latents->C;
     if (latents->B != B) return PIO_E_SHAPE;
     if (pio_encoder_workspace_bytes(cross, layers, L, B, M, N) > workspace_bytes) return PIO_E_WORKSPACE;
+    RangePart range_part;  // range probe: the cross-attend keeps the caller's part, the stack is marked here
     {
         CrossPlan cp;
         const bool qb = (latents->stride_b == 0 && B > 1);
@@ -930,6 +979,7 @@ int pio_encoder_fwd_opts(const pio_cross_attention_t *cross, const pio_self_atte
                                     cp, s, inputs_tail));
     }
     const pio_tensor3_t z = {out, (int64_t)N * D, D, B, N, D};
+    range_part.set(PIO_RP_STACK);
     FoldCarry carry;  // LayerNorm fold: the row statistics of z travel from one block's fc2 to the next block's q|k|v
     for (int blk = 0; blk < num_blocks; ++blk) {  // perceiver.py:104-106: weights shared across blocks
         for (int l = 0; l < L; ++l) {
@@ -997,7 +1047,7 @@ static int decoder_run(const pio_cross_attention_t *cross, const pio_linear_t *f
     // perceiver.py:178-179: final nn.Linear on every query row
     if (final_layer->k != padc(q_c)) return PIO_E_SHAPE;
     const pio_tensor3_t ty = {y, (int64_t)Q * y_ld, y_ld, B, Q, q_c};
-    if (!direct) PIO_TRY(cast_pair(ty, nullptr, p.y16, padc(q_c), cross->attn.dtype, s));
+    if (!direct) PIO_TRY(cast_pair(ty, nullptr, p.y16, padc(q_c), cross->attn.dtype, s, PIO_RK_STREAM));
     return linear_fwd(*final_layer, cross->attn.dtype, p.y16, (int64_t)B * Q, out, nullptr, true, final_out, final_out,
                       0, nullptr, s);
 }

@@ -123,6 +123,21 @@ int pio_qk_logit_absmax(int32_t dtype, int32_t dkp, int32_t dk, const void *Q, c
                             (hipStream_t)stream);
 }
 
+int pio_absmax16(int32_t dtype, const void *x, int64_t rows, int32_t cols, int64_t ld, int32_t batch, int64_t stride_b,
+                 float *absmax, void *stream) {
+    return absmax16_launch(dtype, x, rows, cols, ld, batch, stride_b, absmax, (hipStream_t)stream);
+}
+
+int pio_range_probe_begin(float *records, int32_t max_records) { return range_probe_begin(records, max_records); }
+
+int pio_range_probe_mark(int32_t part) {
+    if (part < PIO_RP_ATTENTION || part > PIO_RP_DECODER) return PIO_E_ARG;
+    range_probe_mark(part);
+    return PIO_OK;
+}
+
+int pio_range_probe_end(int32_t *parts, int32_t *kinds, int32_t cap) { return range_probe_end(parts, kinds, cap); }
+
 int pio_version(void) { return PIO_VERSION; }
 
 int pio_arch_ok(void) {

@@ -137,6 +137,18 @@ int logit_probe_record(int dtype, int dkp, int dk, const AttnOperands &t, int B,
                        const uint8_t *kv_mask, const uint8_t *q_mask, const uint8_t *full_mask, hipStream_t s);
 int logit_probe_begin(float *records, int max_records);
 int logit_probe_end();
+// Range probe (pio_rangeprobe.hip; tooling, off by default): max |x| of one 16-bit buffer, max-merged into *absmax.
+// range_probe_record: what the block entry points call behind every producer of a 16-bit activation buffer while the probe
+// is active (record n++ of pio_range_probe_begin's buffer, labelled with the current part and `kind`, a PIO_RK_*).
+// range_probe_mark sets the part (PIO_RP_*) of the records that follow and returns the previous one.
+int absmax16_launch(int dtype, const void *x, int64_t rows, int64_t cols, int64_t ld, int64_t batch, int64_t stride_b,
+                    float *absmax, hipStream_t s);
+bool range_probe_active();
+int range_probe_record(int kind, int dtype, const void *x, int64_t rows, int64_t cols, int64_t ld, int64_t batch,
+                       int64_t stride_b, hipStream_t s);
+int range_probe_begin(float *records, int max_records);
+int range_probe_mark(int part);
+int range_probe_end(int32_t *parts, int32_t *kinds, int cap);
 // eval BatchNorm -> ReLU -> 3x3/2 SAME max-pool -> channels-last tokens (tail of Conv2DDownsample)
 int bn_relu_pool_nhwc_launch(const float *x, const float *scale, const float *shift, float *y, int B, int C, int H, int W,
                              int pad_top, int pad_left, hipStream_t s);

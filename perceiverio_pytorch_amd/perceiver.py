@@ -121,10 +121,14 @@ class PerceiverEncoder(nn.Module):
             # (the un-folded repeat of the range guard is a PER-CALL option: no process state changes around the call)
             opts = L.CallOpts(1 if self._range_fallback else 0, 0)
             LP.expect("cross", *["stack"] * (Lyr * self._num_blocks))    # (one attention call per block, this order)
-            with R.on_device(dev):
-                L.check(lib.pio_encoder_fwd_opts(cross, layers, Lyr, self._num_blocks, int(per_block), R.tensor3(x),
-                                                 tail3, R.tensor3(z0), im_ptr, out.data_ptr(), ws.data_ptr(),
-                                                 ws.numel(), R.stream_ptr(dev), opts), "pio_encoder_fwd")
+            LP.mark_range("cross")           # (range probe: the library marks "stack" behind the cross-attend itself)
+            try:
+                with R.on_device(dev):
+                    L.check(lib.pio_encoder_fwd_opts(cross, layers, Lyr, self._num_blocks, int(per_block), R.tensor3(x),
+                                                     tail3, R.tensor3(z0), im_ptr, out.data_ptr(), ws.data_ptr(),
+                                                     ws.numel(), R.stream_ptr(dev), opts), "pio_encoder_fwd")
+            finally:
+                LP.mark_range("attention")
             return self._finish(out, flag, inputs, inputs_tail, latents, input_mask)
         # Samples are independent: run `nsplit` batch slices as independent kernel chains on side streams so that
         # one chain's fill / drain / HBM-bound kernels overlap the other's MFMA-bound ones (each slice still fills
@@ -140,13 +144,17 @@ class PerceiverEncoder(nn.Module):
             side.wait_stream(cur)
         for i, side in enumerate(sides):
             LP.expect("cross", *["stack"] * (Lyr * self._num_blocks))
-            with R.on_device(dev), torch.cuda.stream(side):
-                xs, zs = x[i * bs:(i + 1) * bs], z0[i * bs:(i + 1) * bs]
-                ws = R.workspace(dev, lib.pio_encoder_workspace_bytes(cross, layers, Lyr, bs, M, N))
-                mp = im_ptr + i * bs * M if im_ptr is not None else None
-                L.check(lib.pio_encoder_fwd_opts(cross, layers, Lyr, self._num_blocks, 0, R.tensor3(xs), None,
-                                                 R.tensor3(zs), mp, out[i * bs:(i + 1) * bs].data_ptr(), ws.data_ptr(),
-                                                 ws.numel(), side.cuda_stream, opts), "pio_encoder_fwd")
+            LP.mark_range("cross")
+            try:
+                with R.on_device(dev), torch.cuda.stream(side):
+                    xs, zs = x[i * bs:(i + 1) * bs], z0[i * bs:(i + 1) * bs]
+                    ws = R.workspace(dev, lib.pio_encoder_workspace_bytes(cross, layers, Lyr, bs, M, N))
+                    mp = im_ptr + i * bs * M if im_ptr is not None else None
+                    L.check(lib.pio_encoder_fwd_opts(cross, layers, Lyr, self._num_blocks, 0, R.tensor3(xs), None,
+                                                     R.tensor3(zs), mp, out[i * bs:(i + 1) * bs].data_ptr(),
+                                                     ws.data_ptr(), ws.numel(), side.cuda_stream, opts), "pio_encoder_fwd")
+            finally:
+                LP.mark_range("attention")
         for side in sides:                   # ... and `cur` continues behind ALL of them (a wait queued between
             cur.wait_stream(side)            # two slices would chain them one after the other)
         for t in (x, z0, out):
@@ -293,15 +301,19 @@ class PerceiverDecoder(nn.Module):
                 qlo = q_cache["lo"].data_ptr() if q_cache["lo"] is not None else None
                 valid = 1 if q_cache["valid"] else 0
         LP.expect("decoder")
-        with R.on_device(dev):
-            if query_tail is not None:
-                L.check(lib.pio_decoder_fwd_split(cross, fin_ptr, out_ch, R.tensor3(q), R.tensor3(query_tail), R.tensor3(z),
-                                                  qm_ptr, out.data_ptr(), ws.data_ptr(), ws.numel(), R.stream_ptr(dev)),
-                        "pio_decoder_fwd_split")
-            else:
-                L.check(lib.pio_decoder_fwd_qcache(cross, fin_ptr, out_ch, R.tensor3(q), R.tensor3(z), qm_ptr,
-                                                   out.data_ptr(), ws.data_ptr(), ws.numel(), R.stream_ptr(dev), qhi, qlo,
-                                                   valid), "pio_decoder_fwd")
+        LP.mark_range("decoder")
+        try:
+            with R.on_device(dev):
+                if query_tail is not None:
+                    L.check(lib.pio_decoder_fwd_split(cross, fin_ptr, out_ch, R.tensor3(q), R.tensor3(query_tail),
+                                                      R.tensor3(z), qm_ptr, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      R.stream_ptr(dev)), "pio_decoder_fwd_split")
+                else:
+                    L.check(lib.pio_decoder_fwd_qcache(cross, fin_ptr, out_ch, R.tensor3(q), R.tensor3(z), qm_ptr,
+                                                       out.data_ptr(), ws.data_ptr(), ws.numel(), R.stream_ptr(dev), qhi,
+                                                       qlo, valid), "pio_decoder_fwd")
+        finally:
+            LP.mark_range("attention")
         if qhi is not None:
             q_cache["valid"] = True
         return R.forward_only(out, query, latents, *self.parameters())

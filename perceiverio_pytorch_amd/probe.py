@@ -6,13 +6,23 @@ LIMIT).  `logit_probe()` measures max |q . k| / sqrt(dk) of every attention call
 kernel (csrc/pio_qkprobe.hip) behind the process-wide switch pio_logit_probe_begin / _end, or plain torch under the CPU
 plumbing backend -- and `recommend_precision_policy()` turns the figures into a "cross/stack/decoder" policy string.
 
-Tooling, not product path: one probe at a time, one device, not thread-safe, not capturable.  With the probe off nothing
-is measured and nothing extra is launched.
+Range probe: do a model's 16-bit operands fit fp16, and if not, which part has to run in bf16?
+
+Every matrix operand inside the library is 16-bit; with fp16 anything beyond 65 504 becomes inf and the forward returns
+NaN.  `range_probe()` measures max |x| of every 16-bit activation buffer a forward produces -- LayerNorm / cast outputs,
+q / k / v projections, attention-core outputs, GELU'd hidden activations, the LayerNorm fold's 16-bit residual stream and
+the decoders' y16 -- with a separate calibration kernel (csrc/pio_rangeprobe.hip) behind the process-wide switch
+pio_range_probe_begin / _end, or plain torch on the same tensors under the CPU plumbing backend (fp32 there: the true
+magnitude), and `recommend_operand_dtype()` turns the figures into a "cross/stack/decoder" policy string.
+
+Tooling, not product path: one probe of each kind at a time (a logit_probe and a range_probe may be active together), one
+device, not thread-safe, not capturable.  With a probe off nothing is measured and nothing extra is launched.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
-from typing import List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -158,3 +168,135 @@ def recommend_precision_policy(model, *inputs, threshold: Optional[float] = None
             changed = True
     policy = "/".join(parts[n] for n in ("cross", "stack", "decoder")) if changed else current
     return policy, {"absmax": figures, "threshold": float(threshold), "calls": probe.calls, "policy": current}
+
+
+# ======================================================================================================================
+# range probe
+# ======================================================================================================================
+# part / kind names, indexed by the library's PIO_RP_* / PIO_RK_* values (include/pio_hip.h)
+RANGE_PARTS = ("attention", "cross", "stack", "decoder")
+RANGE_KINDS = ("cast", "q", "k", "v", "attn", "hidden", "stream")
+FP16_MAX = 65504.0
+
+_range_active: Optional["range_probe"] = None
+
+
+def range_active() -> bool:
+    return _range_active is not None
+
+
+def mark_range(name: str) -> None:
+    """HIP backend: the part of the records the library call that follows will make (pio_range_probe_mark); "attention"
+    resets it.  A no-op without an active range_probe on the HIP backend."""
+    if _range_active is not None and _range_active._buf is not None:
+        L.check(L.lib().pio_range_probe_mark(RANGE_PARTS.index(name)), "pio_range_probe_mark")
+
+
+def record_range_cpu(kind: str, x: torch.Tensor) -> None:
+    """CPU plumbing backend: max |x| of the fp32 tensor whose 16-bit image the HIP backend measures as `kind`, under the
+    part the enclosing encoder / decoder names (a non-finite element reports inf, an empty tensor 0)."""
+    if _range_active is None:
+        return
+    assert kind in RANGE_KINDS
+    v = float(x.detach().abs().max()) if x.numel() else 0.0
+    if not math.isfinite(v):
+        v = float("inf")
+    _range_active.records.append((_part[-1] if _part else "attention", kind, v))
+
+
+class range_probe:
+    """Context manager: after exit, `.records` is the list of (part, kind, absmax) of every 16-bit activation buffer
+    produced inside it, in call order, and `.calls` their count.  part: "cross" / "stack" / "decoder" (PerceiverEncoder /
+    PerceiverDecoder forwards) or "attention" (the raw Attention / MLP / SelfAttention / CrossAttention modules); kind:
+    one of RANGE_KINDS.  `.by_part()` gives {part: {kind: max}}, `.worst()` {part: max}.
+
+    On the HIP backend the figures live in a device buffer of `max_records` floats on the current device (buffers past it
+    are counted in `.calls` but not recorded); exit synchronises that device.  Entering during stream capture raises.
+    Only one range_probe may be active at a time; a logit_probe may be active beside it."""
+
+    def __init__(self, max_records: int = 16384):
+        if max_records <= 0:
+            raise ValueError("max_records must be positive")
+        self.max_records = int(max_records)
+        self.records: List[Tuple[str, str, float]] = []
+        self.calls = 0
+        self._buf = None
+
+    def __enter__(self):
+        global _range_active
+        if _range_active is not None:
+            raise L.PioError("range_probe: a probe is already active (one at a time: the switch is process-wide)")
+        self.records, self.calls = [], 0
+        if R.get_backend() == "hip":
+            if not torch.cuda.is_available():
+                raise L.PioError("range_probe: the HIP backend needs an MI355X device (CPU: set_backend('torch'))")
+            dev = torch.device("cuda", torch.cuda.current_device())
+            if R.capturing(dev):
+                raise L.PioError("range_probe: cannot start during stream capture (the probe is host-side state, and its "
+                                 "records are read back on exit)")
+            with torch.inference_mode(False):
+                self._buf = torch.zeros(self.max_records, dtype=torch.float32, device=dev)
+            torch.cuda.synchronize(dev)      # (the zeros are in place whatever stream a call inside uses)
+            L.check(L.lib().pio_range_probe_begin(self._buf.data_ptr(), self.max_records), "pio_range_probe_begin")
+        _range_active = self
+        return self
+
+    def __exit__(self, *exc):
+        global _range_active
+        _range_active = None
+        if self._buf is not None:
+            parts = (C.c_int32 * self.max_records)()
+            kinds = (C.c_int32 * self.max_records)()
+            n = int(L.lib().pio_range_probe_end(parts, kinds, self.max_records))
+            buf, self._buf = self._buf, None
+            torch.cuda.synchronize(buf.device)
+            self.calls = n
+            # (the labels are the library's own: what was recorded before an exception stays readable)
+            vals = buf[:min(n, self.max_records)].cpu().tolist()
+            self.records = [(RANGE_PARTS[parts[i]], RANGE_KINDS[kinds[i]], v) for i, v in enumerate(vals)]
+        else:
+            self.calls = len(self.records)
+        return False
+
+    def by_part(self) -> Dict[str, Dict[str, float]]:
+        out: Dict[str, Dict[str, float]] = {}
+        for name, kind, v in self.records:
+            d = out.setdefault(name, {})
+            d[kind] = max(d.get(kind, 0.0), v)
+        return out
+
+    def worst(self) -> Dict[str, float]:
+        return {name: max(d.values()) for name, d in self.by_part().items()}
+
+
+def recommend_operand_dtype(model, *inputs, limit: float = FP16_MAX, **kw):
+    """Run ONE forward of `model(*inputs, **kw)` under the range probe and return (policy string, report).
+
+    The string starts from the model's current policy (`model.precision_policy`, else the ambient one) split into its
+    three parts cross / stack / decoder (models.split_policy3); every part whose largest 16-bit operand is inf or exceeds
+    `limit` becomes "bf16x3" -- the only bf16 policy that meets 1e-3 (runtime.py) -- the others are left alone, and when
+    none does the model's own string comes back unchanged.  Nothing is set: assign `model.precision_policy` yourself.
+    `limit` defaults to the fp16 maximum, 65 504 (not a tuned number): pass a lower one for headroom.
+    report = {"absmax": {part: {kind: figure}}, "limit": l, "calls": n, "policy": the model's current string}.
+
+    A forward that ends in the library's own PIO_E_RANGE error (the guard of the LayerNorm-folded stack) still yields its
+    figures: that is the case the recommendation exists for."""
+    from .models import split_policy3
+    current = getattr(model, "precision_policy", None) or R.get_precision_policy()
+    cross, stack, dec = split_policy3(current)
+    parts = {"cross": cross if cross is not None else stack, "stack": stack, "decoder": dec}
+    probe = range_probe()
+    try:
+        with torch.no_grad(), probe:
+            model(*inputs, **kw)
+    except L.PioError as e:
+        if "PIO_E_RANGE" not in str(e):
+            raise
+    worst = probe.worst()
+    changed = False
+    for name in ("cross", "stack", "decoder"):
+        if worst.get(name, 0.0) > limit and parts[name] != "bf16x3":      # (inf > limit as well)
+            parts[name] = "bf16x3"
+            changed = True
+    policy = "/".join(parts[n] for n in ("cross", "stack", "decoder")) if changed else current
+    return policy, {"absmax": probe.by_part(), "limit": float(limit), "calls": probe.calls, "policy": current}
