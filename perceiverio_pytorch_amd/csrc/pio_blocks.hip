@@ -28,27 +28,11 @@ namespace pio {
             PIO_TRY(range_probe_record(kind, dtype, ptr, rows, cols, ld, batch, stride_b, stream)); \
     } while (0)
 
-struct Pair {  // a 16-bit operand and its optional rounding residual
-    void *hi = nullptr, *lo = nullptr;
-};
-
-static Pair take_pair(Carver &c, size_t elems, bool split) {
-    Pair p;
-    p.hi = c.take(elems * 2);
-    p.lo = split ? c.take(elems * 2) : nullptr;
-    return p;
-}
-
 struct Residual {
     const float *ptr = nullptr;
     int64_t ld = 0, stride_b = 0;
     int rows_per_batch = 0;
 };
-
-// Row pitch (floats) of an INTERNAL fp32 activation buffer: whole float4 groups, so that a channel count like 1026 or
-// 322 does not force the GEMM epilogues and LayerNorm reads onto 4-byte accesses.  The columns [C, pitch4(C)) hold
-// zeros or stale values and are never read as data.
-static inline int pitch4(int c) { return (c + 3) & ~3; }
 
 static Residual residual_of(const pio_tensor3_t &t) {
     Residual r;
@@ -153,63 +137,6 @@ static int cast_pair(const pio_tensor3_t &x, const pio_layernorm_t *ln, Pair y, 
 // ------------------------------------------------------------------------------------------------------
 // attention core on already normalised / cast 16-bit inputs
 // ------------------------------------------------------------------------------------------------------
-// Upper bound of the materialised score matrix held at once (fp32 scores + 16-bit probabilities are carved for this many
-// (batch, row) slabs): attention over more than this is run sample by sample and, inside a sample, in chunks of query
-// rows.  Only the 3-sweep policies ("x3": split activations) still materialise scores for the wide cross-attends; the
-// optical-flow ones (2048 x 182 528 scores: 1.5 GB fp32 + as much again for the probability pair) then run in two
-// passes of <= 1 GiB.  (A 256 MiB cap was measured too: 8 passes, each P V product with only 6 output tiles of a
-// 182 528-deep K loop -- 96 ms instead of 29 per forward.)
-static const int64_t kScoreCapBytes = 1ll << 30;
-
-struct ScoreChunks {
-    int b_chunk;  // samples per pass (>= 1)
-    int q_chunk;  // query rows per pass (== Tq unless b_chunk == 1 and one sample exceeds the cap)
-};
-static ScoreChunks score_chunks(int B, int H, int Tq, int Tk) {
-    const int64_t per_sample = (int64_t)H * Tq * (int64_t)Tk * 4;
-    ScoreChunks c{B, Tq};
-    if ((int64_t)B * per_sample <= kScoreCapBytes) return c;
-    int64_t bc = kScoreCapBytes / (per_sample > 0 ? per_sample : 1);
-    if (bc >= 1) {
-        c.b_chunk = (int)bc;
-        return c;
-    }
-    c.b_chunk = 1;
-    int64_t qc = kScoreCapBytes / ((int64_t)H * Tk * 4);
-    qc = qc / 128 * 128;
-    c.q_chunk = (int)(qc < 128 ? 128 : qc);
-    if (c.q_chunk > Tq) c.q_chunk = Tq;
-    return c;
-}
-
-struct AttnScratch {
-    Pair q16, k16, vt16, p16, o16;
-    float *scores;
-    void *xpart;  // key bits / fp32 split partials of the fused cross-attention cores
-    // lean: the caller never passes a full mask / bias / probability output: no score buffers where attn_plan has a fused core
-    void carve(Carver &c, const pio_attention_t &a, int Bq, int B, int Tq, int Tk, bool lean = false) {
-        const int64_t ldq = (int64_t)a.heads * a.dkp, ldo = (int64_t)a.heads * a.dvp, tkp = pad8(Tk);
-        const int64_t tkv = round_up(Tk, 32);  // V^T row pitch: whole 32-key tiles, zero padded (pio_xattn.hip)
-        const bool sp = a.act_split != 0;
-        const AttnRoute plan = attn_plan(a, B, Bq, Tq, Tk, lean);
-        q16 = take_pair(c, (size_t)Bq * Tq * ldq, sp);
-        // (the fused cross-attention kernel reads whole 32-key tiles: up to 31 rows behind key Tk - 1 of the last
-        //  sample.  They only have to be readable -- their scores are masked by assignment -- and they are: vt16 and
-        //  o16 follow in the same workspace.  No padding here: the fused q|k|v form needs q16 | k16 | vt16 adjacent.)
-        k16 = take_pair(c, (size_t)B * Tk * ldq, sp);
-        vt16 = take_pair(c, (size_t)B * ldo * tkv, sp);
-        scores = nullptr;
-        p16 = Pair();
-        if (plan.need_scores) {
-            const ScoreChunks ch = score_chunks(B, a.heads, Tq, Tk);
-            scores = (float *)c.take((size_t)ch.b_chunk * a.heads * ch.q_chunk * (int64_t)Tk * 4);
-            p16 = take_pair(c, (size_t)ch.b_chunk * a.heads * ch.q_chunk * tkp, sp);
-        }
-        o16 = take_pair(c, (size_t)B * Tq * ldo, sp);
-        xpart = plan.xpart_bytes ? c.take(plan.xpart_bytes) : nullptr;
-    }
-};
-
 static int check_attention(const pio_attention_t &a) {
     if (a.heads <= 0 || a.dk <= 0 || a.dv <= 0) return PIO_E_SHAPE;
     if (a.dkp != pad8(a.dk) || a.dvp != pad8(a.dv)) return PIO_E_SHAPE;
@@ -476,24 +403,6 @@ static int mlp_core(const pio_mlp_t &m, Pair x, int64_t rows, Pair h, const Resi
     return PIO_OK;
 }
 
-// ======================================================================================================
-// plans (workspace layouts)
-// ======================================================================================================
-struct AttentionPlan {
-    Pair xq16, xk16, xv16;
-    AttnScratch core;
-    size_t carve(void *base, const pio_attention_t &a, int B, int Tq, int Tk, bool qb, bool same) {
-        Carver c(base);
-        const bool sp = a.act_split != 0;
-        const int Bq = qb ? 1 : B;
-        xq16 = take_pair(c, (size_t)Bq * Tq * padc(a.q_in), sp);
-        xk16 = take_pair(c, (size_t)B * Tk * padc(a.k_in), sp);
-        xv16 = same ? xk16 : take_pair(c, (size_t)B * Tk * padc(a.v_in), sp);
-        core.carve(c, a, Bq, B, Tq, Tk);
-        return c.off;
-    }
-};
-
 static bool same_tensor(const pio_tensor3_t &a, const pio_tensor3_t &b) {
     return a.data == b.data && a.stride_b == b.stride_b && a.stride_t == b.stride_t && a.B == b.B && a.T == b.T &&
            a.C == b.C;
@@ -516,44 +425,6 @@ static bool fold_inplace() {
     const char *e = getenv("PIO_FOLD_INPLACE");
     return !e || atoi(e) != 0;
 }
-
-struct SelfPlan {
-    Pair x16, h16;
-    float *x1;
-    AttnScratch core;
-    // LayerNorm fold (pio_ln_fold_t): 16-bit copy of x1 and the per-row partial sums of x (A) and x1 (B); the 16-bit
-    // copy of x lives in x16
-    void *x16b = nullptr, *lo_a = nullptr, *lo_b = nullptr;  // lo_*: x - x16 / x1 - x16b (the stream as a 16-bit pair)
-    float *part_a = nullptr, *part_b = nullptr;
-    // lean: the caller never passes a full mask / bias / probability output (the encoder stack): no score buffers
-    // when a fused kernel covers the block
-    size_t carve(void *base, const pio_self_attention_t &sa, int B, int N, bool lean = false) {
-        Carver c(base);
-        const int64_t rows = (int64_t)B * N;
-        const int cmax = padc(sa.attn.q_in) > padc(sa.mlp.in) ? padc(sa.attn.q_in) : padc(sa.mlp.in);
-        x16 = take_pair(c, (size_t)rows * cmax, sa.attn.act_split || sa.mlp.act_split);
-        h16 = take_pair(c, (size_t)rows * padc(sa.mlp.hidden), sa.mlp.act_split != 0);
-        x1 = (float *)c.take((size_t)rows * sa.attn.out * 4);
-        core.carve(c, sa.attn, B, B, N, N, lean);
-        if (sa.fold.qkv.w_hi && sa.fold.fc1.w_hi) {
-            // The residual GEMMs (out, fc2) read the residual pair and write the result pair element for element from
-            // the same lane (load, add, store), and their A operand is another array (attention output / hidden
-            // activations): the stream is updated IN PLACE -- one 16-bit pair instead of two ping-pong pairs, and the
-            // hidden activations take the attention output's buffer (dead once the out projection has run).  Per layer
-            // at B = 32 the arrays in flight shrink from 288 MB (beyond the 256 MB Infinity Cache) to 192 MB.
-            const bool inplace = fold_inplace();
-            x16b = inplace ? x16.hi : c.take((size_t)rows * cmax * 2);
-            lo_a = c.take((size_t)rows * cmax * 2);
-            lo_b = inplace ? lo_a : c.take((size_t)rows * cmax * 2);
-            part_a = (float *)c.take((size_t)rows * (cmax / 64 + 1) * 2 * 4);  // (up to one slot per 64 columns)
-            part_b = (float *)c.take((size_t)rows * (cmax / 64 + 1) * 2 * 4);
-            if (inplace && !sa.mlp.act_split && !sa.attn.act_split &&
-                (size_t)rows * padc(sa.mlp.hidden) <= (size_t)rows * sa.attn.heads * sa.attn.dvp)
-                h16.hi = core.o16.hi;
-        }
-        return c.off;
-    }
-};
 
 // LayerNorm fold switch (pio_ln_fold_enable; initial value from env PIO_LN_FOLD, default 1).
 // 0: never, 1: where it pays, 2: wherever a block offers it.  "Where it pays": the fold's GEMMs are the 256 x 256-tile
@@ -619,6 +490,11 @@ static int64_t ln_fold_small_max_rows() {
     }();
     return max_rows;
 }
+// Every switch of the fold as the plain values pio_block_route.h takes; filled once per C-ABI call (inside its CallOpts).
+static FoldKnobs fold_knobs() {
+    return FoldKnobs{ln_fold_choice(), ln_fold_min_rows(), ln_fold_small_min_rows(), ln_fold_small_max_rows(),
+                     fold_inplace()};
+}
 
 // Carried from one SelfAttention block to the next inside a stack: the 16-bit copy and the partial sums of the block's
 // INPUT, left in the plan's (x16, part_a) buffers by the previous block's fc2 GEMM.
@@ -631,44 +507,27 @@ struct FoldCarry {
 
 static int self_attention_run(const pio_self_attention_t &sa, const pio_tensor3_t &x, const uint8_t *kv_mask,
                               const uint8_t *q_mask, const uint8_t *full_mask, const float *attention_bias,
-                              float *out, float *probs_out, SelfPlan &p, hipStream_t s, FoldCarry *carry = nullptr,
-                              bool need_f32_out = true) {
+                              float *out, float *probs_out, SelfPlan &p, const FoldKnobs &knobs, hipStream_t s,
+                              FoldCarry *carry = nullptr, bool need_f32_out = true) {
     const int B = x.B, N = x.T;
     const int64_t rows = (int64_t)B * N;
     if (x.C != sa.attn.q_in || sa.attn.k_in != x.C || sa.attn.v_in != x.C || sa.attn.out != x.C ||
         sa.mlp.in != x.C || sa.mlp.out != x.C)
         return PIO_E_SHAPE;  // residual adds need matching widths (the reference raises a RuntimeError)
-    // LayerNorm fold: contiguous rows of 512 / 768 / 1024 / 1280 / 1536 channels, single-sweep activations, the fused
-    // q|k|v form (head widths the fused attention kernel covers), nothing that needs the score matrix.  Two kernel
-    // families: the 256 x 256-tile kernel with 128-column statistics slots for stacks with enough rows to fill the chip
-    // (weights may then be (hi, lo) pairs -- policies "x2s" / "x2w": second K sweep against the lo image; of the stacked
-    // q|k|v image only the V rows may have one), the tile kernels with 64-column slots below that (single weights).
-    const bool fold_ok = ln_fold_choice() != 0 && p.x16b && x.C >= 512 && x.C <= 1536 && (x.C % 256) == 0 &&
-                         x.stride_t == x.C && (B == 1 || x.stride_b == (int64_t)N * x.C) && !sa.attn.act_split &&
-                         !sa.mlp.act_split && sa.attn.qkv.w_hi &&
-                         (!sa.fold.qkv.w_lo || sa.fold.qkv.lo_row0 == 2 * sa.attn.heads * sa.attn.dkp) &&
-                         (!sa.fold.fc1.w_lo || sa.fold.fc1.lo_row0 == 0) && flash_supported(sa.attn.dkp, sa.attn.dvp) &&
-                         sa.fold.qkv.n == sa.attn.qkv.n && sa.fold.qkv.k == x.C && sa.fold.fc1.k == x.C &&
-                         sa.fold.fc1.n == sa.mlp.fc1.n && sa.mlp.hidden == x.C && sa.mlp.dtype == sa.attn.dtype &&
-                         !kv_mask && !q_mask && !full_mask && !attention_bias && !probs_out &&
-                         (((uintptr_t)x.data) & 15) == 0;
-    const bool fold_wide = fold_ok && rows >= ln_fold_min_rows();
-    // (tile-kernel family: up to 4095 rows in the automatic mode -- ImageNet B = 8, 4096 rows, measures 8.33 ms folded on
-    //  the tile kernels against 7.86 un-folded, whose q|k|v GEMM runs on the 256 x 256-tile kernel; B = 1 / 2 / 4:
-    //  3.78 / 4.28 / 5.05 against 3.97 / 4.39 / 5.27 ms -- tools/r4_probe4.sh)
-    const bool fold_small = fold_ok && !fold_wide && rows >= ln_fold_small_min_rows() &&
-                            (ln_fold_choice() == 2 || rows < ln_fold_small_max_rows()) && !sa.fold.qkv.w_lo &&
-                            !sa.fold.fc1.w_lo && !sa.attn.o.w_lo && !sa.mlp.fc2.w_lo;
-    const bool fold = fold_wide || fold_small;
-    if (fold) {
-        const int slot_w = fold_wide ? 128 : 64, nslots = x.C / slot_w;
+    SelfCall call = {};
+    call.B = B; call.N = N; call.C = x.C; call.stride_t = x.stride_t; call.stride_b = x.stride_b;
+    call.x_aligned16 = (((uintptr_t)x.data) & 15) == 0; call.has_fold_buffers = p.x16b != nullptr;
+    call.kv_mask = kv_mask; call.q_mask = q_mask; call.full_mask = full_mask; call.bias = attention_bias;
+    call.probs = probs_out;
+    const SelfFold fold = self_fold_route(sa, call, knobs);
+    if (fold.family != SelfFold::NONE) {
         // x16 / part_a: the block input (from the previous block's fc2, or computed here for the first block)
         // Inside the fold the residual stream is the 16-bit pair (x16, lo): 22 mantissa bits, and 64 MB less traffic
         // per residual GEMM than fp32 + copy.  The fp32 form is read here once (first block) and written when the
         // caller needs it (last block).
         if (!(carry && carry->x == x.data && carry->x16 == p.x16.hi && carry->part == p.part_a)) {
             if (carry && !carry->f32_valid) return PIO_E_ARG;  // (the stack decides the fold for all its blocks)
-            PIO_TRY(rowstats_cast_launch(x.data, rows, x.C, slot_w, p.x16.hi, p.lo_a, p.part_a, sa.attn.dtype, s));
+            PIO_TRY(rowstats_cast_launch(x.data, rows, x.C, fold.slot_w, p.x16.hi, p.lo_a, p.part_a, sa.attn.dtype, s));
             PIO_RANGE(PIO_RK_STREAM, sa.attn.dtype, p.x16.hi, rows, x.C, x.C, 1, 0, s);
         }
         const Pair xa = {p.x16.hi, nullptr};
@@ -677,8 +536,8 @@ static int self_attention_run(const pio_self_attention_t &sa, const pio_tensor3_
         f_out.out16 = p.x16b; f_out.ld16 = x.C; f_out.out_part = p.part_b;
         f_out.out16_lo = p.lo_b; f_out.res16_hi = p.x16.hi; f_out.res16_lo = p.lo_a;
         f_out.range_flag = f_fc2.range_flag = sa.fold.range_flag;
-        f_qkv.in_slots = f_fc1.in_slots = nslots;
-        f_out.slot_w = f_fc2.slot_w = slot_w;
+        f_qkv.in_slots = f_fc1.in_slots = fold.nslots;
+        f_out.slot_w = f_fc2.slot_w = fold.slot_w;
         f_fc1.in_part = p.part_b; f_fc1.w = &sa.fold.fc1; f_fc1.c = sa.fold.fc1_c; f_fc1.eps = sa.ln2.eps;
         f_fc2.out16 = p.x16.hi; f_fc2.ld16 = x.C; f_fc2.out_part = p.part_a;
         f_fc2.out16_lo = p.lo_a; f_fc2.res16_hi = p.x16b; f_fc2.res16_lo = p.lo_b;
@@ -714,27 +573,6 @@ static int self_attention_run(const pio_self_attention_t &sa, const pio_tensor3_
     const Residual r1 = residual_of(t1);
     return mlp_core(sa.mlp, xm, rows, p.h16, &r1, out, s);
 }
-
-struct CrossPlan {
-    Pair q16, kv16, h16;
-    float *x1;
-    AttnScratch core;
-    bool q_bcast;
-    size_t carve(void *base, const pio_cross_attention_t &ca, int B, int Tq, int Tk, bool qb, bool lean = false) {
-        Carver c(base);
-        q_bcast = qb;
-        const int Bq = qb ? 1 : B;
-        const int64_t rows = (int64_t)B * Tq;
-        const bool sp = ca.attn.act_split || ca.mlp.act_split;
-        // q16 is reused for LN2(x1): size it for all B*Tq rows
-        q16 = take_pair(c, (size_t)rows * padc(ca.attn.q_in), sp);
-        kv16 = take_pair(c, (size_t)B * Tk * padc(ca.attn.k_in), ca.attn.act_split != 0);
-        h16 = take_pair(c, (size_t)rows * padc(ca.mlp.hidden), ca.mlp.act_split != 0);
-        x1 = (float *)c.take((size_t)rows * pitch4(ca.attn.out) * 4);
-        core.carve(c, ca.attn, Bq, B, Tq, Tk, lean);
-        return c.off;
-    }
-};
 
 // ikv_tail (optional): the key / value input arrives as TWO arrays whose channels are concatenated, [ikv | ikv_tail]
 // (ikv_tail->B == 1: one batch-invariant table, e.g. Fourier position features); layer_norm_kv runs over the virtual
@@ -793,25 +631,6 @@ struct RangePart {
     }
 };
 
-struct DecoderPlan {
-    CrossPlan cp;
-    float *y;
-    Pair y16;
-    size_t carve(void *base, const pio_cross_attention_t &cross, const pio_linear_t *fin, int B, int Q, int N,
-                 bool qb) {
-        Carver c(base);
-        const int64_t rows = (int64_t)B * Q;
-        y = nullptr;
-        y16 = Pair();
-        if (fin) {
-            y = (float *)c.take((size_t)rows * pitch4(cross.attn.q_in) * 4);
-            y16 = take_pair(c, (size_t)rows * padc(cross.attn.q_in), cross.mlp.act_split != 0);
-        }
-        const size_t inner = cp.carve(base ? (char *)base + c.off : nullptr, cross, B, Q, N, qb, true);
-        return c.off + inner;
-    }
-};
-
 }  // namespace pio
 
 using namespace pio;
@@ -850,10 +669,8 @@ int pio_attention_fwd(const pio_attention_t *a, const pio_tensor3_t *iq, const p
 // ======================================================================================================
 size_t pio_mlp_workspace_bytes(const pio_mlp_t *m, int64_t rows) {
     if (!m) return 0;
-    Carver c(nullptr);
-    take_pair(c, (size_t)rows * padc(m->in), m->act_split != 0);
-    take_pair(c, (size_t)rows * padc(m->hidden), m->act_split != 0);
-    return c.off;
+    MlpPlan p;
+    return p.carve(nullptr, *m, rows);
 }
 
 int pio_mlp_fwd(const pio_mlp_t *m, const pio_tensor3_t *x, float *out, void *workspace, size_t workspace_bytes,
@@ -861,13 +678,11 @@ int pio_mlp_fwd(const pio_mlp_t *m, const pio_tensor3_t *x, float *out, void *wo
     if (!m || !x || !out || !workspace) return PIO_E_ARG;
     if (x->C != m->in) return PIO_E_SHAPE;
     const int64_t rows = (int64_t)x->B * x->T;
-    if (pio_mlp_workspace_bytes(m, rows) > workspace_bytes) return PIO_E_WORKSPACE;
+    MlpPlan p;
+    if (p.carve(workspace, *m, rows) > workspace_bytes) return PIO_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    Carver c(workspace);
-    const Pair x16 = take_pair(c, (size_t)rows * padc(m->in), m->act_split != 0);
-    const Pair h16 = take_pair(c, (size_t)rows * padc(m->hidden), m->act_split != 0);
-    PIO_TRY(cast_pair(*x, nullptr, x16, padc(m->in), m->dtype, s));
-    return mlp_core(*m, x16, rows, h16, nullptr, out, s);
+    PIO_TRY(cast_pair(*x, nullptr, p.x16, padc(m->in), m->dtype, s));
+    return mlp_core(*m, p.x16, rows, p.h16, nullptr, out, s);
 }
 
 // ======================================================================================================
@@ -878,7 +693,7 @@ int pio_ln_fold_enable(int on) { return ln_fold_enable(on); }
 size_t pio_self_attention_workspace_bytes(const pio_self_attention_t *sa, int32_t B, int32_t N) {
     if (!sa) return 0;
     SelfPlan p;
-    return p.carve(nullptr, *sa, B, N);
+    return p.carve(nullptr, *sa, B, N, fold_inplace());
 }
 
 int pio_self_attention_fwd(const pio_self_attention_t *sa, const pio_tensor3_t *x, const uint8_t *kv_mask,
@@ -894,9 +709,10 @@ int pio_self_attention_fwd_opts(const pio_self_attention_t *sa, const pio_tensor
                                 const pio_call_opts_t *opts) {
     if (!sa || !x || !out || !workspace) return PIO_E_ARG;
     CallOpts scope(opts);
+    const FoldKnobs knobs = fold_knobs();
     SelfPlan p;
-    if (p.carve(workspace, *sa, x->B, x->T) > workspace_bytes) return PIO_E_WORKSPACE;
-    return self_attention_run(*sa, *x, kv_mask, q_mask, full_mask, attention_bias, out, probs_out, p,
+    if (p.carve(workspace, *sa, x->B, x->T, knobs.inplace) > workspace_bytes) return PIO_E_WORKSPACE;
+    return self_attention_run(*sa, *x, kv_mask, q_mask, full_mask, attention_bias, out, probs_out, p, knobs,
                               (hipStream_t)stream);
 }
 
@@ -926,9 +742,10 @@ size_t pio_encoder_workspace_bytes(const pio_cross_attention_t *cross, const pio
     if (!cross) return 0;
     CrossPlan cp;
     size_t need = cp.carve(nullptr, *cross, B, N, M, false, true);
+    const bool inplace = fold_inplace();
     for (int l = 0; l < L; ++l) {
         SelfPlan sp;
-        const size_t n = sp.carve(nullptr, layers[l], B, N, true);
+        const size_t n = sp.carve(nullptr, layers[l], B, N, inplace, true);
         if (n > need) need = n;
     }
     return need;
@@ -980,15 +797,17 @@ int pio_encoder_fwd_opts(const pio_cross_attention_t *cross, const pio_self_atte
     }
     const pio_tensor3_t z = {out, (int64_t)N * D, D, B, N, D};
     range_part.set(PIO_RP_STACK);
+    const FoldKnobs knobs = fold_knobs();
     FoldCarry carry;  // LayerNorm fold: the row statistics of z travel from one block's fc2 to the next block's q|k|v
     for (int blk = 0; blk < num_blocks; ++blk) {  // perceiver.py:104-106: weights shared across blocks
         for (int l = 0; l < L; ++l) {
             // (per_block: block blk has its own IMAGES of the shared parameters -- same shapes -- at layers[blk * L + l])
             const pio_self_attention_t &lay = layers[(per_block ? (size_t)blk * L : 0) + l];
             SelfPlan sp;
-            sp.carve(workspace, lay, B, N, true);
+            sp.carve(workspace, lay, B, N, knobs.inplace, true);
             const bool last = blk == num_blocks - 1 && l == L - 1;
-            PIO_TRY(self_attention_run(lay, z, nullptr, nullptr, nullptr, nullptr, out, nullptr, sp, s, &carry, last));
+            PIO_TRY(self_attention_run(lay, z, nullptr, nullptr, nullptr, nullptr, out, nullptr, sp, knobs, s, &carry,
+                                       last));
         }
     }
     return PIO_OK;
@@ -1016,6 +835,14 @@ size_t pio_decoder_qcache_bytes(const pio_cross_attention_t *cross, int32_t Bq, 
     return (size_t)round_up((int64_t)Bq * Q * cross->attn.heads * cross->attn.dkp * 2, 256);
 }
 
+static bool dec_y16_enabled() {  // (env PIO_DEC_Y16, read once per process; see decoder_run)
+    static const bool on = [] {
+        const char *e = getenv("PIO_DEC_Y16");
+        return !e || atoi(e) != 0;
+    }();
+    return on;
+}
+
 static int decoder_run(const pio_cross_attention_t *cross, const pio_linear_t *final_layer, int32_t final_out,
                        const pio_tensor3_t *query, const pio_tensor3_t *query_tail, const pio_tensor3_t *latents,
                        const uint8_t *query_mask, float *out, void *workspace, size_t workspace_bytes, void *stream,
@@ -1036,11 +863,7 @@ static int decoder_run(const pio_cross_attention_t *cross, const pio_linear_t *f
     const int64_t y_ld = final_layer ? pitch4(q_c) : q_c;  // (y is internal when a final layer follows)
     // (with a final Linear the cross-attend's result is only ever its operand: fc2 writes it as 16-bit rows directly --
     //  env PIO_DEC_Y16=0: the fp32 rows + cast pass of rounds 1-3, for A/B)
-    static const bool y16_direct = [] {
-        const char *e = getenv("PIO_DEC_Y16");
-        return !e || atoi(e) != 0;
-    }();
-    const bool direct = final_layer && y16_direct && final_layer->k == padc(q_c);
+    const bool direct = decoder_y16_direct(final_layer, q_c, dec_y16_enabled());
     PIO_TRY(cross_attention_run(*cross, *query, *latents, nullptr, query_mask, nullptr, nullptr, y, nullptr, p.cp,
                                 s, nullptr, y_ld, qc, direct ? &p.y16 : nullptr, query_tail));
     if (!final_layer) return PIO_OK;
