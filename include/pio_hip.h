@@ -90,8 +90,9 @@ typedef struct pio_attention_t {
                           3: as 2, and Q and K enter the fused core as (hi, lo) pairs: S = Q_hi K_hi + Q_lo K_hi + Q_hi K_lo,
                           fp32 accumulation, inside the kernel (policy "fp16x3fq").  Pair cores exist for fp16 heads with
                           dkp <= 32 and dvp <= 160 (cross-attention kernel; key / query mask vectors, key splits) and
-                          (dkp, dvp) in {(32,32), (32,160)} (self-attention kernel, un-masked).  Every other shape -- wide
-                          single heads, the tall-head kernel, the K / V-folded path, bf16 -- has no pair core and runs the
+                          (dkp, dvp) in {(32,32), (32,160), (128,128)} (self-attention kernel, un-masked).  Every other
+                          shape -- 64-wide heads, 128-wide heads with mask vectors, wide single heads, the tall-head
+                          kernel, the K / V-folded path, bf16 -- has no pair core and runs the
                           materialised split-operand path of act_split = 1: the request is never served by a single-
                           operand Q K^T                                                                       */
     pio_linear_t qk;   /* optional (w_hi may be NULL): proj_q and proj_k stacked along the output rows
@@ -410,8 +411,9 @@ int pio_flash_attention(int32_t dtype, int32_t dkp, int32_t dvp, int32_t dk, con
  * `workspace` (pio_flash_attention_pair_workspace_bytes: key-bit words of a masked launch, fp32 partials of a key split;
  * for a shape only the tall-head kernel covers its key-bit words, for a shape both kernels cover the larger of the two, so
  * that the figure serves whichever core is named).
- * Pair operands: fp16, dkp <= 32 -- (32,32) / (32,160) on the self-attention kernel, dvp <= 160 on the cross-attention
- * kernel; anything else with Q_lo / K_lo is PIO_E_SHAPE (bf16 included). */
+ * Pair operands: fp16 -- (32,32) / (32,160) / (128,128) on the self-attention kernel (the 128-wide head never with a key
+ * split: 4 waves, or 8 under the 256-row rule), dkp <= 32 and dvp <= 160 on the cross-attention kernel; anything else with
+ * Q_lo / K_lo is PIO_E_SHAPE: (64,64), (128,128) on core 2, bf16. */
 size_t pio_flash_attention_pair_workspace_bytes(int32_t dkp, int32_t dvp, int32_t B, int32_t H, int32_t Tq, int32_t Tk);
 int pio_flash_attention_pair(int32_t dtype, int32_t dkp, int32_t dvp, int32_t dk, const void *Q, const void *Q_lo,
                              const void *K, const void *K_lo, const void *V, void *O, void *O_lo, int32_t B, int32_t H,

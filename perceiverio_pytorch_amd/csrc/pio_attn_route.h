@@ -16,9 +16,10 @@ inline bool flash_supported(int dkp, int dvp) {
            (dkp == 32 && dvp == 160);
 }
 // Q / K as (hi, lo) pairs inside the fused cores' Q K^T (S = Q_hi K_hi + Q_lo K_hi + Q_hi K_lo): the dk <= 32 fp16
-// instantiations of both kernel families.  A launch with Q_lo / K_lo on any other shape or dtype is PIO_E_SHAPE.
+// instantiations of both kernel families and the (128, 128) fp16 head of the self-attention kernel (the latent stack
+// of the classifier).  A launch with Q_lo / K_lo on any other shape or dtype -- (64, 64), bf16 -- is PIO_E_SHAPE.
 inline bool flash_pair_supported(int dtype, int dkp, int dvp) {
-    return dtype == PIO_DT_F16 && dkp == 32 && (dvp == 32 || dvp == 160);
+    return dtype == PIO_DT_F16 && ((dkp == 32 && (dvp == 32 || dvp == 160)) || (dkp == 128 && dvp == 128));
 }
 
 struct FlashRoute {
@@ -41,6 +42,18 @@ inline FlashRoute flash_route(int dkp, int dvp, int B, int H, int Tq, int Tk, bo
     const bool ksplit4 = ksplit && dkp <= 64 && dvp <= 64 && Tk >= 1024 && (Tk % 256) == 0;
     const int NW = ksplit4 ? 16 : (ksplit || wide) ? 8 : 4;
     return FlashRoute{v_rowmajor, NW, ksplit4 ? 4 : ksplit ? 2 : 1, nqt, 64 * NW};
+}
+// ... of a pair-operand launch (Q_lo / K_lo set).  dkp = 32: the same variants.  dkp = 128: a ring stage holds K, K_lo
+// and V (48 KB), two key parts would need 192 KB of LDS -- no key split; 8 waves under the same rule, else 4.
+inline FlashRoute flash_pair_route(int dkp, int dvp, int B, int H, int Tq, int Tk, bool v_rowmajor, bool ksplit_on,
+                                   int cu_budget) {
+    FlashRoute r = flash_route(dkp, dvp, B, H, Tq, Tk, v_rowmajor, ksplit_on, cu_budget);
+    if (dkp == 128 && r.KS != 1) {  // (a key split never changes nqt: 128-row tiles either way)
+        r.NW = 4;
+        r.KS = 1;
+        r.threads = 64 * r.NW;
+    }
+    return r;
 }
 
 // ---- cross-attention kernel (pio_xattn.hip): wide single heads, dv != dk, key / query mask vectors, key splits ------
@@ -168,11 +181,13 @@ inline AttnRoute attn_route(const pio_attention_t &a, const AttnCall &c) {
     // act_split == 2 ("x3f"): the projections around the core run with split operands, the core itself single-sweep
     // on the hi halves of q / k / v^T through the fused cross-attention kernel, which returns its output as a pair.
     // act_split == 3 ("x3fq"): as 2, with Q and K entering the core as the (hi, lo) pairs the projection GEMMs wrote (a
-    // projected-query cache holds both halves too).  Pair cores exist for the dk <= 32 fp16 heads (both kernel families);
-    // every other shape -- wide single heads, xattn_tall_kernel, the K / V-folded path, bf16 -- takes the MATERIALISED split-
-    // operand path, exactly what act_split == 1 runs: a pair request never silently becomes a single-operand Q K^T.
-    const bool pair_core = a.act_split == 3 && (flash_pair_supported(a.dtype, a.dkp, a.dvp) ||
-                                                xattn_pair_supported(a.dtype, a.dkp, a.dvp));
+    // projected-query cache holds both halves too).  Pair cores exist for the dk <= 32 fp16 heads (both kernel families)
+    // and for the (128, 128) fp16 head on the self-attention kernel alone, so the question is asked per core: a call with
+    // mask vectors has one only in the cross-attention family.  Every other shape -- 64-wide heads, masked 128-wide heads,
+    // wide single heads, xattn_tall_kernel, the K / V-folded path, bf16 -- takes the MATERIALISED split-operand path,
+    // exactly what act_split == 1 runs: a pair request never silently becomes a single-operand Q K^T.
+    const bool pair_core = a.act_split == 3 && (xattn_pair_supported(a.dtype, a.dkp, a.dvp) ||
+                                                (!mask_vectors && flash_pair_supported(a.dtype, a.dkp, a.dvp)));
     const bool single_core = a.act_split == 2 || pair_core;
     const bool fused_policy = !a.act_split || single_core;
     AttnRoute r = {PIO_OK, AttnCore::MATERIALISED, false, false, false, false, 0};
@@ -225,10 +240,18 @@ inline AttnRoute attn_route(const pio_attention_t &a, const AttnCall &c) {
 // The same at plan time, when masks and pointers are unknown: the route of the plain call (no mask, nothing shared, no
 // fold, no cache).  lean: the caller never passes a full mask / bias / probability output (the encoder / decoder
 // stacks), so the plan carves score buffers only when that route needs them; xpart_bytes holds for every call of the shape.
-inline AttnRoute attn_plan(const pio_attention_t &a, int B, int Bq, int Tq, int Tk, bool lean) {
+// mask_vectors: the caller may still pass key / query mask vectors (the cross-attends): where such a call has no fused core
+// of its own -- a pair request on the 128-wide head -- the plan keeps the score buffers for it.
+inline AttnRoute attn_plan(const pio_attention_t &a, int B, int Bq, int Tq, int Tk, bool lean, bool mask_vectors = false) {
     AttnCall c = {};
     c.B = B; c.Bq = Bq; c.Tq = Tq; c.Tk = Tk;
     AttnRoute r = attn_route(a, c);
+    if (mask_vectors) {
+        c.kv_mask = true;
+        const AttnRoute m = attn_route(a, c);
+        r.need_scores = r.need_scores || m.need_scores;
+        if (m.xpart_bytes > r.xpart_bytes) r.xpart_bytes = m.xpart_bytes;
+    }
     if (!lean) r.need_scores = true;
     return r;
 }

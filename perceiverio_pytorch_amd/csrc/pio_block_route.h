@@ -85,11 +85,12 @@ struct AttnScratch {
     float *scores;
     void *xpart;  // key bits / fp32 split partials of the fused cross-attention cores
     // lean: the caller never passes a full mask / bias / probability output: no score buffers where attn_plan has a fused core
-    void carve(Carver &c, const pio_attention_t &a, int Bq, int B, int Tq, int Tk, bool lean = false) {
+    // masked: ... but may pass key / query mask vectors (a cross-attend)
+    void carve(Carver &c, const pio_attention_t &a, int Bq, int B, int Tq, int Tk, bool lean = false, bool masked = false) {
         const int64_t ldq = (int64_t)a.heads * a.dkp, ldo = (int64_t)a.heads * a.dvp, tkp = pad8(Tk);
         const int64_t tkv = round_up(Tk, 32);  // V^T row pitch: whole 32-key tiles, zero padded (pio_xattn.hip)
         const bool sp = a.act_split != 0;
-        const AttnRoute plan = attn_plan(a, B, Bq, Tq, Tk, lean);
+        const AttnRoute plan = attn_plan(a, B, Bq, Tq, Tk, lean, masked);
         q16 = take_pair(c, (size_t)Bq * Tq * ldq, sp);
         // (the fused cross-attention kernel reads whole 32-key tiles: up to 31 rows behind key Tk - 1 of the last
         //  sample.  They only have to be readable -- their scores are masked by assignment -- and they are: vt16 and
@@ -187,7 +188,7 @@ struct CrossPlan {
         kv16 = take_pair(c, (size_t)B * Tk * padc(ca.attn.k_in), ca.attn.act_split != 0);
         h16 = take_pair(c, (size_t)rows * padc(ca.mlp.hidden), ca.mlp.act_split != 0);
         x1 = (float *)c.take((size_t)rows * pitch4(ca.attn.out) * 4);
-        core.carve(c, ca.attn, Bq, B, Tq, Tk, lean);
+        core.carve(c, ca.attn, Bq, B, Tq, Tk, lean, true);
         return c.off;
     }
 };

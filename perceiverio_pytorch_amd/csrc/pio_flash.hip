@@ -14,11 +14,14 @@
 //     XOR swizzle applied on the source address and on the ds_read side (conflict-free K reads, 2-way V^T reads).
 //   * V is consumed K-contiguous (V^T [dv][keys]), which is exactly what the V projection GEMM writes.
 //   * online softmax in base 2 (scale folded into the exponent constant), fp32 statistics and accumulators.
-//   * QK_PAIR (DK = 32, fp16): Q and K arrive as (hi, lo) pairs and S^T = K_lo Q_hi^T + K_hi Q_lo^T + K_hi Q_hi^T,
+//   * QK_PAIR (DK = 32 and DK = DV = 128, fp16): Q and K arrive as (hi, lo) pairs and S^T = K_lo Q_hi^T + K_hi Q_lo^T + K_hi Q_hi^T,
 //     accumulated in fp32 IN THAT ORDER (the two small products first, the large one last); lo x lo is dropped.  Q_lo is
 //     a second set of register fragments, K_lo a second K tile in every ring stage (same pieces, same swizzle, same
 //     conflict-free reads, same single barrier per tile).  Everything behind S^T is unchanged; the output may leave as a
 //     pair (O_lo: the rounding residual), which the split-operand out projection behind the core consumes.
+//     The same for the 128-wide stack heads (DK = DV = 128, fp16, no key split): there the K fragments are streamed per
+//     k-step for the two small products and K_hi is read from LDS a second time for the large one.  Everything else --
+//     64-wide heads, bf16, a key-split pair variant -- has no pair instantiation: PIO_E_SHAPE from the launcher.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -68,9 +71,13 @@ __device__ __forceinline__ int vrow_swz(int r) {
 // (two waves per SIMD: one wave's dependent MFMA -> exp2 -> MFMA chain covers the other's) and merge (m, l, O) through
 // LDS at the end.  For the shapes that offer only one 4-wave workgroup per CU: the flow stack (16 heads x 2048 latents:
 // 256 workgroups of ~1 900 cycles per 64-key tile against 256 cycles of MFMAs), small ImageNet batches.
+// QK_PAIR on the 128-wide head (DK = DV = 128, KS = 1): a ring stage is K + K_lo + V = 48 KB, two stages 96 KB -- one
+// workgroup per CU whatever NW is -- and Q_hi, Q_lo, O and S already take 224 registers of a wave, so the K fragments
+// are not all held at once as for DK = 32: see the S^T block.
 template <int DT, int DK, int DV, bool VROW, int NW, int KS = 1, bool QK_PAIR = false>
-__global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void flash_attn_kernel(const FlashParams p) {
-    static_assert(!QK_PAIR || (DK == 32 && DT == PIO_DT_F16), "pair-operand Q K^T: the DK = 32 fp16 instantiations");
+__global__ __launch_bounds__(NW * 64, (NW >= 8 || (QK_PAIR && DK == 128)) ? 1 : 2) void flash_attn_kernel(const FlashParams p) {
+    static_assert(!QK_PAIR || (DT == PIO_DT_F16 && (DK == 32 || (DK == 128 && DV == 128 && KS == 1))),
+                  "pair-operand Q K^T: the DK = 32 and the (128, 128) un-split fp16 instantiations");
     typedef typename Op<DT>::T T;
     typedef typename Op<DT>::V8 V8;
     typedef typename Op<DT>::V4 V4;
@@ -92,6 +99,7 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void flash_attn_kernel(co
     constexpr int MRG = KS > 1 ? (KS - 1) * NWQ * 64 * (NDT * 16 + 2) * 4 : 0;   // merge area: (O^T, m, l) of the other key parts
     constexpr int RING = 2 * KS * (K_STG + V_TILE), OSTG = NW * 32 * OROW;
     constexpr int SM0 = RING > OSTG ? RING : OSTG;
+    static_assert((SM0 > MRG ? SM0 : MRG) <= 160 * 1024, "LDS budget of one CU");
     __shared__ __attribute__((aligned(16))) char smem[SM0 > MRG ? SM0 : MRG];
 
     const int tid = threadIdx.x;
@@ -211,7 +219,26 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void flash_attn_kernel(co
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
             for (int j = 0; j < 16; ++j) sacc[t][j] = 0.f;
-            if constexpr (QK_PAIR) {
+            if constexpr (QK_PAIR && DK == 128) {
+                // The same sum in the same order -- the two small products first, the large one last -- with the K
+                // fragments streamed: K_lo and K_hi of one k-step feed the two small products and are dropped, then K_hi
+                // is read from LDS a second time for the large product (16 fragments held at once would be 64 registers).
+#pragma unroll
+                for (int s = 0; s < NQS; ++s) {
+                    const int chunk = (2 * s + hh) ^ k_swz;
+                    const V8 kl = *(const V8 *)(kb + K_TILE + k_off[t] + chunk * 16);
+                    const V8 kf = *(const V8 *)(kb + k_off[t] + chunk * 16);
+                    sacc[t] = Op<DT>::mfma32(kl, qf[s], sacc[t]);
+                    sacc[t] = Op<DT>::mfma32(kf, ql[s], sacc[t]);
+                }
+                asm volatile("" ::: "memory");   // (keeps the second read a read: no K_hi fragment lives across this line)
+#pragma unroll
+                for (int s = 0; s < NQS; ++s) {
+                    const int chunk = (2 * s + hh) ^ k_swz;
+                    const V8 kf = *(const V8 *)(kb + k_off[t] + chunk * 16);
+                    sacc[t] = Op<DT>::mfma32(kf, qf[s], sacc[t]);
+                }
+            } else if constexpr (QK_PAIR) {
                 // the small products first (K_lo Q_hi^T, then K_hi Q_lo^T), the large one last; every K fragment is read
                 // from LDS once
                 V8 kh_f[NQS], kl_f[NQS];
@@ -436,20 +463,25 @@ extern "C" int pio_debug_flash_variant(int which) { return flash_variant_overrid
 #endif
 
 // The instantiation flash_route names: (V^T, 4, 1), (row, 4, 1), (row, 8, 1), (row, 8, 2) for every head shape, and
-// (row, 16, 4) for the narrow heads.
+// (row, 16, 4) for the narrow heads.  The pair-operand 128-wide head (flash_pair_route) has the first three: two key parts
+// would need 192 KB of ring.
 template <int DT, int DK, int DV, bool PAIR>
 static void flash_launch(const FlashRoute &r, dim3 grid, hipStream_t s, const FlashParams &p) {
     void (*k)(FlashParams) = flash_attn_kernel<DT, DK, DV, false, 4, 1, PAIR>;
     if (r.v_rowmajor) k = flash_attn_kernel<DT, DK, DV, true, 4, 1, PAIR>;
-    if (r.NW == 8) k = r.KS == 2 ? flash_attn_kernel<DT, DK, DV, true, 8, 2, PAIR> : flash_attn_kernel<DT, DK, DV, true, 8, 1, PAIR>;
-    if constexpr (DK <= 64 && DV <= 64)
-        if (r.NW == 16) k = flash_attn_kernel<DT, DK, DV, true, 16, 4, PAIR>;
+    if constexpr (PAIR && DK == 128) {
+        if (r.NW == 8) k = flash_attn_kernel<DT, DK, DV, true, 8, 1, PAIR>;
+    } else {
+        if (r.NW == 8) k = r.KS == 2 ? flash_attn_kernel<DT, DK, DV, true, 8, 2, PAIR> : flash_attn_kernel<DT, DK, DV, true, 8, 1, PAIR>;
+        if constexpr (DK <= 64 && DV <= 64)
+            if (r.NW == 16) k = flash_attn_kernel<DT, DK, DV, true, 16, 4, PAIR>;
+    }
     hipLaunchKernelGGL(k, grid, dim3(r.threads), 0, s, p);
 }
-// ... over the operand dtype and, on the DK = 32 fp16 heads, the pair-operand (QK_PAIR) instantiations
+// ... over the operand dtype and, on the DK = 32 and the (128, 128) fp16 heads, the pair-operand (QK_PAIR) instantiations
 template <int DK, int DV>
 static void flash_launch_dt(int dtype, bool pair, const FlashRoute &r, dim3 grid, hipStream_t s, const FlashParams &p) {
-    if constexpr (DK == 32)
+    if constexpr (DK == 32 || (DK == 128 && DV == 128))
         if (pair) return flash_launch<PIO_DT_F16, DK, DV, true>(r, grid, s, p);
     if (dtype == PIO_DT_F16) flash_launch<PIO_DT_F16, DK, DV, false>(r, grid, s, p);
     else flash_launch<PIO_DT_BF16, DK, DV, false>(r, grid, s, p);
@@ -468,7 +500,8 @@ int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const At
         const char *e = getenv("PIO_FLASH_KSPLIT");
         return !e || atoi(e) != 0;
     }();
-    const FlashRoute r = flash_route(dkp, dvp, B, H, Tq, Tk, v_rowmajor, ksplit_on, cu_budget());
+    const FlashRoute r = pair ? flash_pair_route(dkp, dvp, B, H, Tq, Tk, v_rowmajor, ksplit_on, cu_budget())
+                              : flash_route(dkp, dvp, B, H, Tq, Tk, v_rowmajor, ksplit_on, cu_budget());
     // (an output PAIR leaves through the per-lane 8-byte stores: the staged whole-row epilogue carries one half only)
     const int o_rows16 = (!t.O_lo && t.ldo % 8 == 0 && t.sOb % 8 == 0 && ((uintptr_t)t.O & 15) == 0) ? 1 : 0;
     FlashParams p{t.Q, t.K, t.VT, t.O, Tq, Tk, H, r.nqt, t.ldq, t.ldk, t.ldvt, t.ldo, t.sQb, t.sKb, t.sVb, t.sOb,
