@@ -321,6 +321,25 @@ int pio_layernorm_cast_cat(const pio_tensor3_t *x1, const pio_tensor3_t *x2, con
 int pio_bn_relu_maxpool_tokens(const float *x, const float *scale, const float *shift, float *y, int32_t B, int32_t C,
                                int32_t H, int32_t W, int32_t pad_top, int32_t pad_left, void *stream);
 
+/* Front end of the optical-flow model in one pass over a frame pair: the zero-padded 3x3 neighbourhood of every pixel
+ * (processor_utils.py:98-116 patches_for_flow, :59-95 extract_patches: colour fastest inside a patch position), the two
+ * frames side by side in the channel axis (processor_utils.py:21-38 space_to_depth with temporal_block_size = 2: frame
+ * slowest) and the projection behind them (preprocessors.py:57-258 ImagePreprocessor, conv_after_patching: nn.Linear) --
+ * one 3x3 "same" convolution from 2 C planes to `out` channels-last outputs:
+ *   y[n, r*W + x, o] = bias[o] + sum_{t<2} sum_{py,px<3} sum_{c<C} w[o, t*9*C + (py*3+px)*C + c]
+ *                                                                  * frame_t[n, c, r+py-1, x+px-1]     (0 outside the image)
+ * frame0 / frame1: fp32 [N, C, H, W] views with x contiguous and their own element strides (sample, plane, row); positions
+ * outside [0,H) x [0,W) are never read.  w [out, 18*C] row-major, bias [out]; y [N, H*W, out] fp32 with row pitch ldy.
+ * w == NULL (conv_after_patching = False): y receives the 18*C raw patch channels in the order above, out must equal 18*C
+ * and bias is ignored.  fp32 FMA accumulation, one chain bias -> k = 0 .. 18*C-1 per output: the result does not depend on
+ * the launch geometry and is bit-identical from run to run.  No workspace, no device allocation, no synchronisation.
+ * PIO_E_ARG: NULL frame0 / frame1 / y, or w without bias; PIO_E_SHAPE: N, H, W <= 0, C outside [1, 4], out outside
+ * [1, 128], out % 4 != 0 with w (out != 18*C without), ldy < out, N or ceil(H/4) above 65535; PIO_E_ALIGN: ldy % 4 != 0,
+ * y not 16-byte aligned, a frame / w / bias pointer not 4-byte aligned.  A refused call launches nothing. */
+int pio_flow_patch_tokens(const float *frame0, const float *frame1, int64_t sn0, int64_t sc0, int64_t sy0, int64_t sn1,
+                          int64_t sc1, int64_t sy1, const float *w, const float *bias, float *y, int64_t ldy, int32_t N,
+                          int32_t C, int32_t H, int32_t W, int32_t out, void *stream);
+
 /* C = epilogue(alpha * A B^T): A [M,K], B [N,K] operand dtype, K contiguous (multiple of 8).
  * Batched over z = zb*nh + zh with element strides; bias_mode 0 none / 1 per column / 2 per row;
  * act 0 none / 1 exact-erf GELU (F.gelu, transformer_primitives.py:214); optional fp32 residual R

@@ -196,6 +196,13 @@ int pio_bn_relu_maxpool_tokens(const float *x, const float *scale, const float *
     return bn_relu_pool_nhwc_launch(x, scale, shift, y, B, C, H, W, pad_top, pad_left, (hipStream_t)stream);
 }
 
+int pio_flow_patch_tokens(const float *frame0, const float *frame1, int64_t sn0, int64_t sc0, int64_t sy0, int64_t sn1,
+                          int64_t sc1, int64_t sy1, const float *w, const float *bias, float *y, int64_t ldy, int32_t N,
+                          int32_t C, int32_t H, int32_t W, int32_t out, void *stream) {
+    return flow_patch_tokens_launch(frame0, frame1, sn0, sc0, sy0, sn1, sc1, sy1, w, bias, y, ldy, N, C, H, W, out,
+                                    (hipStream_t)stream);
+}
+
 int pio_gemm_nt(const pio_gemm_t *g, void *stream) {
     if (!g) return PIO_E_ARG;
     return gemm_nt_launch(*g, (hipStream_t)stream);

@@ -132,6 +132,10 @@ int range_probe_end(int32_t *parts, int32_t *kinds, int cap);
 // eval BatchNorm -> ReLU -> 3x3/2 SAME max-pool -> channels-last tokens (tail of Conv2DDownsample)
 int bn_relu_pool_nhwc_launch(const float *x, const float *scale, const float *shift, float *y, int B, int C, int H, int W,
                              int pad_top, int pad_left, hipStream_t s);
+// flow front end: 3x3 zero-padded patches of a frame pair + the 1x1 projection behind them (w == NULL: the raw patches)
+int flow_patch_tokens_launch(const float *f0, const float *f1, int64_t sn0, int64_t sc0, int64_t sy0, int64_t sn1,
+                             int64_t sc1, int64_t sy1, const float *w, const float *bias, float *y, int64_t ldy, int N,
+                             int C, int H, int W, int out, hipStream_t s);
 int pack_linear_launch(const float *w, const float *bias, int out, int in, int64_t ldw, int row_heads,
                        int col_heads, void *dst_hi, void *dst_lo, float *dst_bias, int dst_row0, int k_pad,
                        int dtype, hipStream_t s);

@@ -251,6 +251,7 @@ class ImagePreprocessor(nn.Module, _PosMixin):
         self._spatial_downsample = spatial_downsample
         self._temporal_downsample = temporal_downsample
         self._conv_after_patching = conv_after_patching
+        self._patch_channels = input_channels * spatial_downsample ** 2 * temporal_downsample
         self._position_encoding_type = position_encoding_type
         if prep_type == "conv":
             layers = math.log(spatial_downsample, 4)
@@ -288,8 +289,52 @@ class ImagePreprocessor(nn.Module, _PosMixin):
     def n_output_channels(self):
         return self.output_channels
 
+    def _flow_front(self, pair: torch.Tensor):
+        """The optical-flow front end on a RAW frame pair [N, 2, C, H, W] by ONE HIP kernel (pio_flow_patch_tokens):
+        patches_for_flow (3x3 zero-padded neighbourhoods), the channels-last copy, space_to_depth (the two frames side by
+        side: 18 C channels) and the Linear of conv_after_patching, without any of their temporaries.  Returns the feature
+        array [N, H*W, out] -- without the Linear the 18 C patch channels, as a view of rows padded to a multiple of 4
+        -- or None when this configuration or input is not the covered one (the caller's ordinary path then runs: it
+        expects the PATCHED frames [N, 2, 9 C, H, W])."""
+        if (self._prep_type != "patches" or self._spatial_downsample != 1 or self._temporal_downsample != 2
+                or pair.dim() != 5 or pair.shape[1] != 2 or not pair.is_cuda or pair.dtype != torch.float32):
+            return None
+        from . import _lib as L
+        from . import runtime as R
+        n, _, c, h, w = pair.shape
+        if R.get_backend() != "hip" or not 1 <= c <= 4 or [h, w] != list(self.index_dims):
+            return None
+        if self._conv_after_patching:
+            lin = self._conv_after_patch_layer
+            out = lin.out_features
+            if lin.in_features != 18 * c or out % 4 or out > 128 or lin.weight.dtype != torch.float32:
+                return None
+            wt, bias = lin.weight.detach().contiguous(), lin.bias.detach().contiguous()
+            deps = (pair, lin.weight, lin.bias)
+        else:
+            out = 18 * c
+            if self._patch_channels != out:
+                return None
+            wt = bias = None
+            deps = (pair,)
+        if pair.stride(4) != 1 and w > 1:
+            pair = pair.contiguous()
+        ldy = (out + 3) // 4 * 4
+        y = torch.empty((n, h * w, ldy), dtype=torch.float32, device=pair.device)
+        f0, f1 = pair[:, 0], pair[:, 1]
+        with R.on_device(pair.device):
+            L.check(L.lib().pio_flow_patch_tokens(f0.data_ptr(), f1.data_ptr(), pair.stride(0), pair.stride(2),
+                                                  pair.stride(3), pair.stride(0), pair.stride(2), pair.stride(3),
+                                                  None if wt is None else wt.data_ptr(),
+                                                  None if bias is None else bias.data_ptr(), y.data_ptr(), ldy, n, c, h,
+                                                  w, out, R.stream_ptr(pair.device)), "pio_flow_patch_tokens")
+        return R.forward_only(y if ldy == out else y[:, :, :out], *deps)
+
     def _features(self, inputs: torch.Tensor) -> torch.Tensor:
         x = inputs
+        tokens = self._flow_front(x)                     # raw frame pair: 3x3 patches + projection in one HIP pass
+        if tokens is not None:
+            return tokens
         if self._prep_type == "conv" and x.dim() == 4:
             tokens = self.convnet.forward_tokens(x)      # conv (MIOpen) + one fused HIP pass, channels-last tokens
             if tokens is not None:

@@ -12,12 +12,13 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import io_processors
 from .io_processors import (AudioPostprocessor, AudioPreprocessor, ClassificationPostprocessor,
                             EmbeddingPostprocessor, EmbeddingPreprocessor, FlowPostprocessor, ImagePreprocessor,
-                            OneHotPreprocessor, ProjectionPostprocessor, patches_for_flow)
+                            OneHotPreprocessor, ProjectionPostprocessor)
 from .output_queries import FlowQuery, FourierQuery, TrainableQuery
 from .perceiver import PerceiverIO
-from .runtime import precision
+from .runtime import get_backend, precision
 from .position_encoding import PosEncodingType
 
 
@@ -230,6 +231,10 @@ class FlowPerceiver(nn.Module):
         self._flow_scale_factor = flow_scale_factor
         self.query_shard = None      # (rank, world): decode this rank's query rows only + all-gather (dist.py)
         self.tiles_per_call = 4      # test-mode tiling: tiles batched per forward (1 = the reference's one at a time)
+        # CUDA fp32 frames under the hip backend reach the preprocessor as the RAW pair: 3x3 patches, the frames side
+        # by side and the 54 -> 64 projection are one HIP pass (pio_flow_patch_tokens) instead of pad / unfold / two
+        # permute copies / a BLAS call.  False (and every other input): patches_for_flow here, as the reference does.
+        self.fused_front_end = True
         prep = ImagePreprocessor(img_size=img_size, input_channels=3 * 3 ** 2, prep_type="patches",
                                  spatial_downsample=1, temporal_downsample=2, conv_after_patching=True,
                                  num_channels=64, n_extra_pos_mlp=0, position_encoding_type=PosEncodingType.FOURIER,
@@ -262,8 +267,10 @@ class FlowPerceiver(nn.Module):
         return itertools.product(ys, xs)
 
     def _predict_patch(self, patch):
+        fused = self.fused_front_end and patch.is_cuda and patch.dtype == torch.float32 and get_backend() == "hip"
         with _policy_scope(self):
-            return self.perceiver(patches_for_flow(patch).movedim(-1, -3), query_shard=self.query_shard)
+            x = patch if fused else io_processors.patches_for_flow(patch).movedim(-1, -3)
+            return self.perceiver(x, query_shard=self.query_shard)
 
     def forward(self, image1: torch.Tensor, image2: torch.Tensor, test_mode: bool = False, min_overlap: int = 20):
         h, w = image1.shape[2], image1.shape[3]
