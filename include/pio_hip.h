@@ -345,7 +345,16 @@ int pio_flow_patch_tokens(const float *frame0, const float *frame1, int64_t sn0,
  * act 0 none / 1 exact-erf GELU (F.gelu, transformer_primitives.py:214); optional fp32 residual R
  * added after the activation (row m of the flattened problem reads
  * R + (m / r_rows_per_batch)*r_stride_b + (m % r_rows_per_batch)*ldr when r_rows_per_batch > 0);
- * output fp32 (out_f32=1) or operand dtype with zero fill of columns [N, n_store). */
+ * output fp32 (out_f32=1) or operand dtype with zero fill of columns [N, n_store).
+ * What a call touches (tests/test_gemm_addr_gpu.py holds every kernel to it, bit for bit, on NaN-surrounded buffers):
+ *   read:    A / A_lo rows < M and B / B_lo rows < N of every (zb, zh) slice, columns < K -- never the pitch bytes
+ *            [K, lda) / [K, ldb), never the gap between two slices, never rows of B_lo below b_lo_n0; bias entries < N
+ *            (per column) or < M (per row); residual columns < N of the rows the formula above names -- one residual for
+ *            every slice: it has no batch index of its own;
+ *   written: rows < M, columns < n_store of every slice of C (and C_lo): columns [N, n_store) as +0, nothing in the
+ *            pitch columns [n_store, ldc), nothing behind row M - 1, nothing between two slices.  Slices may interleave
+ *            inside a row (sCh < ldc: heads side by side, n_store == N).
+ * A descriptor no kernel takes returns its PIO_E_* code and writes nothing. */
 typedef struct pio_gemm_t {
     const void *A, *B;
     const void *A_lo, *B_lo; /* optional extra K sweeps: C += A*B_lo^T, C += A_lo*B^T (split operands) */

@@ -64,6 +64,7 @@ def _assert_close(y, ref, tol=TOL, what=""):
 
 # ----------------------------------------------------------------------------------------------------
 # primitive kernels through raw ctypes
+# (GEMM: arithmetic on dense layouts here; every stride / pitch / offset of pio_gemm_t, exactly: test_gemm_addr_gpu.py)
 # ----------------------------------------------------------------------------------------------------
 GEMM_SHAPES = [
     # M, N, K, batch, nh, bias_mode, act, residual, out_f32, lo
