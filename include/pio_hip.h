@@ -354,7 +354,23 @@ int pio_flow_patch_tokens(const float *frame0, const float *frame1, int64_t sn0,
  *   written: rows < M, columns < n_store of every slice of C (and C_lo): columns [N, n_store) as +0, nothing in the
  *            pitch columns [n_store, ldc), nothing behind row M - 1, nothing between two slices.  Slices may interleave
  *            inside a row (sCh < ldc: heads side by side, n_store == N).
- * A descriptor no kernel takes returns its PIO_E_* code and writes nothing. */
+ * The LayerNorm-fold fields (tests/test_gemm_fold_gpu.py holds gemm_nt_wide and the six tile kernels to it the same way):
+ *   producer  read:    R16_hi / R16_lo (or R) rows < M, columns < N -- never the pitch columns [N, ld16), never a row
+ *                      behind M - 1; bias entries < N;
+ *             written: rows < M, columns < N of X16, X16_lo and (when given) C, nothing in their pitch columns;
+ *                      row_part[m < M][s < N / w][2]; *range_flag = 1 when some row's sum of squares is not finite, and
+ *                      not touched otherwise (it is never cleared; the words beside it are never written).  In place
+ *                      (R16_* == X16*) every element is read before it is written.  With integer-valued x every sum is
+ *                      exact; else it is an fp32 sum in an order the kernel chooses.
+ *   consumer  read:    ln_part rows < M, slots < ln_slots (any ln_slots > 0 on the tile kernels: it need not be K / 64),
+ *                      ln_c and bias entries < N;
+ *             written: rows < M, columns < n_store of C (and, tile kernels, C_lo), [N, n_store) as +0.
+ *             mean = S / K, var = max(Q / K - mean^2, 0), rstd = 1 / sqrt(var + ln_eps) with S, Q the sums of the row's
+ *             slots; 1 / sqrt is exact where var + ln_eps is a power of four.
+ *   One K sweep on the tile kernels; on gemm_nt_wide the consumer and the 16-bit-pair producer also take B_lo, the
+ *   fp32-residual producer B_lo and A_lo; alpha is applied by every producer; a consumer needs alpha == 1.
+ * A descriptor no kernel takes returns its PIO_E_* code and writes nothing.  pio_gemm_kernel_override(1) never sends a
+ * fold descriptor to the streaming kernel, which has no fold epilogue. */
 typedef struct pio_gemm_t {
     const void *A, *B;
     const void *A_lo, *B_lo; /* optional extra K sweeps: C += A*B_lo^T, C += A_lo*B^T (split operands) */

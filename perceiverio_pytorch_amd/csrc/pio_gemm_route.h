@@ -299,7 +299,7 @@ inline GemmRoute gemm_route(const pio_gemm_t &g, const GemmParams &p, int forced
     const int tn128 = (p.n_store + 127) / 128;
     bool stream = !fold_small && g.batch == 1 && g.M >= 1024 && p.n_store >= 128 &&
                   (double)tn128 * 128.0 <= 1.25 * p.n_store && (int64_t)tm256 * tn128 >= 448;
-    if (forced == 1) stream = true;
+    if (forced == 1 && !fold_small) stream = true;   // (never a fold: the streaming kernel has no fold epilogue)
     if (forced == 128 || forced == 256) stream = false;
     if (stream && gemm_stream_ok(p, g.batch, n_cu))
         return route(GemmKernel::STREAM, "stream",

@@ -6,7 +6,7 @@ kernel x feature matrix, the reference against torch) and tests/test_gemm_addr_g
 
 Operands are small integers: every product and every partial sum is an integer far below 2^24, so the fp32 accumulator of
 any kernel holds the true result in any summation order and the comparison needs no tolerance (exact_ok).  act == 0 and
-no LayerNorm-fold fields throughout: GELU and the fold are not exact and stay with tests/test_parity_gpu.py.
+no LayerNorm-fold fields throughout: the fold and GELU under it have tests/gemm_fold_cases.py, test_gemm_fold_host.py / _gpu.py.
 
 A case is a dict of the pio_gemm_t fields that matter plus
     override  value passed to pio_gemm_kernel_override
