@@ -340,6 +340,46 @@ int pio_flow_patch_tokens(const float *frame0, const float *frame1, int64_t sn0,
                           int64_t sc1, int64_t sy1, const float *w, const float *bias, float *y, int64_t ldy, int32_t N,
                           int32_t C, int32_t H, int32_t W, int32_t out, void *stream);
 
+/* One segment of the multimodal front end: rows [row0, row0 + M) of every sample of the token array.  With
+ * Cp = Cc - C1 - C2 >= 0 and x the row
+ *   x[0       : C1     ] = feature(b, m, :)
+ *   x[C1      : C1 + C2] = table[m*ldt : m*ldt + C2]        (one batch-invariant table, row pitch ldt)
+ *   x[C1 + C2 : Cc     ] = pad[0 : Cp]
+ * the segment writes  y[b, row0 + m, c] = x[c]  (token == NULL: an unmasked modality) or  token[c] + 0.0f * x[c]  (a
+ * masked one -- perceiver.py:451-499, mask probability 1: two rounded fp32 operations, a non-finite x[c] gives NaN).
+ * kind PIO_TOKENS_ROWS: feature(b, m, j) = feature[b*sb + m*sm + j]  (st, sc, sy, T, C, H, W, s ignored).
+ * kind PIO_TOKENS_S2D:  space-to-depth (processor_utils.py:21-38) with spatial block s and temporal block 1 of frames
+ *   [B, T, C, H, W] given by their strides (sb, st, sc, sy; x contiguous):  m = (t*(H/s) + y)*(W/s) + x,
+ *   j = (dy*s + dx)*C + c,  feature(b, m, j) = feature[b*sb + t*st + c*sc + (y*s + dy)*sy + x*s + dx];
+ *   1 <= s <= 8, 1 <= C <= 4, H % s == W % s == 0, C1 == s*s*C, M == T*(H/s)*(W/s)  (sm ignored; a 4-D image: T = 1).
+ * A pointer may be NULL where its width (C1, C2, Cp) is 0. */
+enum { PIO_TOKENS_ROWS = 0, PIO_TOKENS_S2D = 1 };
+#define PIO_MAX_TOKEN_SEGMENTS 8
+typedef struct pio_token_segment_t {
+    const float *feature;
+    const float *table;
+    const float *pad;
+    const float *token;
+    int64_t sb, sm, st, sc, sy, ldt; /* element strides */
+    int32_t kind;                    /* PIO_TOKENS_ROWS / PIO_TOKENS_S2D */
+    int32_t row0, M;
+    int32_t C1, C2;
+    int32_t T, C, H, W, s;
+} pio_token_segment_t;
+
+/* The multimodal front end (MultimodalPreprocessor, perceiver.py:451-499: per modality features | position encoding |
+ * padding embedding, optional mask token, concatenation over the modalities) as ONE launch: nseg (1 .. 8) segments fill
+ * their rows of y [B, Mtot, Cc] fp32 (row pitch ldy, sample stride sYb; sYb is not read when B == 1).  Rows no segment
+ * covers and the columns [Cc, ldy) are not written.  Only moves and the exact masked expression above: bit-identical to the
+ * chain of torch.cat calls it replaces, and from run to run.  Cc % 4 == 0: rows leave as 16-byte vectors (y 16-byte aligned,
+ * ldy % 4 == 0, sYb % 4 == 0); otherwise as dwords.  No workspace, no device allocation, no synchronisation.
+ * PIO_E_ARG: NULL segs / y, nseg outside [1, 8], an unknown kind, a NULL feature / table / pad pointer whose width is > 0;
+ * PIO_E_SHAPE: B, Mtot, Cc, M <= 0, C1 or C2 < 0, C1 + C2 > Cc, ldy < Cc, sYb below one sample's extent, the S2D
+ * conditions above, a segment outside [0, Mtot), two segments that overlap; PIO_E_ALIGN: a pointer not 4-byte aligned, on
+ * the vector path y not 16-byte aligned or ldy / sYb no multiple of 4.  A refused call launches nothing. */
+int pio_assemble_tokens(const pio_token_segment_t *segs, int32_t nseg, float *y, int64_t ldy, int64_t sYb, int32_t B,
+                        int32_t Mtot, int32_t Cc, void *stream);
+
 /* C = epilogue(alpha * A B^T): A [M,K], B [N,K] operand dtype, K contiguous (multiple of 8).
  * Batched over z = zb*nh + zh with element strides; bias_mode 0 none / 1 per column / 2 per row;
  * act 0 none / 1 exact-erf GELU (F.gelu, transformer_primitives.py:214); optional fp32 residual R

@@ -71,6 +71,20 @@ class CallOpts(C.Structure):
     _fields_ = [("ln_fold", C.c_int32), ("cu_budget", C.c_int32)]
 
 
+PIO_TOKENS_ROWS = 0
+PIO_TOKENS_S2D = 1
+PIO_MAX_TOKEN_SEGMENTS = 8
+
+
+class TokenSegment(C.Structure):
+    """pio_token_segment_t: one row segment of pio_assemble_tokens (features | position table | padding, optional token)."""
+    _fields_ = [("feature", C.c_void_p), ("table", C.c_void_p), ("pad", C.c_void_p), ("token", C.c_void_p),
+                ("sb", C.c_int64), ("sm", C.c_int64), ("st", C.c_int64), ("sc", C.c_int64), ("sy", C.c_int64),
+                ("ldt", C.c_int64), ("kind", C.c_int32), ("row0", C.c_int32), ("M", C.c_int32), ("C1", C.c_int32),
+                ("C2", C.c_int32), ("T", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("s", C.c_int32)]
+
+
 class Gemm(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("A_lo", C.c_void_p), ("B_lo", C.c_void_p), ("C", C.c_void_p),
                 ("C_lo", C.c_void_p),
@@ -121,6 +135,7 @@ SIGNATURES = {
     "pio_bn_relu_maxpool_tokens": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "pio_flow_patch_tokens": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32,
                                         _i32, _i32, _vp]),
+    "pio_assemble_tokens": (C.c_int, [P(TokenSegment), _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "pio_gemm_nt": (C.c_int, [P(Gemm), _vp]),
     "pio_softmax_rows": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f, _vp, _vp, _vp, _vp, _i32, _vp]),
     "pio_flash_attention": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64,

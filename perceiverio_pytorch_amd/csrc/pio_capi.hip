@@ -203,6 +203,11 @@ int pio_flow_patch_tokens(const float *frame0, const float *frame1, int64_t sn0,
                                     (hipStream_t)stream);
 }
 
+int pio_assemble_tokens(const pio_token_segment_t *segs, int32_t nseg, float *y, int64_t ldy, int64_t sYb, int32_t B,
+                        int32_t Mtot, int32_t Cc, void *stream) {
+    return assemble_tokens_launch(segs, nseg, y, ldy, sYb, B, Mtot, Cc, (hipStream_t)stream);
+}
+
 int pio_gemm_nt(const pio_gemm_t *g, void *stream) {
     if (!g) return PIO_E_ARG;
     return gemm_nt_launch(*g, (hipStream_t)stream);

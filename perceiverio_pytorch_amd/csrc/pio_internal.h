@@ -136,6 +136,9 @@ int bn_relu_pool_nhwc_launch(const float *x, const float *scale, const float *sh
 int flow_patch_tokens_launch(const float *f0, const float *f1, int64_t sn0, int64_t sc0, int64_t sy0, int64_t sn1,
                              int64_t sc1, int64_t sy1, const float *w, const float *bias, float *y, int64_t ldy, int N,
                              int C, int H, int W, int out, hipStream_t s);
+// multimodal front end: features | position table | padding embedding (| mask token) of up to 8 row segments in one launch
+int assemble_tokens_launch(const pio_token_segment_t *segs, int nseg, float *y, int64_t ldy, int64_t sYb, int B, int Mtot,
+                           int Cc, hipStream_t s);
 int pack_linear_launch(const float *w, const float *bias, int out, int in, int64_t ldw, int row_heads,
                        int col_heads, void *dst_hi, void *dst_lo, float *dst_bias, int dst_row0, int k_pad,
                        int dtype, hipStream_t s);

@@ -368,6 +368,17 @@ class MultiModalPerceiver(nn.Module):
             output_queries=queries, input_padding_channels=4, output_query_padding_channels=2,
             input_mask_probs={"image": 0.0, "audio": 0.0, "label": 1.0})
 
+    # The encoder input -- audio | video | label, each padded to 704 channels, the label replaced by its mask token, the
+    # three concatenated -- comes from ONE HIP launch (MultimodalPreprocessor.fused_assembly -> pio_assemble_tokens) for
+    # CUDA fp32 inputs under the hip backend; False restores the chain of torch.cat calls.  Same bits either way.
+    @property
+    def fused_front_end(self) -> bool:
+        return self.perceiver._multi_preprocessor.fused_assembly
+
+    @fused_front_end.setter
+    def fused_front_end(self, on: bool) -> None:
+        self.perceiver._multi_preprocessor.fused_assembly = bool(on)
+
     def forward(self, images: torch.Tensor, audio: torch.Tensor, n_chunks: int = 128):
         with _policy_scope(self):
             return self._forward(images, audio, n_chunks)

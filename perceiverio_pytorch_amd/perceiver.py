@@ -7,6 +7,7 @@ num_self_attends_per_block stack is enqueued on the current HIP stream without r
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import torch
@@ -372,7 +373,133 @@ class MultimodalPreprocessor(nn.Module):
     def n_output_channels(self):
         return self._common_channels
 
+    # One HIP launch (pio_assemble_tokens) instead of the chain of copies below, when every modality is a pure move: see
+    # _assemble.  False, and every input or configuration _assemble declines, runs the chain exactly as before.
+    fused_assembly = True
+
+    def _assemble(self, inputs, pos):
+        """(x, sizes, without_pos) of forward() from ONE pio_assemble_tokens call, or None.  Taken under the hip backend
+        for pos=None, CUDA fp32 inputs, mask probabilities <= 0 or >= 1 and modalities that only move values:
+        ImagePreprocessor "patches" (temporal_downsample 1, no conv_after_patching; a space-to-depth segment) or "pixels"
+        without subsampling, AudioPreprocessor, OneHotPreprocessor -- image / audio with a concatenated, batch-invariant
+        position table and no extra position MLPs.  A masked space-to-depth modality takes the chain.  The result is
+        bit-identical to the chain's; without_pos[m] is a view of x (of the modality's own features where it is masked)."""
+        from .io_processors import AudioPreprocessor, ImagePreprocessor, OneHotPreprocessor
+        if not self.fused_assembly or pos is not None or self._preprocessors is None or R.get_backend() != "hip":
+            return None
+        names = list(self._preprocessors.keys())
+        if not 1 <= len(names) <= L.PIO_MAX_TOKEN_SEGMENTS or any(m not in inputs for m in names):
+            return None
+        dev, batch, cc = None, None, self._common_channels
+        keep, deps, plan = [], [], {}
+        for m in names:
+            prep, x = self._preprocessors[m], inputs[m]
+            if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() < 2:
+                return None
+            if dev is None:
+                dev, batch = x.device, x.shape[0]
+            if x.device != dev or x.shape[0] != batch or batch < 1:
+                return None
+            p = 0.0 if self._mask_probs is None else float(self._mask_probs[m])
+            if 0.0 < p < 1.0:
+                return None
+            seg = L.TokenSegment()
+            if isinstance(prep, OneHotPreprocessor):
+                if x.dim() != 2:
+                    return None
+                feats = x[:, None, :]
+            elif isinstance(prep, AudioPreprocessor):
+                feats = x.reshape(batch, -1, prep._samples_per_patch)
+            elif isinstance(prep, ImagePreprocessor):
+                s = prep._spatial_downsample
+                if prep._prep_type == "patches":
+                    if prep._temporal_downsample != 1 or prep._conv_after_patching:
+                        return None
+                elif prep._prep_type != "pixels" or s != 1 or (x.dim() == 5 and prep._temporal_downsample != 1):
+                    return None
+                if x.dim() not in (4, 5) or p >= 1.0:
+                    return None
+                t = x.shape[1] if x.dim() == 5 else 1
+                c, h, w = x.shape[-3:]
+                if not (1 <= s <= 8 and 1 <= c <= 4) or h % s or w % s or min(t, h, w) < 1:
+                    return None
+                if t * (h // s) * (w // s) != int(math.prod(prep.index_dims)):
+                    return None
+                if x.stride(-1) != 1:
+                    x = x.contiguous()
+                feats = None
+                seg.kind, seg.feature, seg.M, seg.C1 = L.PIO_TOKENS_S2D, x.data_ptr(), t * (h // s) * (w // s), s * s * c
+                seg.sb, seg.st, seg.sc, seg.sy = x.stride(0), x.stride(1) if x.dim() == 5 else 0, x.stride(-3), x.stride(-2)
+                seg.T, seg.C, seg.H, seg.W, seg.s = t, c, h, w, s
+                keep.append(x)
+            else:
+                return None
+            if feats is not None:
+                if feats.stride(2) != 1:
+                    feats = feats.contiguous()
+                seg.kind, seg.feature, seg.M, seg.C1 = L.PIO_TOKENS_ROWS, feats.data_ptr(), feats.shape[1], feats.shape[2]
+                seg.sb, seg.sm = feats.stride(0), feats.stride(1)
+                keep.append(feats)
+            if seg.M < 1 or seg.C1 < 1:
+                return None
+            if not isinstance(prep, OneHotPreprocessor):
+                if prep._concat_or_add_pos != "concat" or prep._n_extra_pos_mlp > 0:
+                    return None
+                enc = prep._positional_encoding(batch_size=batch, pos=None, device=dev).to(dev)
+                if (enc.dim() != 3 or (enc.shape[0] > 1 and enc.stride(0) != 0) or enc.shape[1] != seg.M
+                        or enc.dtype != torch.float32):
+                    return None
+                table = enc[0].detach()
+                if table.shape[1] > 0:
+                    if table.stride(1) != 1:
+                        table = table.contiguous()
+                    seg.table, seg.ldt, seg.C2 = table.data_ptr(), table.stride(0), table.shape[1]
+                    keep.append(table)
+                    deps.append(enc)
+            cp = cc - seg.C1 - seg.C2
+            if cp < 0 or (cp > 0 and self.padding_embeddings is None):
+                return None
+            params = []
+            if self.padding_embeddings is not None:
+                params.append((self.padding_embeddings[m].pos_embs, cp, "pad"))
+            if p >= 1.0:
+                params.append((self.mask_tokens[m].pos_embs, cc, "token"))
+            for w_, width, field in params:
+                if tuple(w_.shape) != (1, width) or w_.dtype != torch.float32 or w_.device != dev:
+                    return None
+                if width > 0:
+                    w_c = w_.detach().contiguous()
+                    setattr(seg, field, w_c.data_ptr())
+                    keep.append(w_c)
+                    deps.append(w_)
+            plan[m] = (seg, feats)
+            deps.append(inputs[m])
+        order = sorted(names)
+        mtot = sum(plan[m][0].M for m in order)
+        if mtot >= 2 ** 31:
+            return None
+        segs = (L.TokenSegment * len(order))()
+        row0 = 0
+        for i, m in enumerate(order):
+            plan[m][0].row0 = row0
+            segs[i] = plan[m][0]
+            row0 += plan[m][0].M
+        y = torch.empty((batch, mtot, cc), dtype=torch.float32, device=dev)
+        with R.on_device(dev):
+            L.check(L.lib().pio_assemble_tokens(segs, len(order), y.data_ptr(), cc, mtot * cc, batch, mtot, cc,
+                                                R.stream_ptr(dev)), "pio_assemble_tokens")
+        x = R.forward_only(y, *deps)
+        sizes = {m: plan[m][0].M for m in names}
+        without_pos = {}
+        for m in names:
+            seg, feats = plan[m]
+            without_pos[m] = feats if seg.token else x[:, seg.row0:seg.row0 + seg.M, :seg.C1]
+        return x, sizes, without_pos
+
     def forward(self, inputs, *, pos=None):
+        fused = self._assemble(inputs, pos)
+        if fused is not None:
+            return fused
         if self._preprocessors is None:
             outputs, without_pos = inputs, inputs
         else:

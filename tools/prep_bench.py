@@ -3,6 +3,8 @@
     python tools/prep_bench.py                  the Conv2DDownsample tail (pio_bn_relu_maxpool_tokens)
     python tools/prep_bench.py --flow-front     the flow front end (pio_flow_patch_tokens): 368 x 496 frame pairs, N = 1
                                                 and N = 4 (a test-mode tile group); prints one JSON line
+    python tools/prep_bench.py --multimodal-front   the multimodal front end (pio_assemble_tokens) at full size
+                                                ([B, 52097, 704]), B = 1 and B = 4; prints one JSON line
 """
 import argparse
 import json
@@ -104,14 +106,74 @@ def flow_front(repeats, launches):
     print(json.dumps(result))
 
 
+def multimodal_front(repeats, launches):
+    """MultimodalPreprocessor of the default MultiModalPerceiver (16 x 224 x 224 video, 30 720 audio samples, label) both
+    ways, timed with device events around `launches` back-to-back calls (after 3 warm-up calls each), `repeats` times, the
+    two alternating inside every repeat:
+      chain -- the torch ops: movedim + space_to_depth, cat with the Fourier table, cat with the padding embedding (image
+               and audio), token + 0 * x for the label, cat over the modalities
+      fused -- MultimodalPreprocessor._assemble: the output allocation + ONE pio_assemble_tokens launch
+    Reported per way: median and (min, max) of the repeats in microseconds and torch.cuda.max_memory_allocated above what
+    was allocated before the call; for the fused way also the store rate over the output's bytes."""
+    from perceiverio_pytorch_amd.models import MultiModalPerceiver
+    model = MultiModalPerceiver().to(dev).eval()
+    mp = model.perceiver._multi_preprocessor
+    with torch.no_grad():
+        for p in list(mp.padding_embeddings.parameters()) + list(mp.mask_tokens.parameters()):
+            p.normal_(0.0, 0.02)
+    result = {"tool": "tools/prep_bench.py --multimodal-front", "library": os.path.basename(
+        os.environ.get("PIO_LIB_PATH", "libpio_hip.so")), "repeats": repeats, "launches_per_repeat": launches, "unit": "us",
+        "cases": {}}
+    for b in (1, 4):
+        ins = {"image": torch.randn(b, 16, 3, 224, 224, device=dev), "audio": torch.randn(b, 30720, 1, device=dev),
+               "label": torch.zeros(b, 700, device=dev)}
+
+        def way(on):
+            def f():
+                mp.fused_assembly = on
+                return mp(ins, pos=None)[0]
+            return f
+        ways = {"chain": way(False), "fused": way(True)}
+        xa, xb = ways["chain"](), ways["fused"]()
+        assert mp._assemble(ins, None) is not None, "the fused path declined"
+        assert torch.equal(xa, xb), "chain and fused outputs differ"
+        shape = list(xa.shape)
+        del xa, xb
+        peak = {}
+        for k, f in ways.items():
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            f()
+            torch.cuda.synchronize()
+            peak[k] = torch.cuda.max_memory_allocated() - base
+        times = {k: [] for k in ways}
+        for _ in range(repeats):
+            for k, f in ways.items():
+                times[k].append(timed(f, launches))
+        case = {k: {"median": statistics.median(v), "min": min(v), "max": max(v), "peak_bytes_above_inputs": peak[k]}
+                for k, v in times.items()}
+        out_bytes = 4.0 * shape[0] * shape[1] * shape[2]
+        case["fused"]["output_bytes"] = out_bytes
+        case["fused"]["store_GB_per_s_at_median"] = out_bytes / (case["fused"]["median"] * 1e-6) / 1e9
+        case["shape"] = shape
+        result["cases"][f"B={b}"] = case
+    mp.fused_assembly = True
+    print(json.dumps(result))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--flow-front", action="store_true", help="time pio_flow_patch_tokens against the torch chain")
+    ap.add_argument("--multimodal-front", action="store_true", help="time pio_assemble_tokens against the torch chain")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--launches", type=int, default=20)
     args = ap.parse_args()
     with torch.no_grad():
         if args.flow_front:
             flow_front(args.repeats, args.launches)
+        elif args.multimodal_front:
+            multimodal_front(args.repeats, args.launches)
         else:
             conv_tail()
