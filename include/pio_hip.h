@@ -14,7 +14,12 @@
  *     mutable state is opt-in tooling, none of it thread-safe: the per-launch profiler (pio_prof_*), the logit
  *     probe (pio_logit_probe_*), the range probe (pio_range_probe_*) and the A/B switches pio_ln_fold_enable / pio_gemm_kernel_override / pio_set_cu_budget (set them before
  *     concurrent use).
- *   - scratch memory is caller-provided: query pio_*_workspace_bytes() first.
+ *   - scratch memory is caller-provided: query pio_*_workspace_bytes() first.  Its CONTENT on entry is undefined --
+ *     stale 16-bit activations, fp32 scores, key-bit words and key-split partials of an earlier, larger call, NaN
+ *     patterns included -- and no result depends on it: every pad region a kernel reads is written by its producer
+ *     inside the call, or masked by assignment.  The same holds for the caller-owned query cache of
+ *     pio_decoder_fwd_qcache while q16_valid == 0 (tests/test_workspace_stale_gpu.py runs every block entry point and
+ *     route of tests/workspace_stale_cases.py on a zeroed, a 0xFF- and a 0x7B-filled workspace, bit for bit).
  *   - tensors at the boundary are float32, last dimension contiguous; batch / row strides are given
  *     in ELEMENTS (a batch stride of 0 is a broadcast view, e.g. the latent table of
  *     position_encoding.py:117-121).

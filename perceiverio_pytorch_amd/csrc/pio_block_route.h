@@ -24,6 +24,10 @@ inline int padc(int c) { return c >= 256 ? (c + 63) & ~63 : (c + 7) & ~7; }
 // 322 does not force the GEMM epilogues and LayerNorm reads onto 4-byte accesses.  The columns [C, pitch4(C)) hold
 // zeros or stale values and are never read as data.
 inline int pitch4(int c) { return (c + 3) & ~3; }
+// Row pitch (floats) of x1, the cross-attend's fp32 result: the residual of fc2, which as the decoders' 16-bit y computes
+// all pad8(C) columns of its packed image and reads that many residual columns.  The out projection writes the columns
+// [C, pitch8(C)) as zeros in every call (n_store), so nothing there depends on what the workspace held.
+inline int pitch8(int c) { return (c + 7) & ~7; }
 
 // carve helper for caller-provided workspaces (256-byte aligned pieces)
 struct Carver {
@@ -187,7 +191,7 @@ struct CrossPlan {
         q16 = take_pair(c, (size_t)rows * padc(ca.attn.q_in), sp);
         kv16 = take_pair(c, (size_t)B * Tk * padc(ca.attn.k_in), ca.attn.act_split != 0);
         h16 = take_pair(c, (size_t)rows * padc(ca.mlp.hidden), ca.mlp.act_split != 0);
-        x1 = (float *)c.take((size_t)rows * pitch4(ca.attn.out) * 4);
+        x1 = (float *)c.take((size_t)rows * pitch8(ca.attn.out) * 4);
         core.carve(c, ca.attn, Bq, B, Tq, Tk, lean, true);
         return c.off;
     }

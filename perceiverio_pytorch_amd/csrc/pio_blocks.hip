@@ -106,8 +106,10 @@ static int linear_fwd(const pio_linear_t &lin_plain, int dtype, Pair x, int64_t 
     g.N = out_f32 ? n_logical : lin.n;
     // fp32 rows with a rounded-up pitch (pitch4: internal buffers): compute whole float4 groups -- the packed image has
     // zero rows / zero bias behind the logical ones -- so that every store and residual load is a 16-byte one
+    // (n_store16 on an fp32 result -- x1 of a cross-attend, pitch8: the columns up to it are written as zeros, so a residual
+    //  there adds nothing a caller's wider rows might hold behind the logical columns)
     if (out_f32 && (n_logical & 3) && ldc >= pitch4(n_logical) && lin.n >= pitch4(n_logical) &&
-        !(res && res->ptr && res->ld < pitch4(n_logical)))
+        !(res && res->ptr && (res->ld < pitch4(n_logical) || n_store16 > n_logical)))
         g.N = pitch4(n_logical);
     g.K = lin.k;
     g.lda = lin.k;
@@ -117,7 +119,7 @@ static int linear_fwd(const pio_linear_t &lin_plain, int dtype, Pair x, int64_t 
     g.bias_mode = lin.bias ? 1 : 0;
     g.act = act;
     g.out_f32 = out_f32 ? 1 : 0;
-    g.n_store = (!out_f32 && n_store16 > g.N) ? n_store16 : g.N;   // (16-bit rows zero-filled up to the channel pitch)
+    g.n_store = n_store16 > g.N ? n_store16 : g.N;   // (rows zero-filled up to the channel pitch / the pitch of x1)
     if (res && res->ptr && !(fold && fold->res16_hi)) {
         g.R = res->ptr;
         g.ldr = res->ld;
@@ -254,7 +256,7 @@ static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair 
                           const float *attention_bias, const Residual *res, float *out, float *probs_out,
                           AttnScratch &w, hipStream_t s, const LnFold *fold_in = nullptr,
                           const LnFold *fold_out = nullptr, int64_t out_ld = 0, const QCache *qc = nullptr) {
-    if (!out_ld) out_ld = a.out;  // row pitch of `out` (>= a.out; an internal buffer may round it up: pitch4)
+    if (!out_ld) out_ld = a.out;  // row pitch of `out` (>= a.out; an internal buffer may round it up: pitch8)
     PIO_TRY(check_attention(a));
     if (qc) {
         if (!qc->pair.hi || (a.act_split && !qc->pair.lo)) return PIO_E_ARG;
@@ -372,7 +374,7 @@ static int attention_core(const pio_attention_t &a, Pair xq, bool q_bcast, Pair 
     // final projection (+ residual) (transformer_primitives.py:110; SelfAttention :290, CrossAttention :396-399); behind
     // the K / V fold it is Wo Wv
     PIO_TRY(linear_fwd(kv_fold ? a.vo : a.o, a.dtype, w.o16, (int64_t)B * Tq, out, nullptr, true, a.out, out_ld, 0, res, s,
-                       fold_out));
+                       fold_out, out_ld > a.out ? (int)out_ld : 0));  // (an internal pitch: zeros behind the logical columns)
     if (fold_out && fold_out->out16)
         PIO_RANGE(PIO_RK_STREAM, a.dtype, fold_out->out16, (int64_t)B * Tq, a.out, fold_out->ld16, 1, 0, s);
     return PIO_OK;
@@ -392,6 +394,10 @@ static int mlp_core(const pio_mlp_t &m, Pair x, int64_t rows, Pair h, const Resi
     PIO_TRY(linear_fwd(m.fc1, m.dtype, x, rows, h.hi, h.lo, false, 0, m.fc1.n, 1, nullptr, s, fold_in));
     PIO_RANGE(PIO_RK_HIDDEN, m.dtype, h.hi, rows, m.hidden, m.fc1.n, 1, 0, s);
     if (out16) {
+        // (this GEMM computes all fc2.n = pad8(m.out) columns, so its epilogue reads that many residual columns: the
+        //  caller's residual rows have a pitch of at least pad8(m.out) and zeros behind the logical columns -- x1 of
+        //  cross_attention_run, pitch8)
+        if (res && res->ptr && res->ld < m.fc2.n) return PIO_E_SHAPE;
         PIO_TRY(linear_fwd(m.fc2, m.dtype, h, rows, out16->hi, out16->lo, false, 0, padc(m.out), 0, res, s, nullptr,
                            padc(m.out)));
         PIO_RANGE(PIO_RK_STREAM, m.dtype, out16->hi, rows, m.out, padc(m.out), 1, 0, s);
@@ -607,9 +613,9 @@ static int cross_attention_run(const pio_cross_attention_t &ca, const pio_tensor
     const Residual rq = residual_of(iq);
     PIO_TRY(attention_core(ca.attn, qa, p.q_bcast, p.kv16, p.kv16, B, Tq, Tk, kv_mask, q_mask, full_mask,
                            attention_bias, ca.use_query_residual ? &rq : nullptr, p.x1, probs_out, p.core, s, nullptr,
-                           nullptr, pitch4(q_c), qc));
+                           nullptr, pitch8(q_c), qc));
     // x + MLP(LN2(x))  (transformer_primitives.py:401)
-    pio_tensor3_t t1 = {p.x1, (int64_t)Tq * pitch4(q_c), pitch4(q_c), B, Tq, q_c};
+    pio_tensor3_t t1 = {p.x1, (int64_t)Tq * pitch8(q_c), pitch8(q_c), B, Tq, q_c};
     const Pair qm = pair_if(p.q16, ca.mlp.act_split);
     PIO_TRY(cast_pair(t1, &ca.ln2, qm, padc(q_c), ca.mlp.dtype, s));
     const Residual r1 = residual_of(t1);

@@ -403,18 +403,18 @@ PLANS = {
         "core.xpart=16777216 split=0 qbytes=2097152 kbytes=2097152 x16b=0 lo_a=25690880 lo_b=25690880 "
         "part_a=27788032 part_b=27935488",
     "flow_decoder_322":
-        "total=2074419456 null_base_total=2074419456 y=0 y16.hi=236556288 y16.lo=376737792 q16.hi=516919296 "
+        "total=2077339904 null_base_total=2077339904 y=0 y16.hi=236556288 y16.lo=376737792 q16.hi=516919296 "
         "q16.lo=657100800 kv16.hi=797282304 kv16.lo=799379456 h16.hi=801476608 h16.lo=941658112 x1=1081839616 "
-        "core.q16.hi=1318395904 core.q16.lo=1505304576 core.k16.hi=1692213248 core.k16.lo=1694310400 "
-        "core.vt16.hi=1696407552 core.vt16.lo=1698504704 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 "
-        "core.o16.hi=1700601856 core.o16.lo=1887510528 core.xpart=2074419200 split=1 qbytes=186908672 "
+        "core.q16.hi=1321316352 core.q16.lo=1508225024 core.k16.hi=1695133696 core.k16.lo=1697230848 "
+        "core.vt16.hi=1699328000 core.vt16.lo=1701425152 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 "
+        "core.o16.hi=1703522304 core.o16.lo=1890430976 core.xpart=2077339648 split=1 qbytes=186908672 "
         "kbytes=2097152 pitch4=324 pad8=328 padc=384 y16_direct=1 y16_switched_off=0",
     "flow_decoder_322_no_final":
-        "total=1557500160 null_base_total=1557500160 y=-1 y16.hi=-1 y16.lo=-1 q16.hi=0 q16.lo=140181504 "
+        "total=1560420608 null_base_total=1560420608 y=-1 y16.hi=-1 y16.lo=-1 q16.hi=0 q16.lo=140181504 "
         "kv16.hi=280363008 kv16.lo=282460160 h16.hi=284557312 h16.lo=424738816 x1=564920320 "
-        "core.q16.hi=801476608 core.q16.lo=988385280 core.k16.hi=1175293952 core.k16.lo=1177391104 "
-        "core.vt16.hi=1179488256 core.vt16.lo=1181585408 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 "
-        "core.o16.hi=1183682560 core.o16.lo=1370591232 core.xpart=1557499904 split=1 qbytes=186908672 "
+        "core.q16.hi=804397056 core.q16.lo=991305728 core.k16.hi=1178214400 core.k16.lo=1180311552 "
+        "core.vt16.hi=1182408704 core.vt16.lo=1184505856 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 "
+        "core.o16.hi=1186603008 core.o16.lo=1373511680 core.xpart=1560420352 split=1 qbytes=186908672 "
         "kbytes=2097152 pitch4=324 pad8=328 padc=384 y16_direct=0 y16_switched_off=0",
     "multimodal_cross":
         "total=254310144 null_base_total=254310144 q16.hi=0 q16.lo=-1 kv16.hi=802816 kv16.lo=-1 "
@@ -428,18 +428,18 @@ PLANS = {
         "core.xpart=6438912 split=0 qbytes=802816 kbytes=802816 x16b=0 lo_a=11407104 lo_b=11407104 "
         "part_a=12209920 part_b=12266496",
     "multimodal_decoder_1026":
-        "total=203199232 null_base_total=203199232 y=0 y16.hi=25856256 y16.lo=39538944 q16.hi=53221632 "
+        "total=203299840 null_base_total=203299840 y=0 y16.hi=25856256 y16.lo=39538944 q16.hi=53221632 "
         "q16.lo=66904320 kv16.hi=80587008 kv16.lo=81389824 h16.hi=82192640 h16.lo=95875328 x1=109558016 "
-        "core.q16.hi=135414272 core.q16.lo=141853184 core.k16.hi=148292096 core.k16.lo=149094912 "
-        "core.vt16.hi=149897728 core.vt16.lo=150716928 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 "
-        "core.o16.hi=151536128 core.o16.lo=157975040 core.xpart=164413952 split=1 qbytes=6438912 "
+        "core.q16.hi=135514880 core.q16.lo=141953792 core.k16.hi=148392704 core.k16.lo=149195520 "
+        "core.vt16.hi=149998336 core.vt16.lo=150817536 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 "
+        "core.o16.hi=151636736 core.o16.lo=158075648 core.xpart=164514560 split=1 qbytes=6438912 "
         "kbytes=802816 pitch4=1028 pad8=1032 padc=1088 y16_direct=1 y16_switched_off=0",
     "multimodal_decoder_1026_no_final":
-        "total=149977600 null_base_total=149977600 y=-1 y16.hi=-1 y16.lo=-1 q16.hi=0 q16.lo=13682688 "
-        "kv16.hi=27365376 kv16.lo=28168192 h16.hi=28971008 h16.lo=42653696 x1=56336384 core.q16.hi=82192640 "
-        "core.q16.lo=88631552 core.k16.hi=95070464 core.k16.lo=95873280 core.vt16.hi=96676096 "
-        "core.vt16.lo=97495296 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 core.o16.hi=98314496 "
-        "core.o16.lo=104753408 core.xpart=111192320 split=1 qbytes=6438912 kbytes=802816 pitch4=1028 "
+        "total=150078208 null_base_total=150078208 y=-1 y16.hi=-1 y16.lo=-1 q16.hi=0 q16.lo=13682688 "
+        "kv16.hi=27365376 kv16.lo=28168192 h16.hi=28971008 h16.lo=42653696 x1=56336384 core.q16.hi=82293248 "
+        "core.q16.lo=88732160 core.k16.hi=95171072 core.k16.lo=95973888 core.vt16.hi=96776704 "
+        "core.vt16.lo=97595904 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 core.o16.hi=98415104 "
+        "core.o16.lo=104854016 core.xpart=111292928 split=1 qbytes=6438912 kbytes=802816 pitch4=1028 "
         "pad8=1032 padc=1088 y16_direct=0 y16_switched_off=0",
     "self_512_act_split_0":
         "total=17375488 null_base_total=17375488 x16.hi=0 x16.lo=-1 h16.hi=16252928 h16.lo=-1 x1=1048576 "

@@ -19,6 +19,8 @@ TIGHT = 5e-5        # what the default policy (fp16x3: split operands, ~fp32 pro
 # channels) that alone is ~1e-3 per few layers, so for THEM the bound asserted is the error budget below; on
 # every realistically sized golden (and on the headline ImageNet config) they are held to TOL as well.
 FAST_TOY_BUDGET = 3e-3
+BF16_FUSED_TOL = 1e-2    # "bf16" through a fused attention core against the oracle (toy widths)
+PROBS_ABS_TOL = 1e-5     # returned probability matrix under "fp16x3": largest absolute difference
 POLICIES = ["fp16x3", "fp16x2w", "fp16x2s", "fp16"]
 # goldens whose widths are those of real configurations (>= 256 channels, or the 322-wide single head, >= 45 keys)
 REALISTIC = {"sa_mid_512x256_h8", "attn_h1_dim322", "ca_keymask", "encdec_mid", "encdec_lang_like",
@@ -514,7 +516,7 @@ def test_attention_return_matrix_and_bias(dev):
     rm, ry = O.attention(p64, g["xq"].astype(np.float64), g["xkv"].astype(np.float64), g["xkv"].astype(np.float64),
                          H, mask, bias.astype(np.float64), return_matrix=True)
     _assert_close(y, ry, TIGHT, what="attention with bias")
-    assert np.abs(pm.cpu().numpy() - rm).max() <= 1e-5
+    assert np.abs(pm.cpu().numpy() - rm).max() <= PROBS_ABS_TOL
 
 
 FLASH_CASES = [
@@ -548,7 +550,7 @@ def test_fused_attention_vs_oracle(dev, case, policy):
     ref = O.attention(p64, xq.astype(np.float64), xkv.astype(np.float64), xkv.astype(np.float64), H)
     _policy(policy)
     y = m(_t(xq, dev), _t(xkv, dev), _t(xkv, dev))
-    _assert_close(y, ref, TOL if policy != "bf16" else 1e-2, what=f"fused attention {case} {policy}")
+    _assert_close(y, ref, TOL if policy != "bf16" else BF16_FUSED_TOL, what=f"fused attention {case} {policy}")
     # a spiky query row forces large running-max jumps between key tiles (the online-softmax rescale branch);
     # compare the fused kernel with the materialised-score path of the SAME policy (return_matrix forces it):
     # identical operand rounding, different algorithm.
