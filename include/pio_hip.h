@@ -385,6 +385,51 @@ typedef struct pio_token_segment_t {
 int pio_assemble_tokens(const pio_token_segment_t *segs, int32_t nseg, float *y, int64_t ldy, int64_t sYb, int32_t B,
                         int32_t Mtot, int32_t Cc, void *stream);
 
+/* One segment of the decoder query array: rows [row0, row0 + M) of y [Qtot, Cq].
+ * kind PIO_QUERY_FOURIER: Fourier features of M index points of a d-dimensional grid (1 <= d <= 3) of sizes dims[0 : d]
+ *   (output_queries.py BasicQuery._encode, position_encoding.py generate_fourier_features).  Row m:
+ *     i = (points ? points[m] : start + m) mod prod(dims)   (the non-negative remainder, as unravel_index takes it),
+ *     (coord_0, .., coord_{d-1}) the row-major unravel of i,  p_j = axis[j][coord_j]   (axis[j]: dims[j] floats),
+ *     phase(j, k) = fmul_rn(fmul_rn(p_j, bands[j*ldb + k]), (float)M_PI)   (two separately rounded fp32 products),
+ *   with c0 = concat_pos ? d : 0 and width = c0 + d*K*(sine_only ? 1 : 2):
+ *     x[0 : d]               = p_j                 (concat_pos only)
+ *     x[c0 + j*K + k]        = sinf(phase(j, k))
+ *     x[c0 + d*K + j*K + k]  = cosf(phase(j, k))   (unless sine_only)
+ *     x[width : Cq]          = pad[0 : Cq - width]
+ *   bands: [d, K] with row pitch ldb >= K (K for a dense table).  The caller builds axis and bands with the host arithmetic
+ *   of the chain it replaces (-1 + 2 * index / size; linspace(1, res / 2, K)).
+ * kind PIO_QUERY_TABLE: x[0 : C] = table[m*ldt : m*ldt + C],  x[C : Cq] = pad[0 : Cq - C]   (width = C).
+ * pad may be NULL where width == Cq, table where C == 0; axis[j] for j >= d, points, and the other kind's fields are not read. */
+enum { PIO_QUERY_FOURIER = 0, PIO_QUERY_TABLE = 1 };
+#define PIO_MAX_QUERY_SEGMENTS 4
+typedef struct pio_query_segment_t {
+    const float *axis[3];
+    const float *bands;
+    const int64_t *points;
+    const float *table;
+    const float *pad;
+    int64_t start, ldb, ldt; /* first index when points == NULL; row pitches of bands and table in elements */
+    int32_t kind;            /* PIO_QUERY_FOURIER / PIO_QUERY_TABLE */
+    int32_t row0, M;
+    int32_t d, dims[3], K, concat_pos, sine_only;
+    int32_t C;
+} pio_query_segment_t;
+
+/* The decoder queries of a multi-modality model (PerceiverIO.decoder_query: per modality position encoding | padding
+ * embedding, concatenated over the modalities) as ONE launch: nseg (1 .. 4) segments fill their rows of the batch-invariant
+ * y [Qtot, Cq] fp32 (row pitch ldy).  Every element is stored once; rows no segment covers and the columns [Cq, ldy) are not
+ * written.  Position, table and padding channels are moves; sine and cosine are the device library's accurate sincosf / sinf
+ * of the phase above.  Rows leave as 16-byte vectors when Cq % 4 == 0, ldy % 4 == 0 and y is 16-byte aligned, as 8-byte
+ * vectors when that holds with 2 and 8 (Cq = 1026), as dwords otherwise.  No workspace, no device allocation, no
+ * synchronisation.
+ * PIO_E_ARG: NULL segs / y, nseg outside [1, 4], an unknown kind, d outside [1, 3], K < 1, a NULL bands / axis[j < d] /
+ * table (C > 0) pointer, a NULL pad where width < Cq; PIO_E_SHAPE: Qtot, Cq, M <= 0, ldy < Cq, dims[j] < 1 or prod(dims) >=
+ * 2^31, ldb < K, C < 0, ldt < C, width > Cq, 32 feature rows (d*K*(sine_only ? 1 : 2) floats each) beyond 64 KiB of LDS
+ * (d*K <= 247 with cosines, 487 without), a segment outside [0, Qtot), two segments that overlap; PIO_E_ALIGN: a float pointer not 4-byte
+ * aligned, points not 8-byte aligned.  A refused call launches nothing. */
+int pio_build_queries(const pio_query_segment_t *segs, int32_t nseg, float *y, int64_t ldy, int32_t Qtot, int32_t Cq,
+                      void *stream);
+
 /* C = epilogue(alpha * A B^T): A [M,K], B [N,K] operand dtype, K contiguous (multiple of 8).
  * Batched over z = zb*nh + zh with element strides; bias_mode 0 none / 1 per column / 2 per row;
  * act 0 none / 1 exact-erf GELU (F.gelu, transformer_primitives.py:214); optional fp32 residual R

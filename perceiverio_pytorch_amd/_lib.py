@@ -85,6 +85,19 @@ class TokenSegment(C.Structure):
                 ("s", C.c_int32)]
 
 
+PIO_QUERY_FOURIER = 0
+PIO_QUERY_TABLE = 1
+PIO_MAX_QUERY_SEGMENTS = 4
+
+
+class QuerySegment(C.Structure):
+    """pio_query_segment_t: one row segment of pio_build_queries (Fourier features of index points, or a table | padding)."""
+    _fields_ = [("axis", C.c_void_p * 3), ("bands", C.c_void_p), ("points", C.c_void_p), ("table", C.c_void_p),
+                ("pad", C.c_void_p), ("start", C.c_int64), ("ldb", C.c_int64), ("ldt", C.c_int64), ("kind", C.c_int32),
+                ("row0", C.c_int32), ("M", C.c_int32), ("d", C.c_int32), ("dims", C.c_int32 * 3), ("K", C.c_int32),
+                ("concat_pos", C.c_int32), ("sine_only", C.c_int32), ("C", C.c_int32)]
+
+
 class Gemm(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("A_lo", C.c_void_p), ("B_lo", C.c_void_p), ("C", C.c_void_p),
                 ("C_lo", C.c_void_p),
@@ -136,6 +149,7 @@ SIGNATURES = {
     "pio_flow_patch_tokens": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32,
                                         _i32, _i32, _vp]),
     "pio_assemble_tokens": (C.c_int, [P(TokenSegment), _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "pio_build_queries": (C.c_int, [P(QuerySegment), _i32, _vp, _i64, _i32, _i32, _vp]),
     "pio_gemm_nt": (C.c_int, [P(Gemm), _vp]),
     "pio_softmax_rows": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f, _vp, _vp, _vp, _vp, _i32, _vp]),
     "pio_flash_attention": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64,

@@ -208,6 +208,11 @@ int pio_assemble_tokens(const pio_token_segment_t *segs, int32_t nseg, float *y,
     return assemble_tokens_launch(segs, nseg, y, ldy, sYb, B, Mtot, Cc, (hipStream_t)stream);
 }
 
+int pio_build_queries(const pio_query_segment_t *segs, int32_t nseg, float *y, int64_t ldy, int32_t Qtot, int32_t Cq,
+                      void *stream) {
+    return build_queries_launch(segs, nseg, y, ldy, Qtot, Cq, (hipStream_t)stream);
+}
+
 int pio_gemm_nt(const pio_gemm_t *g, void *stream) {
     if (!g) return PIO_E_ARG;
     return gemm_nt_launch(*g, (hipStream_t)stream);

@@ -139,6 +139,8 @@ int flow_patch_tokens_launch(const float *f0, const float *f1, int64_t sn0, int6
 // multimodal front end: features | position table | padding embedding (| mask token) of up to 8 row segments in one launch
 int assemble_tokens_launch(const pio_token_segment_t *segs, int nseg, float *y, int64_t ldy, int64_t sYb, int B, int Mtot,
                            int Cc, hipStream_t s);
+// decoder queries: Fourier features of index points | learned table, each with its padding embedding, up to 4 row segments
+int build_queries_launch(const pio_query_segment_t *segs, int nseg, float *y, int64_t ldy, int Qtot, int Cq, hipStream_t s);
 int pack_linear_launch(const float *w, const float *bias, int out, int in, int64_t ldw, int row_heads,
                        int col_heads, void *dst_hi, void *dst_lo, float *dst_bias, int dst_row0, int k_pad,
                        int dtype, hipStream_t s);

@@ -379,6 +379,18 @@ class MultiModalPerceiver(nn.Module):
     def fused_front_end(self, on: bool) -> None:
         self.perceiver._multi_preprocessor.fused_assembly = bool(on)
 
+    # The decoder query array of a chunk group -- Fourier features of the audio and video index points, the learned label
+    # query, the three padding embeddings -- comes from ONE HIP launch as well (PerceiverIO.fused_queries ->
+    # pio_build_queries) under the hip backend on a GPU; False restores the chain of torch ops.  Moves are the same bits
+    # either way, sines and cosines agree to the device math library's accuracy.
+    @property
+    def fused_queries(self) -> bool:
+        return self.perceiver.fused_queries
+
+    @fused_queries.setter
+    def fused_queries(self, on: bool) -> None:
+        self.perceiver.fused_queries = bool(on)
+
     def forward(self, images: torch.Tensor, audio: torch.Tensor, n_chunks: int = 128):
         with _policy_scope(self):
             return self._forward(images, audio, n_chunks)

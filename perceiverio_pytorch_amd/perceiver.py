@@ -616,9 +616,119 @@ class PerceiverIO(nn.Module):
                 and not self._decoder._use_query_residual and self.decoder_query_rows is None
                 and q.n_query_channels() == self.query_channels)
 
+    # One HIP launch (pio_build_queries) instead of the chain of torch ops in decoder_query, for a multi-modality model whose
+    # queries depend on parameters and constants only: see _fused_decoder_query.  False, and every configuration it
+    # declines, runs the chain exactly as before.
+    fused_queries = True
+
+    def _query_tables(self, name, enc, device):
+        """(axis tables, bands [d, K]) of a Fourier query on `device`, built once per module and device with the chain's own
+        arithmetic: axis[j][i] = -1 + 2 * i / dims[j] as BasicQuery._encode computes it (int64 -> fp32 division on that
+        device), bands from the torch.linspace calls of generate_fourier_features."""
+        store = self.__dict__.setdefault("_query_table_cache", {})
+        key = (name, str(device))
+        hit = store.get(key)
+        if hit is None:
+            with torch.no_grad():
+                axes = [(-1 + 2 * torch.arange(int(n), device=device) / torch.tensor(int(n), device=device)).contiguous()
+                        for n in enc._index_dims]
+                bands = torch.stack([torch.linspace(1.0, res / 2, steps=enc._num_bands) for res in enc._max_resolution],
+                                    dim=0).to(device).contiguous()
+            hit = store[key] = (axes, bands)
+        return hit
+
+    def _fused_decoder_query(self, inputs, subsampled_points):
+        """(query, sizes) of decoder_query from ONE pio_build_queries call, or None.  Taken under the hip backend on a CUDA
+        device for two to four output queries, every one a BasicQuery with concat_preprocessed_input=False over either an
+        unprojected FourierPositionEncoding (d <= 3) with a 1-D int64 `subsampled_points` tensor on that device, or a
+        TrainablePositionEncoding (fp32) without points; at least one Fourier; fp32 padding embeddings.  The array is
+        batch-invariant: ONE [1, Q, Cq] allocation returned as a stride-0 view over the batch (the decoder projects such
+        views once).  Position, table and padding channels equal the chain's bit for bit, sine / cosine to the device
+        library's accuracy."""
+        from .output_queries import BasicQuery
+        from .position_encoding import FourierPositionEncoding
+        if not self.fused_queries or R.get_backend() != "hip" or not isinstance(inputs, torch.Tensor) or not inputs.is_cuda:
+            return None
+        names = list(self._output_queries.keys())
+        if not 2 <= len(names) <= L.PIO_MAX_QUERY_SEGMENTS:
+            return None
+        dev, cq = inputs.device, self.query_channels
+        plan, keep, deps, n_fourier = {}, [], [], 0
+        for m in names:
+            q = self._output_queries[m]
+            if not isinstance(q, BasicQuery) or q._concat_preprocessed_input:
+                return None
+            enc, points = q._position_encoding, subsampled_points.get(m)
+            seg = L.QuerySegment()
+            if type(enc) is FourierPositionEncoding:
+                dims, d, k = tuple(enc._index_dims), len(enc._index_dims), int(enc._num_bands)
+                if (not 1 <= d <= 3 or len(enc._max_resolution) != d or k < 1 or min(dims) < 1
+                        or math.prod(dims) >= 2 ** 31):
+                    return None
+                if (not isinstance(points, torch.Tensor) or points.dim() != 1 or points.dtype != torch.int64
+                        or points.device != dev or points.numel() < 1):
+                    return None
+                feats = d * k * (1 if enc._sine_only else 2)
+                if 4 * (288 + d * k + 32 * feats) > 65536:      # (a strip's feature rows have to fit the kernel's LDS)
+                    return None
+                axes, bands = self._query_tables(m, enc, dev)
+                if points.stride(0) != 1:
+                    points = points.contiguous()
+                seg.kind, seg.M, seg.d, seg.K, seg.ldb = L.PIO_QUERY_FOURIER, points.numel(), d, k, bands.stride(0)
+                seg.concat_pos, seg.sine_only = int(bool(enc._concat_pos)), int(bool(enc._sine_only))
+                for j in range(d):
+                    seg.dims[j], seg.axis[j] = dims[j], axes[j].data_ptr()
+                seg.bands, seg.points = bands.data_ptr(), points.data_ptr()
+                width = enc.n_output_channels()
+                keep.append(points)
+                n_fourier += 1
+            elif type(enc) is TrainablePositionEncoding:
+                w = enc.pos_embs
+                if points is not None or w.dim() != 2 or w.dtype != torch.float32 or w.device != dev or w.shape[0] < 1:
+                    return None
+                table = w.detach()
+                if table.shape[1] > 0 and table.stride(1) != 1:
+                    table = table.contiguous()
+                seg.kind, seg.M, seg.C, seg.ldt = L.PIO_QUERY_TABLE, table.shape[0], table.shape[1], table.stride(0)
+                seg.table = table.data_ptr() if table.shape[1] > 0 else None
+                width = table.shape[1]
+                keep.append(table)
+                deps.append(w)
+            else:
+                return None
+            pad = self.padding_embeddings[m].pos_embs
+            if (width != q.n_query_channels() or tuple(pad.shape) != (1, cq - width) or pad.dtype != torch.float32
+                    or pad.device != dev):
+                return None
+            if cq > width:
+                pad_c = pad.detach().contiguous()
+                seg.pad = pad_c.data_ptr()
+                keep.append(pad_c)
+                deps.append(pad)
+            plan[m] = seg
+        qtot = sum(plan[m].M for m in names)
+        if n_fourier < 1 or qtot >= 2 ** 31:
+            return None
+        order = sorted(names)
+        segs = (L.QuerySegment * len(order))()
+        row0 = 0
+        for i, m in enumerate(order):
+            plan[m].row0 = row0
+            segs[i] = plan[m]
+            row0 += plan[m].M
+        y = torch.empty((1, qtot, cq), dtype=torch.float32, device=dev)
+        with R.on_device(dev):
+            L.check(L.lib().pio_build_queries(segs, len(order), y.data_ptr(), cq, qtot, cq, R.stream_ptr(dev)),
+                    "pio_build_queries")
+        y = R.forward_only(y, *deps)
+        return torch.broadcast_to(y, (inputs.shape[0], qtot, cq)), {m: plan[m].M for m in names}
+
     def decoder_query(self, inputs, modality_sizes, inputs_without_pos=None, subsampled_points=None):
         per_mod = restructure(modality_sizes, inputs)
         subsampled_points = subsampled_points or {}
+        fused = self._fused_decoder_query(inputs, subsampled_points)
+        if fused is not None:
+            return fused
         any_input = next(iter(per_mod.values()))
         queries = {}
         for m, make_query in self._output_queries.items():

@@ -5,6 +5,10 @@
                                                 and N = 4 (a test-mode tile group); prints one JSON line
     python tools/prep_bench.py --multimodal-front   the multimodal front end (pio_assemble_tokens) at full size
                                                 ([B, 52097, 704]), B = 1 and B = 4; prints one JSON line
+    python tools/prep_bench.py --decoder-queries    the multimodal decoder queries (pio_build_queries) at full size: one
+                                                16-chunk group [1, 100593, 1026] and the 8 groups of a 128-chunk forward,
+                                                the sine / cosine error of chain and kernel over tests/query_cases.py, and
+                                                the whole model with and without the query cache; prints one JSON line
 """
 import argparse
 import json
@@ -163,10 +167,154 @@ def multimodal_front(repeats, launches):
     print(json.dumps(result))
 
 
+def _query_errors():
+    """Largest |value - float64 sine / cosine of the fp32 phase| over the cases of tests/query_cases.py: the torch chain
+    (FourierQuery on this device) and pio_build_queries, each case's bands being torch.linspace's."""
+    sys.path[:0] = [os.path.join(ROOT, "tests")]
+    import numpy as np
+    import query_cases as QC
+    from perceiverio_pytorch_amd import _lib as L
+    from perceiverio_pytorch_amd.output_queries import FourierQuery
+    from test_queries_host import build_queries
+    worst = {"chain": 0.0, "kernel": 0.0}
+    per_case = {}
+    for name, c in QC.CASES.items():
+        bands = {i: torch.stack([torch.linspace(1.0, r / 2, steps=g["K"]) for r in g["res"]]).numpy()
+                 for i, g in enumerate(c["segs"]) if g["kind"] == QC.FOURIER}
+        data = QC.gen(name, bands)
+        ref = QC.reference(name, data)
+        held = {(i, w): torch.from_numpy(d[w + "_full"]).to(dev) for i, d in enumerate(data) for w in QC.POINTER_FIELDS
+                if d[w + "_full"] is not None}
+        segs, args = QC.call_fields(name, data, lambda i, w: held[(i, w)].data_ptr())
+        y = torch.full((c["Qtot"], c["ldy"]), float("nan"), device=dev)
+        L.check(build_queries(L, segs, y.data_ptr(), args, torch.cuda.current_stream().cuda_stream), name)
+        chain = np.full(ref[0].shape, np.nan, dtype=np.float32)
+        for g in c["segs"]:
+            rows = slice(g["row0"], g["row0"] + g["M"])
+            if g["kind"] == QC.FOURIER:
+                q = FourierQuery(output_index_dims=g["dims"], num_bands=g["K"], max_resolution=g["res"],
+                                 sine_only=g["sine_only"], concat_pos=g["concat_pos"])
+                pts = torch.from_numpy(g["points"]) if g["points"] is not None else torch.arange(g["start"], g["start"] + g["M"])
+                chain[rows, :g["width"]] = q(torch.zeros(1, 1, 1, device=dev), subsampled_points=pts.to(dev))[0].cpu().numpy()
+                chain[rows, g["width"]:c["Cq"]] = ref[0][rows, g["width"]:c["Cq"]]
+            else:
+                chain[rows, :c["Cq"]] = ref[0][rows, :c["Cq"]]
+        per_case[name] = {"max_abs_phase_rad": QC.max_phase(name, data),
+                          "chain": QC.compare(chain, ref, name + " chain", bound=1.0),
+                          "kernel": QC.compare(y.cpu().numpy(), ref, name + " kernel", bound=1.0)}
+        for k in worst:
+            worst[k] = max(worst[k], per_case[name][k])
+    return {"reference": "float64 sine / cosine of the fp32 phase; position, table and padding channels bit-identical",
+            "chain": worst["chain"], "kernel": worst["kernel"], "bound_in_tests": 2 * worst["chain"], "per_case": per_case}
+
+
+def decoder_queries(repeats, launches):
+    """The decoder query array of the default MultiModalPerceiver both ways, timed like multimodal_front:
+      chain -- PerceiverIO.decoder_query's torch ops (unravel_index, division, the [n, d, K] product, sin, cos, three cats)
+      fused -- PerceiverIO._fused_decoder_query: the output allocation + ONE pio_build_queries launch
+    for one 16-chunk group (Q = 100 593) and for the 8 groups of a 128-chunk forward; then the whole model: the first forward
+    of a fresh model, and the steady step with cache_queries=False both ways beside the cached step."""
+    import time
+    from perceiverio_pytorch_amd.models import MultiModalPerceiver
+    result = {"tool": "tools/prep_bench.py --decoder-queries", "repeats": repeats, "launches_per_repeat": launches,
+              "unit": "us", "cases": {}}
+    import contextlib
+    with contextlib.redirect_stdout(sys.stderr):         # (the comparison prints each case's figure)
+        result["sincos_error"] = _query_errors()
+    model = MultiModalPerceiver().to(dev).eval()
+    P = model.perceiver
+    with torch.no_grad():
+        for p in P.padding_embeddings.parameters():
+            p.normal_(0.0, 0.02)
+    n_chunks, g = 128, model.decode_chunks_per_call
+    img_chunk, aud_chunk = 16 * 224 * 224 // n_chunks, 30720 // 16 // n_chunks
+    x, sizes = torch.zeros((1, 6, 1), device=dev), {"audio": 2, "image": 2, "label": 2}
+
+    def points(k):
+        return {"image": torch.arange(img_chunk * k, img_chunk * (k + g), device=dev),
+                "audio": torch.arange(aud_chunk * k, aud_chunk * (k + g), device=dev), "label": None}
+    groups = [points(k) for k in range(0, n_chunks, g)]
+
+    def way(on, pts):
+        def f():
+            P.fused_queries = on
+            q = None
+            for p in pts:
+                q = P.decoder_query(x, sizes, None, subsampled_points=p)[0]
+            return q
+        return f
+    for label, pts in (("one 16-chunk group", groups[:1]), ("128-chunk forward (8 groups)", groups)):
+        ways = {"chain": way(False, pts), "fused": way(True, pts)}
+        qa, qb = ways["chain"](), ways["fused"]()
+        assert P._fused_decoder_query(x, pts[0]) is not None, "the fused path declined"
+        shape = list(qa.shape)
+        diff = float((qa - qb).abs().max())
+        del qa, qb
+        peak = {}
+        for k, f in ways.items():
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            f()
+            torch.cuda.synchronize()
+            peak[k] = torch.cuda.max_memory_allocated() - base
+        times = {k: [] for k in ways}
+        for _ in range(repeats):
+            for k, f in ways.items():
+                times[k].append(timed(f, launches))
+        case = {k: {"median": statistics.median(v), "min": min(v), "max": max(v), "peak_bytes_above_inputs": peak[k]}
+                for k, v in times.items()}
+        out_bytes = 4.0 * shape[1] * shape[2] * len(pts)
+        for k in case:
+            case[k]["store_GB_per_s_at_median"] = out_bytes / (case[k]["median"] * 1e-6) / 1e9
+        case.update(shape=shape, arrays=len(pts), output_bytes=out_bytes, max_abs_chain_minus_fused=diff)
+        result["cases"][label] = case
+    del model, P, groups
+    torch.cuda.empty_cache()
+
+    gen = torch.Generator().manual_seed(7)
+    images = torch.rand(1, 16, 3, 224, 224, generator=gen).to(dev)
+    audio = (torch.rand(1, 30720, 1, generator=gen) * 2 - 1).to(dev)
+
+    def wall(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+    whole = {"unit": "ms", "steps": 5}
+    with torch.inference_mode():                         # (one forward of a throw-away model: the process's one-time costs --
+        warm = MultiModalPerceiver().to(dev).eval()      #  code objects loaded on first use -- belong to neither way)
+        warm(images, audio)
+        del warm
+    torch.cuda.empty_cache()
+    for k, on in (("chain", False), ("fused", True)):
+        torch.manual_seed(3)
+        m = MultiModalPerceiver().to(dev).eval()
+        m.fused_queries = on
+        with torch.inference_mode():
+            m.cache_queries = False
+            cold = wall(lambda: m(images, audio))       # (weight packing and workspaces included, the same both ways)
+            uncached = [wall(lambda: m(images, audio)) for _ in range(5)]
+            m.cache_queries = True
+            first_cached = wall(lambda: m(images, audio))
+            cached = [wall(lambda: m(images, audio)) for _ in range(5)]
+        whole[k] = {"cold_first_forward": cold, "step_cache_queries_False": statistics.median(uncached),
+                    "step_cache_queries_False_min_max": [min(uncached), max(uncached)],
+                    "first_forward_filling_the_cache": first_cached, "step_cached": statistics.median(cached),
+                    "step_cached_min_max": [min(cached), max(cached)]}
+        del m
+        torch.cuda.empty_cache()
+    result["whole_model_B1_128_chunks"] = whole
+    print(json.dumps(result))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--flow-front", action="store_true", help="time pio_flow_patch_tokens against the torch chain")
     ap.add_argument("--multimodal-front", action="store_true", help="time pio_assemble_tokens against the torch chain")
+    ap.add_argument("--decoder-queries", action="store_true", help="time pio_build_queries against the torch chain")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--launches", type=int, default=20)
     args = ap.parse_args()
@@ -175,5 +323,7 @@ if __name__ == "__main__":
             flow_front(args.repeats, args.launches)
         elif args.multimodal_front:
             multimodal_front(args.repeats, args.launches)
+        elif args.decoder_queries:
+            decoder_queries(args.repeats, args.launches)
         else:
             conv_tail()
