@@ -430,6 +430,26 @@ typedef struct pio_query_segment_t {
 int pio_build_queries(const pio_query_segment_t *segs, int32_t nseg, float *y, int64_t ldy, int32_t Qtot, int32_t Cq,
                       void *stream);
 
+/* The language front end (io_processors.py EmbeddingPreprocessor: embed(ids) + learned position embedding) as ONE launch.
+ * ids [B, T] int32 (id_bytes 4) or int64 (id_bytes 8), t contiguous, sample stride ids_sb elements; table [V, C] fp32 (row
+ * pitch ldt); pos [T, C] fp32 (row pitch ldp); y [B, T, C] fp32 (row pitch ldy, sample stride y_sb); tokens: optional
+ * (NULL) second output of the same shape with its own ldtok / tok_sb.  Sample strides are not read when B == 1.  Per
+ * (b, t, c), with id = ids[b*ids_sb + t]:
+ *   0 <= id < V:  y = fadd_rn(table[id*ldt + c], pos[t*ldp + c])  (one rounded fp32 add: the bits of `embed(ids) + pos`),
+ *                 tokens = table[id*ldt + c];
+ *   otherwise:    y and tokens are quiet NaN in all C channels of that row, no table row is read, and bad_ids[0] = 1 where
+ *                 bad_ids (optional, a device int32) is given.  The range test is made on the full-width id.  The call never
+ *                 clears the word and never reads it: the caller zeroes it on the stream before the call and reads it later.
+ * Only the C channels of each of the B*T rows are written: [C, ld) and everything else stays untouched.  Rows leave as
+ * 16-byte vectors when C, every pitch and (B > 1) every sample stride of a float array are multiples of 4 and table, pos, y
+ * and tokens are 16-byte aligned; as dwords otherwise.  No workspace, no device allocation, no synchronisation.
+ * PIO_E_ARG: NULL ids / table / pos / y, id_bytes not 4 or 8, ids not aligned to id_bytes, table / pos / y / tokens /
+ * bad_ids not 4-byte aligned; PIO_E_SHAPE: B, T, C or V < 1, a pitch below C, for B > 1 ids_sb < T or y_sb < T*ldy or
+ * tok_sb < T*ldtok, tokens == y, B * ceil(T / 32) workgroups beyond 2^31 - 1.  A refused call launches nothing. */
+int pio_embed_tokens(const void *ids, int32_t id_bytes, int64_t ids_sb, const float *table, int64_t ldt, int32_t V,
+                     const float *pos, int64_t ldp, float *y, int64_t y_sb, int64_t ldy, float *tokens, int64_t tok_sb,
+                     int64_t ldtok, int32_t *bad_ids, int32_t B, int32_t T, int32_t C, void *stream);
+
 /* C = epilogue(alpha * A B^T): A [M,K], B [N,K] operand dtype, K contiguous (multiple of 8).
  * Batched over z = zb*nh + zh with element strides; bias_mode 0 none / 1 per column / 2 per row;
  * act 0 none / 1 exact-erf GELU (F.gelu, transformer_primitives.py:214); optional fp32 residual R

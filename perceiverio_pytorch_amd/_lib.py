@@ -150,6 +150,8 @@ SIGNATURES = {
                                         _i32, _i32, _vp]),
     "pio_assemble_tokens": (C.c_int, [P(TokenSegment), _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "pio_build_queries": (C.c_int, [P(QuerySegment), _i32, _vp, _i64, _i32, _i32, _vp]),
+    "pio_embed_tokens": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32,
+                                   _i32, _i32, _vp]),
     "pio_gemm_nt": (C.c_int, [P(Gemm), _vp]),
     "pio_softmax_rows": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f, _vp, _vp, _vp, _vp, _i32, _vp]),
     "pio_flash_attention": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64,

@@ -213,6 +213,13 @@ int pio_build_queries(const pio_query_segment_t *segs, int32_t nseg, float *y, i
     return build_queries_launch(segs, nseg, y, ldy, Qtot, Cq, (hipStream_t)stream);
 }
 
+int pio_embed_tokens(const void *ids, int32_t id_bytes, int64_t ids_sb, const float *table, int64_t ldt, int32_t V,
+                     const float *pos, int64_t ldp, float *y, int64_t y_sb, int64_t ldy, float *tokens, int64_t tok_sb,
+                     int64_t ldtok, int32_t *bad_ids, int32_t B, int32_t T, int32_t C, void *stream) {
+    return embed_tokens_launch(ids, id_bytes, ids_sb, table, ldt, V, pos, ldp, y, y_sb, ldy, tokens, tok_sb, ldtok, bad_ids,
+                               B, T, C, (hipStream_t)stream);
+}
+
 int pio_gemm_nt(const pio_gemm_t *g, void *stream) {
     if (!g) return PIO_E_ARG;
     return gemm_nt_launch(*g, (hipStream_t)stream);

@@ -139,6 +139,10 @@ int flow_patch_tokens_launch(const float *f0, const float *f1, int64_t sn0, int6
 // multimodal front end: features | position table | padding embedding (| mask token) of up to 8 row segments in one launch
 int assemble_tokens_launch(const pio_token_segment_t *segs, int nseg, float *y, int64_t ldy, int64_t sYb, int B, int Mtot,
                            int Cc, hipStream_t s);
+// language front end: table[ids[b, t]] + pos[t] (and optionally table[ids[b, t]] alone); NaN rows + a flag for bad ids
+int embed_tokens_launch(const void *ids, int id_bytes, int64_t ids_sb, const float *table, int64_t ldt, int V,
+                        const float *pos, int64_t ldp, float *y, int64_t y_sb, int64_t ldy, float *tokens, int64_t tok_sb,
+                        int64_t ldtok, int32_t *bad_ids, int B, int T, int C, hipStream_t s);
 // decoder queries: Fourier features of index points | learned table, each with its padding embedding, up to 4 row segments
 int build_queries_launch(const pio_query_segment_t *segs, int nseg, float *y, int64_t ldy, int Qtot, int Cq, hipStream_t s);
 int pack_linear_launch(const float *w, const float *bias, int out, int in, int64_t ldw, int row_heads,

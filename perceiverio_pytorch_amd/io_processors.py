@@ -228,7 +228,70 @@ class EmbeddingPreprocessor(nn.Module):
     def n_output_channels(self):
         return self._output_channels
 
+    # One HIP launch (pio_embed_tokens) instead of nn.Embedding + the add: see _fused.  False, and every input _fused
+    # declines, runs the two torch lines of forward exactly as before.
+    fused_embedding = True
+    # False: the fused path skips the position-free second output and returns (y, None) -- for models whose query never
+    # reads it (LanguagePerceiver).  The chain always returns both.
+    need_tokens = True
+
+    def bad_ids_flag(self, device) -> torch.Tensor:
+        """The device word (int32[1]) the fused path reports out-of-range ids into, one per module and device.  Every fused
+        forward zeroes it on the current stream and the kernel sets it to 1 if any id lies outside [0, vocab_size); the
+        forward itself never reads it and adds no synchronisation: the caller reads it when it wants to know (after a
+        graph replay too), as with runtime.last_range_flag."""
+        device = torch.device(device)
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        store = self.__dict__.setdefault("_bad_ids_flags", {})
+        if idx not in store:
+            with torch.inference_mode(False):   # (a normal tensor: zeroed in place from inside and outside inference mode)
+                store[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
+        return store[idx]
+
+    def _fused(self, inputs):
+        """(embed(inputs) + pos, embed(inputs) or None) from ONE pio_embed_tokens call, or None.  Taken under the hip
+        backend for a 2-D CUDA int32 / int64 id tensor with unit stride along t whose length equals the position table's,
+        fp32 embedding and position tables on that device, no padding_idx and no max_norm.  y is one fresh [B, T, C]
+        allocation and equals the chain's bit for bit (one rounded fp32 add of the same operands).  Unlike ATen, which
+        raises a device-side assert, an id outside [0, vocab_size) gives a NaN row in both outputs and sets the word of
+        bad_ids_flag(device)."""
+        from . import _lib as L
+        from . import runtime as R
+        w, p = self.embed.weight, self.input_pos_encoding.pos_embs
+        if (not self.fused_embedding or R.get_backend() != "hip" or not isinstance(inputs, torch.Tensor)
+                or not inputs.is_cuda or inputs.dim() != 2 or inputs.dtype not in (torch.int32, torch.int64)):
+            return None
+        dev = inputs.device
+        b, t = inputs.shape
+        if (b < 1 or t < 1 or (t > 1 and inputs.stride(1) != 1) or t != p.shape[0]
+                or (b > 1 and inputs.stride(0) < t)):
+            return None
+        if (w.dtype != torch.float32 or p.dtype != torch.float32 or w.device != dev or p.device != dev
+                or p.dim() != 2 or p.shape[1] != w.shape[1] or w.shape[1] < 1
+                or self.embed.padding_idx is not None or self.embed.max_norm is not None):
+            return None
+        table, ptab = w.detach(), p.detach()
+        if table.stride(1) != 1 or table.stride(0) < table.shape[1]:
+            table = table.contiguous()
+        if ptab.stride(1) != 1 or ptab.stride(0) < ptab.shape[1]:
+            ptab = ptab.contiguous()
+        v, c = table.shape
+        y = torch.empty((b, t, c), dtype=torch.float32, device=dev)
+        tokens = torch.empty((b, t, c), dtype=torch.float32, device=dev) if self.need_tokens else None
+        flag = self.bad_ids_flag(dev)
+        with R.on_device(dev):
+            flag.zero_()
+            L.check(L.lib().pio_embed_tokens(inputs.data_ptr(), inputs.element_size(), inputs.stride(0), table.data_ptr(),
+                                             table.stride(0), v, ptab.data_ptr(), ptab.stride(0), y.data_ptr(), t * c, c,
+                                             None if tokens is None else tokens.data_ptr(), t * c, c, flag.data_ptr(),
+                                             b, t, c, R.stream_ptr(dev)), "pio_embed_tokens")
+        y = R.forward_only(y, w, p)
+        return y, (None if tokens is None else R.forward_only(tokens, w, p))
+
     def forward(self, inputs: torch.Tensor, *, pos: Optional[torch.Tensor] = None):
+        fused = self._fused(inputs)
+        if fused is not None:
+            return fused
         tokens = self.embed(inputs)
         return tokens + self.input_pos_encoding(inputs.shape[0]), tokens
 

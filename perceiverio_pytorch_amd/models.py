@@ -199,6 +199,7 @@ class LanguagePerceiver(nn.Module):
         super().__init__()
         self.precision_policy = precision_policy
         prep = EmbeddingPreprocessor(vocab_size=vocab_size, max_seq_len=max_seq_len, embedding_dims=embed_dim)
+        prep.need_tokens = False     # (the TrainableQuery below never reads the position-free tokens)
         self.perceiver = PerceiverIO(
             final_project=False, num_self_attends_per_block=num_self_attends_per_block, num_blocks=num_blocks,
             num_latents=num_latents, num_latent_channels=num_latent_channels, input_preprocessors=prep,
@@ -208,6 +209,18 @@ class LanguagePerceiver(nn.Module):
             perceiver_decoder_kwargs=dict(qk_channels=8 * 32, v_channels=embed_dim, num_heads=8,
                                           use_query_residual=False),
             output_queries=TrainableQuery(output_index_dims=max_seq_len, num_channels=embed_dim))
+
+    # The encoder input -- the byte embedding gathered by id plus the learned position embedding -- comes from ONE HIP launch
+    # (EmbeddingPreprocessor.fused_embedding -> pio_embed_tokens) for CUDA int32 / int64 ids of the full sequence length
+    # under the hip backend; False restores nn.Embedding, the add and the one-element torch.cat.  Same bits either way.
+    # An id outside [0, vocab_size) gives a NaN row and sets prep.bad_ids_flag(device) instead of ATen's device-side assert.
+    @property
+    def fused_front_end(self) -> bool:
+        return self.perceiver._multi_preprocessor._preprocessors["__default"].fused_embedding
+
+    @fused_front_end.setter
+    def fused_front_end(self, on: bool) -> None:
+        self.perceiver._multi_preprocessor._preprocessors["__default"].fused_embedding = bool(on)
 
     def forward(self, inputs: torch.Tensor, input_masks: torch.Tensor):
         with _policy_scope(self):

@@ -496,8 +496,28 @@ class MultimodalPreprocessor(nn.Module):
             without_pos[m] = feats if seg.token else x[:, seg.row0:seg.row0 + seg.M, :seg.C1]
         return x, sizes, without_pos
 
+    def _single_embedding(self, inputs):
+        """(x, sizes, without_pos) of forward() for ONE EmbeddingPreprocessor without padding embeddings or mask
+        probabilities whose fused path (pio_embed_tokens) takes these inputs: its output IS the encoder input, so it is
+        returned as it stands instead of going through the one-element torch.cat below (a plain copy of the largest
+        activation).  Same values.  None -- and the chain below, unchanged -- for everything else."""
+        from .io_processors import EmbeddingPreprocessor
+        if (self._preprocessors is None or len(self._preprocessors) != 1 or self.padding_embeddings is not None
+                or self._mask_probs is not None):
+            return None
+        (m, prep), = self._preprocessors.items()
+        if not isinstance(prep, EmbeddingPreprocessor) or m not in inputs:
+            return None
+        fused = prep._fused(inputs[m])
+        if fused is None:
+            return None
+        return fused[0], {m: fused[0].shape[1]}, {m: fused[1]}
+
     def forward(self, inputs, *, pos=None):
         fused = self._assemble(inputs, pos)
+        if fused is not None:
+            return fused
+        fused = self._single_embedding(inputs)
         if fused is not None:
             return fused
         if self._preprocessors is None:

@@ -9,6 +9,8 @@
                                                 16-chunk group [1, 100593, 1026] and the 8 groups of a 128-chunk forward,
                                                 the sine / cosine error of chain and kernel over tests/query_cases.py, and
                                                 the whole model with and without the query cache; prints one JSON line
+    python tools/prep_bench.py --language-front     the language front end (pio_embed_tokens) at full size ([B, 2048, 768],
+                                                V = 262, int64 ids), B = 1, 8 and 100; prints one JSON line
 """
 import argparse
 import json
@@ -310,11 +312,82 @@ def decoder_queries(repeats, launches):
     print(json.dumps(result))
 
 
+def language_front(repeats, launches):
+    """The encoder input of the default LanguagePerceiver (T = 2048, C = 768, V = 262, int64 ids) for B = 1, 8 and 100, timed
+    like multimodal_front (device events around `launches` back-to-back calls after 3 warm-up calls, `repeats` times, the
+    ways alternating inside every repeat):
+      chain -- MultimodalPreprocessor with the switch off: nn.Embedding, the add of the position table, the one-element cat
+      fused -- the same call with the switch on (need_tokens = False, as the model sets it): the output allocation, the
+               memset of the flag word and ONE pio_embed_tokens launch
+      entry -- pio_embed_tokens alone into a resident output, no flag word
+    Reported per way: median and (min, max) of the repeats in microseconds, the store rate over the output's bytes and (chain,
+    fused) torch.cuda.max_memory_allocated above what was allocated before the call."""
+    from perceiverio_pytorch_amd import _lib as L
+    from perceiverio_pytorch_amd.io_processors import EmbeddingPreprocessor
+    from perceiverio_pytorch_amd.perceiver import MultimodalPreprocessor
+    T, C, V = 2048, 768, 262
+    torch.manual_seed(5)
+    prep = EmbeddingPreprocessor(vocab_size=V, max_seq_len=T, embedding_dims=C).to(dev).eval()
+    prep.need_tokens = False
+    mp = MultimodalPreprocessor(input_preprocessors=torch.nn.ModuleDict({"__default": prep}), min_padding_size=0)
+    table, pos = prep.embed.weight.detach(), prep.input_pos_encoding.pos_embs.detach()
+    lib, stream = L.lib(), torch.cuda.current_stream().cuda_stream
+    result = {"tool": "tools/prep_bench.py --language-front", "library": os.path.basename(
+        os.environ.get("PIO_LIB_PATH", "libpio_hip.so")), "T": T, "C": C, "V": V, "ids": "int64", "repeats": repeats,
+        "launches_per_repeat": launches, "unit": "us", "cases": {}}
+    for b in (1, 8, 100):
+        ids = torch.randint(0, V, (b, T), device=dev)
+        ins = {"__default": ids}
+        resident = torch.empty(b, T, C, device=dev)
+
+        def way(on):
+            def f():
+                prep.fused_embedding = on
+                return mp(ins, pos=None)[0]
+            return f
+
+        def entry():
+            L.check(lib.pio_embed_tokens(ids.data_ptr(), 8, T, table.data_ptr(), C, V, pos.data_ptr(), C, resident.data_ptr(),
+                                         T * C, C, None, 0, 0, None, b, T, C, stream), "pio_embed_tokens")
+        ways = {"chain": way(False), "fused": way(True), "entry": entry}
+        with torch.no_grad():
+            xa, xb = ways["chain"](), ways["fused"]()
+            entry()
+            assert prep._fused(ids) is not None, "the fused path declined"
+            assert torch.equal(xa, xb) and torch.equal(xa, resident), "chain and fused outputs differ"
+            del xa, xb
+            peak = {}
+            for k in ("chain", "fused"):
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                base = torch.cuda.memory_allocated()
+                torch.cuda.reset_peak_memory_stats()
+                ways[k]()
+                torch.cuda.synchronize()
+                peak[k] = torch.cuda.max_memory_allocated() - base
+            times = {k: [] for k in ways}
+            for _ in range(repeats):
+                for k, f in ways.items():
+                    times[k].append(timed(f, launches))
+        out_bytes = 4.0 * b * T * C
+        case = {k: {"median": statistics.median(v), "min": min(v), "max": max(v),
+                    "store_GB_per_s_at_median": out_bytes / (statistics.median(v) * 1e-6) / 1e9} for k, v in times.items()}
+        for k, v in peak.items():
+            case[k]["peak_bytes_above_inputs"] = v
+        case.update(shape=[b, T, C], output_bytes=out_bytes)
+        result["cases"][f"B={b}"] = case
+        del resident, ids, ins
+        torch.cuda.empty_cache()
+    prep.fused_embedding = True
+    print(json.dumps(result))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--flow-front", action="store_true", help="time pio_flow_patch_tokens against the torch chain")
     ap.add_argument("--multimodal-front", action="store_true", help="time pio_assemble_tokens against the torch chain")
     ap.add_argument("--decoder-queries", action="store_true", help="time pio_build_queries against the torch chain")
+    ap.add_argument("--language-front", action="store_true", help="time pio_embed_tokens against the torch chain")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--launches", type=int, default=20)
     args = ap.parse_args()
@@ -325,5 +398,7 @@ if __name__ == "__main__":
             multimodal_front(args.repeats, args.launches)
         elif args.decoder_queries:
             decoder_queries(args.repeats, args.launches)
+        elif args.language_front:
+            language_front(args.repeats, args.launches)
         else:
             conv_tail()
