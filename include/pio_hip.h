@@ -450,6 +450,46 @@ int pio_embed_tokens(const void *ids, int32_t id_bytes, int64_t ids_sb, const fl
                      const float *pos, int64_t ldp, float *y, int64_t y_sb, int64_t ldy, float *tokens, int64_t tok_sb,
                      int64_t ldtok, int32_t *bad_ids, int32_t B, int32_t T, int32_t C, void *stream);
 
+/* The tail of tiled optical-flow inference (FlowPerceiver.forward with test_mode, flow_perceiver.py:165-190: every tile's
+ * flow times a linear ramp that peaks at the tile centre, zero-padded to the image and summed, divided by the summed ramps)
+ * as ONE launch.  The ny*nx tiles of size H x W have their top-left corners at the product ys x xs, ys outer, in list order:
+ * tile k = iy*nx + ix lies in group[k / tiles_per_group] at local index j = k % tiles_per_group (the last group holds the
+ * remaining tiles), and sample n of it is batch row j*N + n of that group, a fp32 [tiles*N, 2, H, W] view with the element
+ * strides sn, sc, sy, sx (the same for every group).  out is [N, 2, h, w] fp32 with x contiguous and strides on, oc, oy.
+ * Per output element (n, c, Y, X):
+ *   acc = +0, wsum = +0
+ *   for iy in 0 .. ny-1, for ix in 0 .. nx-1 (this order), ly = Y - ys[iy], lx = X - xs[ix], only where 0 <= ly < H and
+ *   0 <= lx < W:
+ *     r    = fdiv_rn((float)min(lx + 1, W - lx, ly + 1, H - ly), (float)min((W + 1) / 2, (H + 1) / 2))
+ *     acc  = fadd_rn(acc, fmul_rn(flow_k[n, c, ly, lx], r))      (two rounded operations, never an FMA)
+ *     wsum = fadd_rn(wsum, r)
+ *   out = fdiv_rn(acc, wsum)                                      (both divisions correctly rounded)
+ * which are the bits of the chain, signs of zeros included: where a tile does not cover a pixel the chain adds +0 to a sum
+ * that began as +0.  The order of the tiles is part of the definition.  A tile begins inside the image and may hang over its
+ * lower or right edge (compute_grid_indices makes such tiles when an inner corner lies behind h - H): what hangs over is
+ * neither read nor written, as with the chain's negative padding.  Only the N*2*h*w elements of out are written: the
+ * columns [w, oy) and everything else stay untouched; of a group only tile elements are read.  The struct is copied into the
+ * kernel arguments: no table lives in device memory.  Both channels of a tile pixel are one 8-byte load when sc == 1,
+ * sx == 2, sn and sy are even and every group pointer is 8-byte aligned (the permuted view of [B, H, W, 2] that
+ * FlowPostprocessor returns); any other strides work, as two dword loads.  No workspace, no device allocation, no
+ * synchronisation.
+ * PIO_E_ARG: NULL p / out, NULL group[i] for i < ngroups; PIO_E_SHAPE: N, H or W < 1, h < H, w < W, ny or nx outside
+ * [1, 64], ngroups outside [1, 64], tiles_per_group < 1, ngroups != ceil(ny*nx / tiles_per_group), a corner outside
+ * [0, h - 1] / [0, w - 1], a row or column of the image that no tile covers (the chain gives 0 / 0 there), oy < w,
+ * N * h * ceil(w / 256) workgroups beyond 2^31 - 1; PIO_E_ALIGN: out or a group pointer not 4-byte aligned.  A refused call
+ * launches nothing. */
+#define PIO_MAX_BLEND_AXIS 64
+#define PIO_MAX_BLEND_GROUPS 64
+typedef struct pio_flow_blend_t {
+    const float *group[PIO_MAX_BLEND_GROUPS]; /* flows of tile group i */
+    int64_t sn, sc, sy, sx; /* element strides of a group's [tiles*N, 2, H, W] view, the same for every group */
+    int32_t ngroups, tiles_per_group;
+    int32_t ny, nx; /* tile corners are the product ys x xs, ys outer, in list order */
+    int32_t ys[PIO_MAX_BLEND_AXIS], xs[PIO_MAX_BLEND_AXIS];
+    int32_t N, H, W, h, w; /* samples, tile size, image size */
+} pio_flow_blend_t;
+int pio_flow_blend_tiles(const pio_flow_blend_t *p, float *out, int64_t on, int64_t oc, int64_t oy, void *stream);
+
 /* C = epilogue(alpha * A B^T): A [M,K], B [N,K] operand dtype, K contiguous (multiple of 8).
  * Batched over z = zb*nh + zh with element strides; bias_mode 0 none / 1 per column / 2 per row;
  * act 0 none / 1 exact-erf GELU (F.gelu, transformer_primitives.py:214); optional fp32 residual R

@@ -98,6 +98,18 @@ class QuerySegment(C.Structure):
                 ("concat_pos", C.c_int32), ("sine_only", C.c_int32), ("C", C.c_int32)]
 
 
+PIO_MAX_BLEND_AXIS = 64
+PIO_MAX_BLEND_GROUPS = 64
+
+
+class FlowBlend(C.Structure):
+    """pio_flow_blend_t: the tile groups, corners and sizes of pio_flow_blend_tiles (passed by value into the kernel)."""
+    _fields_ = [("group", C.c_void_p * PIO_MAX_BLEND_GROUPS), ("sn", C.c_int64), ("sc", C.c_int64), ("sy", C.c_int64),
+                ("sx", C.c_int64), ("ngroups", C.c_int32), ("tiles_per_group", C.c_int32), ("ny", C.c_int32),
+                ("nx", C.c_int32), ("ys", C.c_int32 * PIO_MAX_BLEND_AXIS), ("xs", C.c_int32 * PIO_MAX_BLEND_AXIS),
+                ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+
 class Gemm(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("A_lo", C.c_void_p), ("B_lo", C.c_void_p), ("C", C.c_void_p),
                 ("C_lo", C.c_void_p),
@@ -152,6 +164,7 @@ SIGNATURES = {
     "pio_build_queries": (C.c_int, [P(QuerySegment), _i32, _vp, _i64, _i32, _i32, _vp]),
     "pio_embed_tokens": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32,
                                    _i32, _i32, _vp]),
+    "pio_flow_blend_tiles": (C.c_int, [P(FlowBlend), _vp, _i64, _i64, _i64, _vp]),
     "pio_gemm_nt": (C.c_int, [P(Gemm), _vp]),
     "pio_softmax_rows": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f, _vp, _vp, _vp, _vp, _i32, _vp]),
     "pio_flash_attention": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64,

@@ -220,6 +220,10 @@ int pio_embed_tokens(const void *ids, int32_t id_bytes, int64_t ids_sb, const fl
                                B, T, C, (hipStream_t)stream);
 }
 
+int pio_flow_blend_tiles(const pio_flow_blend_t *p, float *out, int64_t on, int64_t oc, int64_t oy, void *stream) {
+    return flow_blend_tiles_launch(p, out, on, oc, oy, (hipStream_t)stream);
+}
+
 int pio_gemm_nt(const pio_gemm_t *g, void *stream) {
     if (!g) return PIO_E_ARG;
     return gemm_nt_launch(*g, (hipStream_t)stream);

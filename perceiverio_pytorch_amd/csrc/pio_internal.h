@@ -143,6 +143,8 @@ int assemble_tokens_launch(const pio_token_segment_t *segs, int nseg, float *y, 
 int embed_tokens_launch(const void *ids, int id_bytes, int64_t ids_sb, const float *table, int64_t ldt, int V,
                         const float *pos, int64_t ldp, float *y, int64_t y_sb, int64_t ldy, float *tokens, int64_t tok_sb,
                         int64_t ldtok, int32_t *bad_ids, int B, int T, int C, hipStream_t s);
+// tiled flow inference: ramp-weighted sum of all tile flows over the summed ramps, in tile order
+int flow_blend_tiles_launch(const pio_flow_blend_t *p, float *out, int64_t on, int64_t oc, int64_t oy, hipStream_t s);
 // decoder queries: Fourier features of index points | learned table, each with its padding embedding, up to 4 row segments
 int build_queries_launch(const pio_query_segment_t *segs, int nseg, float *y, int64_t ldy, int Qtot, int Cq, hipStream_t s);
 int pack_linear_launch(const float *w, const float *bias, int out, int in, int64_t ldw, int row_heads,

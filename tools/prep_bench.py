@@ -11,6 +11,12 @@
                                                 the whole model with and without the query cache; prints one JSON line
     python tools/prep_bench.py --language-front     the language front end (pio_embed_tokens) at full size ([B, 2048, 768],
                                                 V = 262, int64 ids), B = 1, 8 and 100; prints one JSON line
+    python tools/prep_bench.py --flow-blend         the tile blend of tiled flow inference (pio_flow_blend_tiles) against the
+                                                torch chain at 436 x 1024 (6 tiles) and 1080 x 1920 (20 tiles), b = 1; prints
+                                                one JSON line
+    python tools/prep_bench.py --flow-blend-forward [--package-root DIR]   the whole test_mode forward of the full-size
+                                                FlowPerceiver at 436 x 1024 with the package under DIR (default: this tree):
+                                                run it alternately on two checkouts to compare them; prints one JSON line
 """
 import argparse
 import json
@@ -19,6 +25,8 @@ import statistics
 import sys
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+if "--package-root" in sys.argv:                 # (--flow-blend-forward: time another checkout's package)
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--package-root") + 1])
 sys.path[:0] = [ROOT]
 import torch  # noqa: E402
 from perceiverio_pytorch_amd.io_processors import Conv2DDownsample  # noqa: E402
@@ -382,12 +390,148 @@ def language_front(repeats, launches):
     print(json.dumps(result))
 
 
+def _kernel_launches(f):
+    """Device kernels and memory copies of one call of f, counted by the profiler (None where it is not usable)."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        f()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            f()
+            torch.cuda.synchronize()
+        ev = [e for e in prof.events() if str(e.device_type).endswith("CUDA")]
+        copies = sum(1 for e in ev if "memcpy" in e.name.lower() or "copy" in e.name.lower() and "kernel" not in e.name.lower())
+        return {"device_events": len(ev), "of_them_memory_copies": copies}
+    except Exception as e:      # noqa: BLE001
+        return {"error": repr(e)}
+
+
+def flow_blend(repeats, launches):
+    """The tile blend of FlowPerceiver.forward(test_mode=True) at the default tile size 368 x 496, b = 1, tiles_per_call 4,
+    for a Sintel frame (436 x 1024, min_overlap 20: 6 tiles) and a 1080p frame (1080 x 1920, min_overlap 24: 20 tiles).  _predict_patch is
+    replaced by a stub that hands out resident flows in the layout FlowPostprocessor returns, so no model runs and the two
+    ways differ in the blend alone; both still stack the frames and torch.cat the tiles of every group, as the model does.
+      chain -- fused_blend = False: the ramp built on the host and copied over, per tile multiply, two pads, two adds, one divide
+      fused -- fused_blend = True: the output allocation and ONE pio_flow_blend_tiles launch
+      entry -- pio_flow_blend_tiles alone into a resident output
+      stack_and_cats -- the stack and the cats alone (what chain and fused share)
+    Timed like the other front ends (device events around `launches` back-to-back calls after 3 warm-up calls, `repeats`
+    times, the ways alternating inside every repeat): median and (min, max) in microseconds; device events of one call from
+    the profiler; torch.cuda.max_memory_allocated above what was allocated before the call."""
+    from perceiverio_pytorch_amd import _lib as L
+    from perceiverio_pytorch_amd.models import FlowPerceiver
+    H, W = 368, 496
+    model = FlowPerceiver(num_latents=4, num_latent_channels=16, num_self_attends_per_block=1).to(dev).eval()
+    lib, stream = L.lib(), torch.cuda.current_stream().cuda_stream
+    result = {"tool": "tools/prep_bench.py --flow-blend", "tile": [H, W], "b": 1, "tiles_per_call": 4,
+              "repeats": repeats, "launches_per_repeat": launches, "unit": "us", "cases": {}}
+    # (1080 x 1920 at min_overlap 20 puts a corner at x = 1428 > 1920 - 496: that tile hangs over the edge and the model's
+    #  torch.cat of tiles refuses it, chain or not; 24 is the smallest overlap whose 20 tiles all lie inside the frame)
+    for h, w, overlap in ((436, 1024, 20), (1080, 1920, 24)):
+        ys, xs = model._grid_axes((h, w), overlap)
+        tiles = len(ys) * len(xs)
+        groups = [torch.randn(min(4, tiles - i), H, W, 2, device=dev).permute(0, 3, 1, 2) for i in range(0, tiles, 4)]
+        frames = torch.randn(1, 3, h, w, device=dev)
+        resident = torch.empty(1, 2, h, w, device=dev)
+        state = {"i": 0}
+
+        def predict(t):
+            state["i"] = (state["i"] + 1) % len(groups)
+            return groups[state["i"] - 1]
+        model._predict_patch = predict
+
+        def way(on):
+            def f():
+                model.fused_blend = on
+                state["i"] = 0
+                return model(frames, frames, test_mode=True, min_overlap=overlap)
+            return f
+
+        p = L.FlowBlend()
+        for i, g in enumerate(groups):
+            p.group[i] = g.data_ptr()
+        p.sn, p.sc, p.sy, p.sx = groups[0].stride()
+        p.ngroups, p.tiles_per_group, p.ny, p.nx = len(groups), 4, len(ys), len(xs)
+        p.ys[:len(ys)], p.xs[:len(xs)] = ys, xs
+        p.N, p.H, p.W, p.h, p.w = 1, H, W, h, w
+
+        def entry():
+            L.check(lib.pio_flow_blend_tiles(p, resident.data_ptr(), 2 * h * w, h * w, w, stream), "pio_flow_blend_tiles")
+
+        def tiles_only():
+            pair = torch.stack([frames.contiguous(), frames.contiguous()], dim=1)
+            for i in range(0, tiles, 4):
+                torch.cat([pair[..., y:y + H, x:x + W] for y in ys for x in xs][i:i + 4], dim=0)
+        ways = {"chain": way(False), "fused": way(True), "entry": entry, "stack_and_cats": tiles_only}
+        xa, xb = ways["chain"](), ways["fused"]()
+        entry()
+        torch.cuda.synchronize()
+        assert torch.equal(xb, resident), "module and raw entry disagree"
+        equal = bool(torch.equal(xa.view(torch.int32), xb.view(torch.int32)))
+        maxdiff = float((xa - xb).abs().max())
+        del xa, xb
+        peak, events = {}, {}
+        for k in ("chain", "fused"):
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            ways[k]()
+            torch.cuda.synchronize()
+            peak[k] = torch.cuda.max_memory_allocated() - base
+        for k in ways:
+            events[k] = _kernel_launches(ways[k])
+        times = {k: [] for k in ways}
+        for _ in range(repeats):
+            for k, f in ways.items():
+                times[k].append(timed(f, launches))
+        case = {k: {"median": statistics.median(v), "min": min(v), "max": max(v), "one_call": events[k]}
+                for k, v in times.items()}
+        for k, v in peak.items():
+            case[k]["peak_bytes_above_inputs"] = v
+        need = 8.0 * h * w + 8.0 * tiles * H * W
+        case["entry"]["algorithm_bytes"] = need
+        case["entry"]["GB_per_s_at_median"] = need / (case["entry"]["median"] * 1e-6) / 1e9
+        case.update(image=[h, w], min_overlap=overlap, tiles=tiles, groups=len(groups), chain_equals_fused_bit_for_bit=equal,
+                    max_abs_chain_minus_fused=maxdiff)
+        result["cases"][f"{h}x{w}"] = case
+        del groups, frames, resident
+        torch.cuda.empty_cache()
+    print(json.dumps(result))
+
+
+def flow_blend_forward(repeats, launches):
+    """The whole test_mode forward of the full-size FlowPerceiver (default policy, tiles_per_call 4) on a 436 x 1024 frame
+    pair, b = 1: 6 tile forwards in two groups and the blend.  Timed with device events around `launches` forwards after 3
+    warm-up forwards, `repeats` times; prints the package it ran and whether that package has the fused blend."""
+    from perceiverio_pytorch_amd.models import FlowPerceiver
+    torch.manual_seed(1)
+    model = FlowPerceiver().to(dev).eval()
+    with torch.no_grad():
+        for q in model.parameters():             # (the decoder's output weights start as zeros)
+            if q.numel() and float(q.abs().max()) == 0.0:
+                q.normal_(0.0, 0.02)
+    a, b = torch.randn(1, 3, 436, 1024, device=dev), torch.randn(1, 3, 436, 1024, device=dev)
+    with torch.inference_mode():
+        f = lambda: model(a, b, test_mode=True, min_overlap=20)      # noqa: E731
+        out = f()
+        t = [timed(f, launches) for _ in range(repeats)]
+    import hashlib
+    print(json.dumps({"tool": "tools/prep_bench.py --flow-blend-forward", "package_root": ROOT,
+                      "fused_blend": getattr(model, "fused_blend", None), "image": [436, 1024], "unit": "us",
+                      "repeats": repeats, "launches_per_repeat": launches, "median": statistics.median(t), "min": min(t),
+                      "max": max(t), "output_sha1": hashlib.sha1(out.cpu().numpy().tobytes()).hexdigest()}))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--flow-front", action="store_true", help="time pio_flow_patch_tokens against the torch chain")
     ap.add_argument("--multimodal-front", action="store_true", help="time pio_assemble_tokens against the torch chain")
     ap.add_argument("--decoder-queries", action="store_true", help="time pio_build_queries against the torch chain")
     ap.add_argument("--language-front", action="store_true", help="time pio_embed_tokens against the torch chain")
+    ap.add_argument("--flow-blend", action="store_true", help="time pio_flow_blend_tiles against the torch chain")
+    ap.add_argument("--flow-blend-forward", action="store_true", help="time the whole tiled forward of the flow model")
+    ap.add_argument("--package-root", default=None, help="--flow-blend-forward: the checkout whose package is timed")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--launches", type=int, default=20)
     args = ap.parse_args()
@@ -400,5 +544,9 @@ if __name__ == "__main__":
             decoder_queries(args.repeats, args.launches)
         elif args.language_front:
             language_front(args.repeats, args.launches)
+        elif args.flow_blend:
+            flow_blend(args.repeats, args.launches)
+        elif args.flow_blend_forward:
+            flow_blend_forward(args.repeats, args.launches)
         else:
             conv_tail()
