@@ -27,7 +27,7 @@
 
 #include <type_traits>
 
-#include "pio_internal.h"
+#include "pio_device.h"
 
 namespace pio {
 
@@ -47,7 +47,6 @@ struct FlashParams {
     void *O_lo;                  // QK_PAIR instantiations only (optional): o - float(O); the launcher clears o_rows16 with it
 };
 
-static __device__ __attribute__((aligned(16))) uint32_t g_zero_chunk_f[4] = {0, 0, 0, 0};
 
 // VROW = true: V is consumed ROW-major ([keys][H*dv], the layout a plain projection GEMM writes, so Q | K | V come out
 // of ONE fused GEMM) through transposed LDS reads; VROW = false: V^T [dv][keys] as before.
@@ -119,7 +118,7 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 || (QK_PAIR && DK == 128)) ? 1 : 
     const T *Qg = (const T *)p.Q + b * p.sQb + (int64_t)h * DK;
     const T *Kg = (const T *)p.K + b * p.sKb + (int64_t)h * DK;
     const T *Vg = (const T *)p.VT + b * p.sVb + (VROW ? (int64_t)h * DV : (int64_t)h * DV * p.ldvt);
-    const T *zsrc = (const T *)g_zero_chunk_f;
+    const T *zsrc = (const T *)g_zero16;
     const T *Klg = nullptr;
     if constexpr (QK_PAIR) Klg = (const T *)p.K_lo + b * p.sKb + (int64_t)h * DK;
 

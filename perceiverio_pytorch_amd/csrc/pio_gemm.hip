@@ -18,7 +18,6 @@
 
 namespace pio {
 
-__device__ __attribute__((aligned(16))) uint32_t g_zero_chunk[4] = {0, 0, 0, 0};
 
 #ifdef PIO_G128_STAMPS
 // Dev-only (tools/g128_stamps.py builds a private copy of the library with this flag): thread 0 of one workgroup records
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(256 * KG) void gemm_nt_128(const GemmParams p) {
         gn = gn < p.N ? gn : p.N - 1;
         b_src[i] = B + (int64_t)gn * p.ldb + c * 8;
     }
-    const T *zsrc = (const T *)g_zero_chunk;
+    const T *zsrc = (const T *)g_zero16;
 
     const int nk1 = (p.K + BK * KG - 1) / (BK * KG);   // steps per pass (of one team)
     const int nk = p.npass * nk1;

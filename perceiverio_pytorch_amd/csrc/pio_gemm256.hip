@@ -18,8 +18,6 @@
 
 namespace pio {
 
-static __device__ __attribute__((aligned(16))) uint32_t g_zero256[4] = {0, 0, 0, 0};
-
 #ifdef PIO_GEMM_STAMPS
 // Dev-only phase stamps (tools/gemm_stamps.py --build makes a private copy of the library with this flag; the shipped
 // library never has it): wave 0 of tile 0 records s_memtime at the phase edges, g_epi_mode selects an epilogue
@@ -68,7 +66,7 @@ __global__ __launch_bounds__(512) void gemm_nt_256(const GemmParams p) {
 
     const T *A = (const T *)p.A + zb * p.sAb + zh * p.sAh;
     const T *B = (const T *)p.B + zb * p.sBb + zh * p.sBh;
-    const T *zsrc = (const T *)g_zero256;
+    const T *zsrc = (const T *)g_zero16;
 
     // ---- staging: stage = A[256][32] | B[256][32]; a 1-KiB piece = 16 rows; wave w owns pieces 2w, 2w+1
     const T *a_src[2];

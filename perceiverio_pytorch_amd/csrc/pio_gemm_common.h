@@ -1,6 +1,6 @@
 // Shared by the two NT-GEMM kernels (pio_gemm.hip: 128x128 tile; pio_gemm256.hip: 256x256 tile).
 #pragma once
-#include "pio_internal.h"
+#include "pio_device.h"
 #include "pio_gemm_route.h"
 
 namespace pio {

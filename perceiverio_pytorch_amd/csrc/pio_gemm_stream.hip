@@ -34,16 +34,9 @@
 // Results are identical to gemm_nt_256 / gemm_nt_128 (same MFMA, same K order, fp32 epilogue), except that bias and
 // residual enter the fp32 accumulation early instead of last.
 // Shapes: K % 64 == 0, K*passes >= 1024, N % 4 == 0 (gemm_stream_ok); everything else stays on the tile kernels.
-#include <type_traits>
-
 #include "pio_gemm_common.h"
 
 namespace pio {
-
-static __device__ __attribute__((aligned(16))) uint32_t g_zero_s[4] = {0, 0, 0, 0};
-// Stores of lanes outside the matrix (and of the first tile's empty predecessor) go here instead of being
-// predicated off: the store instruction is then ALWAYS issued, so the counted waits can count it.
-static __device__ __attribute__((aligned(16))) uint32_t g_sink_s[64 * 4];
 
 #ifdef PIO_GEMM_STAMPS
 // Dev-only (tools/gemm_stamps.py): wave 0 of workgroup 0 records s_memtime inside one unrolled step with epilogue
@@ -73,33 +66,10 @@ constexpr int S_BIAS_W = 768;             // per wave: 3 slots x 64 floats (bias
 constexpr int S_TAB = S_RING + 8 * S_BIAS_W;
 constexpr int S_SMEM = S_TAB + S_TAB_N * 32;
 
-__device__ __forceinline__ void wait_vm_n(int n) {  // n: wave-uniform
-#define PIO_W(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-    switch (n) {
-        PIO_W(0) PIO_W(1) PIO_W(2) PIO_W(3) PIO_W(4) PIO_W(5) PIO_W(6) PIO_W(7) PIO_W(8) PIO_W(9) PIO_W(10)
-        PIO_W(11) PIO_W(12) PIO_W(13) PIO_W(14) PIO_W(15) PIO_W(16) PIO_W(17) PIO_W(18) PIO_W(19)
-        default: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-    }
-#undef PIO_W
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
 __device__ __forceinline__ int64_t uniform64(int64_t v) {  // a value every lane holds -> scalar registers
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32));
     return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-__device__ __forceinline__ void lds_dma16(const void *src, void *lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
 }
 
 struct STile {  // wave-uniform description of one output tile
@@ -293,13 +263,13 @@ __global__ __launch_bounds__(512) void gemm_nt_stream(const GemmParams p, int ti
         const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
         if (lane < 16) {
             const int n = n0 + team * 64 + lane * 4;
-            const float *src = (p.bias_mode == 1 && n < p.N) ? p.bias + n : (const float *)g_zero_s;
+            const float *src = (p.bias_mode == 1 && n < p.N) ? p.bias + n : (const float *)g_zero16;
             lds_dma16(src, bstash + slot * 64);
         }
     };
     auto bias_of = [&](int slot, int ni) { return *(const f32x4 *)(bstash + slot * 64 + ni * 16 + fq * 4); };
     int bslot = 0;  // stash slot of the CURRENT tile's bias row (j % 3); tile j+2's row goes to (bslot + 2) % 3
-    char *const sink = (char *)g_sink_s + lane * 16;
+    char *const sink = (char *)g_sink + lane * 16;
     auto store_unit = [&](f32x4 v, int mi, int ni, bool live) {
         const int m = o_m + mi * 16, n = o_n + ni * 16;
 #pragma unroll

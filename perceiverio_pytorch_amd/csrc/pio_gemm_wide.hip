@@ -35,8 +35,6 @@
 // issues its 32 stores (out-of-range ones to a global sink), so the counted waits are exact.
 //
 // Reference semantics: y = x W^T + b of nn.Linear (perceiver_io/transformer_primitives.py:93-95, 110).
-#include <type_traits>
-
 #include "pio_gemm_common.h"
 
 namespace pio {
@@ -47,9 +45,6 @@ constexpr int W_STAGE = 2 * W_AB;        // 32 KiB
 constexpr int W_RING = W_NST * W_STAGE;  // 128 KiB
 constexpr int W_BIAS = W_RING + 4 * 1024;  // after the per-wave sinks for the pieces past the end: per-wave bias rows
 constexpr int W_SMEM = W_BIAS + 4 * 1024;  // per wave: bias row (512 B) + the LayerNorm fold's c row (512 B)
-
-static __device__ __attribute__((aligned(16))) uint32_t g_sink_w[64 * 4];
-static __device__ __attribute__((aligned(16))) uint32_t g_zero_w[4] = {0, 0, 0, 0};
 
 #ifdef PIO_GEMM_STAMPS
 // Dev-only (tools/gemm_stamps.py --wide): wave 0 of workgroup 0 records s_memtime inside its ordinary phases (the
@@ -77,27 +72,6 @@ __device__ unsigned long long g_westamps[16];  // staged producer epilogue: star
 #define PIO_WSTAMP(i)
 #define PIO_WESTAMP(i)
 #endif
-
-template <int I, int N, class F>
-__device__ __forceinline__ void wide_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        wide_for<I + 1, N>(f);
-    }
-}
-
-__device__ __forceinline__ void wide_dma16(const void *src, void *lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
-}
-
-// Reads one accumulator element where it lives (an AGPR): without this the register allocator moves all 256 to VGPRs
-// at the end of the K loop and a handful of address registers spill.
-__device__ __forceinline__ float acc_read(float a) {
-    float v;
-    asm("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a));
-    return v;
-}
 
 // The MFMA as inline assembly with its accumulator pinned to AGPRs ("+a"), accumulating in place: left to the
 // register allocator, the 256 accumulator registers wander between the two files and a few of them spill.  (The
@@ -274,8 +248,8 @@ __global__ __launch_bounds__(256) void gemm_nt_wide(const GemmParams p, int tile
         //  register pair: "uniform base + zext(32-bit VGPR)" at the use is what selects the SGPR-base form of the DMA)
         uint32_t &o = i < 4 ? voa[i] : vob[i - 4];
         asm volatile("" : "+v"(o));  // (in place: no copy)
-        if (i < 4) wide_dma16(ia + (uint64_t)o, isb + i * istep);
-        else wide_dma16(ib + (uint64_t)o, isb + ibo + (i - 4) * istep);
+        if (i < 4) lds_dma16(ia + (uint64_t)o, isb + i * istep);
+        else lds_dma16(ib + (uint64_t)o, isb + ibo + (i - 4) * istep);
     };
     auto issue_end = [&]() {
         dslot = (dslot + 1) & 3;
@@ -349,7 +323,7 @@ __global__ __launch_bounds__(256) void gemm_nt_wide(const GemmParams p, int tile
     float *const bstash = (float *)(smem + W_BIAS + wave * 1024);
     float *const cstash = bstash + 128;
     int o_m = 0, o_n = 0, o_n0 = 0;  // this lane's first row / column of the current tile; the wave's first column
-    char *const sink = (char *)g_sink_w + lane * 16;
+    char *const sink = (char *)g_sink + lane * 16;
 
     // One phase.  The wave is alone on its SIMD, so whatever it issues outside an MFMA's shadow idles the matrix pipe:
     // the meeting point of the phase (counted wait for the DMA, wait for the LDS reads, barrier) sits BEHIND the
@@ -364,15 +338,15 @@ __global__ __launch_bounds__(256) void gemm_nt_wide(const GemmParams p, int tile
         if constexpr (FIRST) {
             if (lane < 32) {
                 const int n = o_n0 + lane * 4;
-                const float *src = (p.bias_mode == 1 && n < p.N) ? p.bias + n : (const float *)g_zero_w;
-                wide_dma16(src, bstash);
+                const float *src = (p.bias_mode == 1 && n < p.N) ? p.bias + n : (const float *)g_zero16;
+                lds_dma16(src, bstash);
                 if constexpr (LNF == 2) {
-                    const float *srcc = n < p.N ? p.ln_c + n : (const float *)g_zero_w;
-                    wide_dma16(srcc, cstash);
+                    const float *srcc = n < p.N ? p.ln_c + n : (const float *)g_zero16;
+                    lds_dma16(srcc, cstash);
                 }
             }
         }
-        wide_for<0, 16>([&](auto GI) {
+        static_for<0, 16>([&](auto GI) {
             constexpr int g = decltype(GI)::value;
 #ifdef PIO_GEMM_STAMPS
             constexpr bool skip_rd = PIO_WIDE_ABL & 1, skip_dma = PIO_WIDE_ABL & 2;
@@ -492,8 +466,8 @@ __global__ __launch_bounds__(256) void gemm_nt_wide(const GemmParams p, int tile
                 int m = o_m + mi * 16;
                 m = m < p.M ? m : p.M - 1;
                 const float *pr = p.ln_part + (int64_t)m * ns * 2;
-                part[mi] = *(const f32x4 *)(2 * fq < ns ? pr + 4 * fq : (const float *)g_zero_w);
-                part2[mi] = *(const pio_f32x2 *)(8 + fq < ns ? pr + 16 + 2 * fq : (const float *)g_zero_w);
+                part[mi] = *(const f32x4 *)(2 * fq < ns ? pr + 4 * fq : (const float *)g_zero16);
+                part2[mi] = *(const pio_f32x2 *)(8 + fq < ns ? pr + 16 + 2 * fq : (const float *)g_zero16);
             }
         }
         constexpr int NSTORE = OUT == 2 ? 64 : 32;

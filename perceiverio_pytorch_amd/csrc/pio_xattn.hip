@@ -34,19 +34,9 @@
 //     (scale, masks, softmax, P rounded once, P V, key splits, the O / O_lo pair, the wipe) is the code above, unchanged.
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "pio_internal.h"
+#include "pio_device.h"
 
 namespace pio {
-
-template <int I, int N, class F>
-__device__ __forceinline__ void xa_for(F &&f) {  // compile-time loop: the index arrives as an integral_constant
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        xa_for<I + 1, N>(f);
-    }
-}
 
 struct XattnParams {
     const void *Q, *K, *VT;
@@ -61,11 +51,6 @@ struct XattnParams {
     float scale_log2;  // log2(e) / sqrt(dk)
     const void *Q_lo, *K_lo;  // QK_PAIR instantiations only: the rounding residuals of Q / K (same strides as Q / K)
 };
-
-__device__ __forceinline__ void xattn_dma16(const void *src, void *lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
-}
 
 // MFMAs as inline assembly with their register files pinned (the pattern of pio_gemm_wide.hip).  The O^T accumulator
 // (up to 176 registers) lives in AGPRs and accumulates in place; the first (256 - |O^T|) / 4 Q fragments live in AGPRs
@@ -93,11 +78,6 @@ __device__ __forceinline__ void xa_mfma_v0(f32x16 &c, typename Op<DT>::V8 a, typ
         if constexpr (B_IN_AGPR) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "a"(b));
         else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "v"(b));
     }
-}
-template <int DT>
-__device__ __forceinline__ void xa_mfma_a(f32x16 &c, typename Op<DT>::V8 a, typename Op<DT>::V8 b) {  // acc in AGPRs
-    if constexpr (DT == PIO_DT_F16) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-    else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
 }
 
 template <int DT, int DKL, int DVS, bool QK_PAIR = false>
@@ -247,15 +227,15 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
             char *dst = (4 * i + 4 <= K_PIECES || wave + 4 * i < K_PIECES) ? stage_kb + i * stage_step
                                                                           : smem + SINK + wave * 1024;
             // (QK_PAIR: every piece holds chunks of both halves -- the base is chosen per lane)
-            if constexpr (QK_PAIR) xattn_dma16((const char *)(klo[i] ? stage_kl : stage_k) + 2 * (uint64_t)o, dst);
-            else xattn_dma16((const char *)stage_k + 2 * (uint64_t)o, dst);
+            if constexpr (QK_PAIR) lds_dma16((const char *)(klo[i] ? stage_kl : stage_k) + 2 * (uint64_t)o, dst);
+            else lds_dma16((const char *)stage_k + 2 * (uint64_t)o, dst);
         } else {
             constexpr int j = i - KPW;
             uint32_t &o = voff[j];
             asm volatile("" : "+v"(o));
             char *dst = (4 * j + 4 <= V_PIECES || wave + 4 * j < V_PIECES) ? stage_vb + j * stage_step
                                                                           : smem + SINK + wave * 1024;
-            xattn_dma16((const char *)stage_v + 2 * (uint64_t)o, dst);
+            lds_dma16((const char *)stage_v + 2 * (uint64_t)o, dst);
         }
     };
 
@@ -288,7 +268,7 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
 #pragma unroll
     for (int j = 0; j < NST - 1; ++j) {
         stage_begin(t_begin + j, j, t_begin + j < t_end);
-        xa_for<0, NP>([&](auto PI) { stage_piece(PI); });
+        static_for<0, NP>([&](auto PI) { stage_piece(PI); });
     }
     int slot = 0;  // ring stage of tile kt
     for (int kt = t_begin; kt < t_end; ++kt) {
@@ -326,7 +306,7 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
 #pragma unroll
             for (int i = 0; i < 2 * NQS; ++i) kf[i] = k_read(i);
             __builtin_amdgcn_sched_barrier(0);
-            xa_for<0, 3 * NQS>([&](auto JI) {
+            static_for<0, 3 * NQS>([&](auto JI) {
                 constexpr int j = decltype(JI)::value;
                 constexpr int which = j / NQS, sx = j % NQS;
                 if constexpr (which == 0) sacc = Op<DT>::mfma32(kf[NQS + sx], qf[sx], sacc);
@@ -335,12 +315,12 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
                 if constexpr (j < KPW + VPW) stage_piece(std::integral_constant<int, j>{});
                 __builtin_amdgcn_sched_barrier(0);
             });
-            xa_for<3 * NQS, KPW + VPW>([&](auto PI) { stage_piece(PI); });
+            static_for<3 * NQS, KPW + VPW>([&](auto PI) { stage_piece(PI); });
         } else {
 #pragma unroll
         for (int i = 0; i < RK; ++i) kf[i] = k_read(i);
         __builtin_amdgcn_sched_barrier(0);
-        xa_for<0, NQS>([&](auto SI) {
+        static_for<0, NQS>([&](auto SI) {
             constexpr int sx = decltype(SI)::value;
             if constexpr (!PIN) sacc = Op<DT>::mfma32(kf[sx % RK], qf[sx], sacc);
             else if constexpr (sx == 0) xa_mfma_v0<DT, (0 < NQ_A)>(sacc, kf[0], qf[0]);
@@ -349,7 +329,7 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
             if constexpr (sx < KPW + VPW) stage_piece(std::integral_constant<int, sx>{});
             __builtin_amdgcn_sched_barrier(0);
         });
-        xa_for<NQS, KPW + VPW>([&](auto PI) { stage_piece(PI); });
+        static_for<NQS, KPW + VPW>([&](auto PI) { stage_piece(PI); });
         }
         // first V^T fragments: in flight during the softmax arithmetic.  Fragment f = 2 d + s2 (d tile, k-step).
         constexpr int NVF = 2 * NDT, RV = NVF < RING ? NVF : RING;
@@ -430,10 +410,10 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (PIN) asm volatile("s_nop 3" ::: "memory");  // VALU write of P^T -> MFMA reads it as SrcB
         __builtin_amdgcn_sched_barrier(0);
-        xa_for<0, NVF>([&](auto FI) {
+        static_for<0, NVF>([&](auto FI) {
             constexpr int f = decltype(FI)::value;
             constexpr int d = f >> 1, s2 = f & 1;
-            if constexpr (PIN) xa_mfma_a<DT>(oacc[d], vf[f % RV], pf[s2]);
+            if constexpr (PIN) mfma32_agpr<DT>(oacc[d], vf[f % RV], pf[s2]);
             else oacc[d] = Op<DT>::mfma32(vf[f % RV], pf[s2], oacc[d]);
             if constexpr (f + RV < NVF) vf[f % RV] = v_read(f + RV);
             __builtin_amdgcn_sched_barrier(0);

@@ -29,19 +29,9 @@
 // pio_xattn.hip.
 #include <stdlib.h>
 
-#include <type_traits>
-
-#include "pio_internal.h"
+#include "pio_device.h"
 
 namespace pio {
-
-template <int I, int N, class F>
-__device__ __forceinline__ void xt_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        xt_for<I + 1, N>(f);
-    }
-}
 
 struct XtallParams {
     const void *Q, *K, *VT;
@@ -62,24 +52,7 @@ constexpr int T_NP = 10;                  // LDS-DMA pieces per wave and chunk -
 constexpr int T_SINK = T_NST * T_STAGE;   // 1 KiB per wave
 constexpr int T_SMEM = T_SINK + 4096;
 
-__device__ __attribute__((aligned(16))) uint32_t g_sink_t[64 * 4];   // stores of rows past Tq (so that they can be counted)
-
-__device__ __forceinline__ void xt_dma16(const void *src, void *lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
-}
-
-template <int DT>
-__device__ __forceinline__ void xt_mfma(f32x16 &c, typename Op<DT>::V8 a, typename Op<DT>::V8 b) {  // acc in AGPRs
-    if constexpr (DT == PIO_DT_F16) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-    else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-}
-// (macros: an asm operand may name a vector element, a reference may not)
-__device__ __forceinline__ float xt_acc_read(float a) {
-    float v;
-    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a));
-    return v;
-}
+// (a macro: an asm operand may name a vector element, a reference may not)
 #define XT_ACC_WRITE(dst, val) asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(dst) : "v"(val))
 
 template <int DT>
@@ -189,11 +162,11 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
             // (signed: the column correction of a chunk past the row pitch is negative and may exceed a small row offset --
             //  the chunk's base pointer, which already carries cb * 64, makes up for it)
             const int32_t o = i_b ? (int32_t)voff[i] + i_vadj : (int32_t)koff[i];
-            xt_dma16(i_src0 + 2 * (int64_t)o, i_dst + i * i_step);
+            lds_dma16(i_src0 + 2 * (int64_t)o, i_dst + i * i_step);
         } else {
             uint32_t &o = qoff[i & 1];
             asm volatile("" : "+v"(o));
-            xt_dma16(i_src1 + 2 * (uint64_t)o, i_dstq + (i - 8) * i_stepq);
+            lds_dma16(i_src1 + 2 * (uint64_t)o, i_dstq + (i - 8) * i_stepq);
         }
     };
 
@@ -213,9 +186,9 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
 
     // ---- prologue: chunks 0, 1 in flight (both phase A: nka >= 2); chunk 0 landed
     issue_begin(0, 0);
-    xt_for<0, T_NP>([&](auto PI) { issue_piece(PI); });
+    static_for<0, T_NP>([&](auto PI) { issue_piece(PI); });
     issue_begin(1, 1);
-    xt_for<0, T_NP>([&](auto PI) { issue_piece(PI); });
+    static_for<0, T_NP>([&](auto PI) { issue_piece(PI); });
 
     f32x16 sacc[T_NKB];
     {
@@ -256,9 +229,9 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
         const int nslot2 = slot == 0 ? 2 : slot - 1;          // stage of chunk c + 2 (= of chunk c - 1: free)
         const char *stn = smem + nslot1 * T_STAGE;
         issue_begin(c + 2, nslot2);
-        xt_for<0, 32>([&](auto FI) {
+        static_for<0, 32>([&](auto FI) {
             constexpr int f = decltype(FI)::value;
-            xt_mfma<DT>(sacc[f & 15], kf[f & 7], qf[f >> 4]);
+            mfma32_agpr<DT>(sacc[f & 15], kf[f & 7], qf[f >> 4]);
             if constexpr ((f & 1) == 0 && f < 2 * T_NP) issue_piece(std::integral_constant<int, f / 2>{});
             if constexpr (f + 8 < 32) kf[f & 7] = k_read(st, f + 8);
             if constexpr (f == 27) {
@@ -313,7 +286,7 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
             float m0 = -INFINITY, m1 = -INFINITY;
 #pragma unroll
             for (int i = 0; i < 16; i += 2) {
-                float v0 = xt_acc_read(sacc[kb][i]), v1 = xt_acc_read(sacc[kb][i + 1]);
+                float v0 = acc_read_ordered(sacc[kb][i]), v1 = acc_read_ordered(sacc[kb][i + 1]);
                 if constexpr (MASKED) {
                     v0 = ((bits >> (16 * (i >> 3) + (i & 7))) & 1u) ? v0 : -INFINITY;
                     v1 = ((bits >> (16 * ((i + 1) >> 3) + ((i + 1) & 7))) & 1u) ? v1 : -INFINITY;
@@ -334,7 +307,7 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
             for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    float v = xt_acc_read(sacc[kb][8 * s2 + j]);
+                    float v = acc_read_ordered(sacc[kb][8 * s2 + j]);
                     if constexpr (MASKED) v = ((bits >> (16 * s2 + j)) & 1u) ? v : -INFINITY;
                     const float e = __builtin_amdgcn_exp2f(fmaf(v, p.scale_log2, -m_use));
                     psum += e;
@@ -357,7 +330,7 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
     auto v_read = [&](const char *st, int f) { return *(const V8 *)(st + va[f >> 3] + 4096 * (f & 7)); };
     const int64_t obase = b * p.sOb + (int64_t)q * p.ldo + (int64_t)h * p.dvp;
     bool after_epilogue = false;
-    char *const gsink = (char *)g_sink_t + lane * 16;
+    char *const gsink = (char *)g_sink + lane * 16;   // stores of rows past Tq (so that they can be counted)
 #pragma unroll 1
     for (int pass = 0; pass < p.npass; ++pass) {
         {
@@ -375,16 +348,16 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_nop 7" ::: "memory");  // VALU write of the zeroed O^T (and of P^T) -> MFMA operands
         __builtin_amdgcn_sched_barrier(0);
-        xt_for<0, 8>([&](auto CBI) {
+        static_for<0, 8>([&](auto CBI) {
             constexpr int cb = decltype(CBI)::value;
             const char *st = smem + slot * T_STAGE;
             const int nslot1 = slot == 2 ? 0 : slot + 1;
             const int nslot2 = slot == 0 ? 2 : slot - 1;
             const char *stn = smem + nslot1 * T_STAGE;
             issue_begin(n_a + pass * 8 + cb + 2, nslot2);
-            xt_for<0, 32>([&](auto FI) {
+            static_for<0, 32>([&](auto FI) {
                 constexpr int f = decltype(FI)::value;
-                xt_mfma<DT>(oacc[f & 7], vf[f & 7], pf[4 * cb + (f >> 3)]);
+                mfma32_agpr<DT>(oacc[f & 7], vf[f & 7], pf[4 * cb + (f >> 3)]);
                 if constexpr ((f & 1) == 0 && f < 2 * T_NP) issue_piece(std::integral_constant<int, f / 2>{});
                 if constexpr (f + 8 < 32) vf[f & 7] = v_read(st, f + 8);
                 if constexpr (f == 27) {
@@ -430,7 +403,7 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
                     V4 o, l;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const float v = xt_acc_read(oacc[d][4 * g4 + j]) * inv;
+                        const float v = acc_read_ordered(oacc[d][4 * g4 + j]) * inv;
                         o[j] = Op<DT>::from_f32(v);
                         l[j] = Op<DT>::from_f32(v - Op<DT>::to_f32(o[j]));
                     }

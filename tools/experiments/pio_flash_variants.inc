@@ -4,14 +4,6 @@
 // (DESIGN_LOG.md), so they are not part of libpio_hip.so: this file is included by pio_flash.hip only when it is built
 // with -DPIO_EXPERIMENTS (make -C perceiverio_pytorch_amd/csrc experiments -> tools/_abl/libpio_hip_exp.so).
 
-template <int I, int N, class F>
-__device__ __forceinline__ void fl_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        fl_for<I + 1, N>(f);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // The same attention for the hot shape of the latent self-attend stack (128-wide heads, V row-major out of the fused
 // q|k|v GEMM, 256-query workgroups of 8 waves = 2 per SIMD) with the two waves of a SIMD STAGGERED by half a key tile.
@@ -204,7 +196,7 @@ __global__ __launch_bounds__(512, 1) void flash_attn_stag_kernel(const FlashPara
             }
         };
         rd(std::integral_constant<int, 0>{}, 0);
-        fl_for<0, NDT>([&](auto DC) __attribute__((always_inline)) {
+        static_for<0, NDT>([&](auto DC) __attribute__((always_inline)) {
             constexpr int d = decltype(DC)::value;
             constexpr int bi = d & 1;
             if constexpr (d + 1 < NDT) {
@@ -632,7 +624,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pipe_kernel(const FlashPara
         const float nmA = sm_head(PC, I0{});
         const float nmB = sm_head(PC, I1{});
         __builtin_amdgcn_sched_barrier(0);
-        fl_for<0, 32>([&](auto IC) __attribute__((always_inline)) {
+        static_for<0, 32>([&](auto IC) __attribute__((always_inline)) {
             constexpr int i = decltype(IC)::value;
             constexpr int f = i >> 1, X = i & 1, t = f >> 3, s = f & 7;
             if constexpr (DO_S) {
@@ -653,7 +645,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pipe_kernel(const FlashPara
         vfr[0] = vread(I0{});
         vfr[1] = vread(I1{});
         __builtin_amdgcn_sched_barrier(0);
-        fl_for<0, 16>([&](auto JC) __attribute__((always_inline)) {
+        static_for<0, 16>([&](auto JC) __attribute__((always_inline)) {
             constexpr int j = decltype(JC)::value;
             if constexpr (j + 2 < 16) vfr[(j + 2) & 3] = vread(std::integral_constant<int, (j + 2) & 15>{});
             fp_wait_lds<(j + 2 < 16) ? 4 : 2 * (15 - j)>();
@@ -702,7 +694,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pipe_kernel(const FlashPara
         V8 kfr[4];
         kfr[0] = kread(I0{});
         kfr[1] = kread(I1{});
-        fl_for<0, 32>([&](auto IC) __attribute__((always_inline)) {
+        static_for<0, 32>([&](auto IC) __attribute__((always_inline)) {
             constexpr int i = decltype(IC)::value;
             constexpr int f = i >> 1, X = i & 1, t = f >> 3, s = f & 7;
             if constexpr (X == 0) {

@@ -15,8 +15,6 @@
 // permutation and epilogue column mapping are those of pio_gemm_wide.hip.
 //
 // Reference semantics: x + Linear(...) of transformer_primitives.py:290-292.
-#include <type_traits>
-
 #include "../../perceiverio_pytorch_amd/csrc/pio_gemm_common.h"
 
 namespace pio {
@@ -30,22 +28,6 @@ constexpr int D_SINK = D_RING;                 // 4 x 1 KiB: pieces past the end
 constexpr int D_BIAS = D_SINK + 4 * 1024;      // 4 x 512 B: per-wave bias rows
 constexpr int D_SMEM = D_BIAS + 4 * 512;       // 78 KiB: two workgroups per CU
 
-static __device__ __attribute__((aligned(16))) uint32_t g_sink_d[64 * 4];
-static __device__ __attribute__((aligned(16))) uint32_t g_zero_d[4] = {0, 0, 0, 0};
-
-template <int I, int N, class F>
-__device__ __forceinline__ void duo_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        duo_for<I + 1, N>(f);
-    }
-}
-
-__device__ __forceinline__ void duo_dma16(const void *src, void *lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
-}
-
 template <int DT>
 __device__ __forceinline__ void duo_mfma(f32x4 &c, typename Op<DT>::V8 a, typename Op<DT>::V8 b) {
     if constexpr (DT == PIO_DT_F16) asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
@@ -55,11 +37,6 @@ template <int DT>
 __device__ __forceinline__ void duo_mfma_first(f32x4 &c, typename Op<DT>::V8 a, typename Op<DT>::V8 b) {
     if constexpr (DT == PIO_DT_F16) asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
     else asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ float duo_acc_read(float a) {
-    float v;
-    asm("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a));
-    return v;
 }
 
 template <int DT>
@@ -135,8 +112,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_duo(const GemmParams p, int ti
     auto piece = [&](int i) {  // 0..1: A, 2..5: B
         uint32_t &o = i < 2 ? voa[i] : vob[i - 2];
         asm volatile("" : "+v"(o));
-        if (i < 2) duo_dma16(ia + (uint64_t)o, isb + ioa + i * istep);
-        else duo_dma16(ib + (uint64_t)o, isb + iob + (i - 2) * istep);
+        if (i < 2) lds_dma16(ia + (uint64_t)o, isb + ioa + i * istep);
+        else lds_dma16(ib + (uint64_t)o, isb + iob + (i - 2) * istep);
     };
 
     // ---- MFMA side (layout as pio_gemm_wide.hip)
@@ -153,13 +130,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_duo(const GemmParams p, int ti
     const int o_n0 = tn * D_BN + wn * 128;
     const int o_n = o_n0 + fq * 8;
     float *const bstash = (float *)(smem + D_BIAS + wave * 512);
-    char *const sink = (char *)g_sink_d + lane * 16;
+    char *const sink = (char *)g_sink + lane * 16;
 
     // ---- prologue: bias row, slices 0..2 in flight, slice 0 landed and in the fragment registers
     if (lane < 32) {
         const int n = o_n0 + lane * 4;
-        const float *src = (p.bias_mode == 1 && n < p.N) ? p.bias + n : (const float *)g_zero_d;
-        duo_dma16(src, bstash);
+        const float *src = (p.bias_mode == 1 && n < p.N) ? p.bias + n : (const float *)g_zero16;
+        lds_dma16(src, bstash);
     }
 #pragma unroll
     for (int s = 0; s < 3; ++s) {  // (unrolled: the offset arrays must stay in registers)
@@ -179,7 +156,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_duo(const GemmParams p, int ti
         constexpr int P = decltype(PC)::value;
         constexpr bool FIRST = decltype(FC)::value;
         const char *rb = smem + rslot * D_STAGE;
-        duo_for<0, 8>([&](auto NI) {
+        static_for<0, 8>([&](auto NI) {
             constexpr int ni = decltype(NI)::value;
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi) {
@@ -250,8 +227,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_duo(const GemmParams p, int ti
             f32x4 x0, x1;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                x0[r] = duo_acc_read(acc[mi][2 * pp][r]) + b0[r] + (Op<DT>::to_f32(hh[r]) + Op<DT>::to_f32(ll[r]));
-                x1[r] = duo_acc_read(acc[mi][2 * pp + 1][r]) + b1[r] +
+                x0[r] = acc_read(acc[mi][2 * pp][r]) + b0[r] + (Op<DT>::to_f32(hh[r]) + Op<DT>::to_f32(ll[r]));
+                x1[r] = acc_read(acc[mi][2 * pp + 1][r]) + b1[r] +
                         (Op<DT>::to_f32(hh[4 + r]) + Op<DT>::to_f32(ll[4 + r]));
             }
             if (!interior && n >= p.N) {
