@@ -430,6 +430,40 @@ typedef struct pio_query_segment_t {
 int pio_build_queries(const pio_query_segment_t *segs, int32_t nseg, float *y, int64_t ldy, int32_t Qtot, int32_t Cq,
                       void *stream);
 
+/* One row segment of pio_project_heads: rows [row0, row0 + rows) of every sample of x go through the head (w, bias) into y.
+ *   y[b*y_sb + r*y_rs + j] = bias[j] + sum_k w[j*ldw + k] * x[b*x_sb + (row0 + r)*ldx + k],  r in [0, rows), j in [0, n_out)
+ * bias may be NULL (nothing is added); rows may be 0 (the segment does nothing, its pointers are still checked). */
+#define PIO_MAX_HEAD_SEGMENTS 4
+typedef struct pio_head_segment_t {
+    int32_t row0, rows; /* rows [row0, row0 + rows) of every sample of x */
+    const float *w;     /* [n_out, K] fp32, row pitch ldw >= K */
+    int64_t ldw;
+    const float *bias;  /* [n_out] fp32 or NULL */
+    int32_t n_out;      /* 1 .. 16 */
+    float *y;           /* y[b*y_sb + r*y_rs + j], r in [0, rows), j < n_out */
+    int64_t y_sb, y_rs;
+} pio_head_segment_t;
+
+/* The narrow linear heads behind the decoder of a multi-modality model (postprocessors.py ProjectionPostprocessor /
+ * AudioPostprocessor: an nn.Linear on a row range of the decoder output) as ONE launch: nseg (1 .. 4) segments of
+ * x [B, Q, K] fp32 (row pitch ldx, sample stride x_sb; x_sb is not read when B == 1), each multiplied by its own
+ * [n_out, K] fp32 weights and written straight into its own output array.  x is read once, as fp32, and the products are
+ * fp32 FMAs: nothing is rounded to 16 bits, no temporary is made.  Rows of x that no segment covers are not read; of y only
+ * the n_out columns of the rows [0, rows) of every sample are written: [n_out, y_rs) and everything else stay untouched.
+ * Summation order (part of the definition): with lane l = (k / 4) % 64 and sweep i = k / 256,
+ *   p_l = +0;  for i ascending, for k = 4*(l + 64*i) .. + 3 ascending (k < K):  p_l = fmaf(w[j, k], x[k], p_l)
+ *   s   = pairwise tree over the 64 p_l: offsets 32, 16, 8, 4, 2, 1,  p_l = fadd_rn(p_l, p_(l xor offset))
+ *   y   = bias ? fadd_rn(s, bias[j]) : s
+ * so the bits of an output row depend only on that row of x, the segment's w, bias, n_out and K -- not on B, Q, row0, rows,
+ * the strides, the other segments or the position of the row in the launch; there are no atomics.  A NaN in a row of x makes
+ * the n_out outputs of that row NaN and no others.  No workspace, no device allocation, no synchronisation.
+ * PIO_E_ARG: NULL segs / x / w / y, nseg outside [1, 4]; PIO_E_SHAPE: B or Q < 1, K outside [4, 1024] or not a multiple of
+ * 4, ldx < K, n_out outside [1, 16], rows < 0, a segment outside [0, Q), ldw < K, y_rs < n_out, two non-empty segments whose
+ * row ranges overlap, B * sum ceil(rows / 64) workgroups beyond 2^31 - 1; PIO_E_ALIGN: x or w not 16-byte aligned, ldx, ldw
+ * or x_sb not a multiple of 4, y or bias not 4-byte aligned.  A refused call launches nothing. */
+int pio_project_heads(const pio_head_segment_t *segs, int32_t nseg, const float *x, int64_t x_sb, int64_t ldx,
+                      int32_t B, int32_t Q, int32_t K, void *stream);
+
 /* The language front end (io_processors.py EmbeddingPreprocessor: embed(ids) + learned position embedding) as ONE launch.
  * ids [B, T] int32 (id_bytes 4) or int64 (id_bytes 8), t contiguous, sample stride ids_sb elements; table [V, C] fp32 (row
  * pitch ldt); pos [T, C] fp32 (row pitch ldp); y [B, T, C] fp32 (row pitch ldy, sample stride y_sb); tokens: optional

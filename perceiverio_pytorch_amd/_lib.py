@@ -98,6 +98,15 @@ class QuerySegment(C.Structure):
                 ("concat_pos", C.c_int32), ("sine_only", C.c_int32), ("C", C.c_int32)]
 
 
+PIO_MAX_HEAD_SEGMENTS = 4
+
+
+class HeadSegment(C.Structure):
+    """pio_head_segment_t: one row segment of pio_project_heads (rows of the decoder output through one narrow fp32 head)."""
+    _fields_ = [("row0", C.c_int32), ("rows", C.c_int32), ("w", C.c_void_p), ("ldw", C.c_int64), ("bias", C.c_void_p),
+                ("n_out", C.c_int32), ("y", C.c_void_p), ("y_sb", C.c_int64), ("y_rs", C.c_int64)]
+
+
 PIO_MAX_BLEND_AXIS = 64
 PIO_MAX_BLEND_GROUPS = 64
 
@@ -162,6 +171,7 @@ SIGNATURES = {
                                         _i32, _i32, _vp]),
     "pio_assemble_tokens": (C.c_int, [P(TokenSegment), _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "pio_build_queries": (C.c_int, [P(QuerySegment), _i32, _vp, _i64, _i32, _i32, _vp]),
+    "pio_project_heads": (C.c_int, [P(HeadSegment), _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "pio_embed_tokens": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32,
                                    _i32, _i32, _vp]),
     "pio_flow_blend_tiles": (C.c_int, [P(FlowBlend), _vp, _i64, _i64, _i64, _vp]),

@@ -213,6 +213,11 @@ int pio_build_queries(const pio_query_segment_t *segs, int32_t nseg, float *y, i
     return build_queries_launch(segs, nseg, y, ldy, Qtot, Cq, (hipStream_t)stream);
 }
 
+int pio_project_heads(const pio_head_segment_t *segs, int32_t nseg, const float *x, int64_t x_sb, int64_t ldx,
+                      int32_t B, int32_t Q, int32_t K, void *stream) {
+    return project_heads_launch(segs, nseg, x, x_sb, ldx, B, Q, K, (hipStream_t)stream);
+}
+
 int pio_embed_tokens(const void *ids, int32_t id_bytes, int64_t ids_sb, const float *table, int64_t ldt, int32_t V,
                      const float *pos, int64_t ldp, float *y, int64_t y_sb, int64_t ldy, float *tokens, int64_t tok_sb,
                      int64_t ldtok, int32_t *bad_ids, int32_t B, int32_t T, int32_t C, void *stream) {

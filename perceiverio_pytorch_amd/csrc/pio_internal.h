@@ -147,6 +147,9 @@ int embed_tokens_launch(const void *ids, int id_bytes, int64_t ids_sb, const flo
 int flow_blend_tiles_launch(const pio_flow_blend_t *p, float *out, int64_t on, int64_t oc, int64_t oy, hipStream_t s);
 // decoder queries: Fourier features of index points | learned table, each with its padding embedding, up to 4 row segments
 int build_queries_launch(const pio_query_segment_t *segs, int nseg, float *y, int64_t ldy, int Qtot, int Cq, hipStream_t s);
+// output heads: up to 4 row segments of the decoder output, each through its own narrow fp32 linear head, written in place
+int project_heads_launch(const pio_head_segment_t *segs, int nseg, const float *x, int64_t x_sb, int64_t ldx, int B, int Q,
+                         int K, hipStream_t s);
 int pack_linear_launch(const float *w, const float *bias, int out, int in, int64_t ldw, int row_heads,
                        int col_heads, void *dst_hi, void *dst_lo, float *dst_bias, int dst_row0, int k_pad,
                        int dtype, hipStream_t s);

@@ -479,6 +479,20 @@ class MultiModalPerceiver(nn.Module):
     def fused_queries(self, on: bool) -> None:
         self.perceiver.fused_queries = bool(on)
 
+    # The two narrow heads behind the decoder -- image 512 -> 3, audio 512 -> 16 -- are ONE HIP launch per decoder call
+    # (PerceiverIO.fused_heads -> pio_project_heads) that reads the fp32 decoder output once and, with encode_once, writes
+    # each group's rows straight into the final image / audio arrays: no 16-bit copy of the decoder output, no per-group
+    # pieces, no torch.cat.  fp32 products of the unrounded decoder output, where the chain multiplies its 16-bit image.
+    # False restores the chain (runtime.hip_linear per head, torch.cat behind the loop) exactly.  The label head is the
+    # chain's either way.
+    @property
+    def fused_heads(self) -> bool:
+        return self.perceiver.fused_heads
+
+    @fused_heads.setter
+    def fused_heads(self, on: bool) -> None:
+        self.perceiver.fused_heads = bool(on)
+
     def forward(self, images: torch.Tensor, audio: torch.Tensor, n_chunks: int = 128):
         with _policy_scope(self):
             return self._forward(images, audio, n_chunks)
@@ -528,6 +542,7 @@ class MultiModalPerceiver(nn.Module):
         P = self.perceiver
         rec = {"image": [], "audio": [], "label": []}
         cached = None
+        bufs, tied = None, []       # (fused heads: the final image / audio arrays, made once; the group views that wrote them)
         step = self.decode_chunks_per_call if self.encode_once else 1
         for k in range(0, n_chunks, step):
             g = min(step, n_chunks - k)
@@ -550,13 +565,36 @@ class MultiModalPerceiver(nn.Module):
                 with precision(P.decoder_policy):
                     # (qc: LayerNorm_q + proj_q of a cached -- parameter-only -- query array run once, not per forward:
                     #  206 MB of projected queries per group of 16 chunks at the default policy)
-                    per_mod = restructure(qsizes, P._decoder(query, latents, q_cache=qc if self.cache_projected_queries
-                                                             else None))
-                    out = {m: post(per_mod[m], pos=None, modality_sizes=None)
-                           for m, post in P._output_postprocessors.items()}
-            rec["image"].append(out["image"])
-            rec["audio"].append(out["audio"])
+                    decoded = P._decoder(query, latents, q_cache=qc if self.cache_projected_queries else None)
+                    # (fused heads: every group writes its rows of the final arrays in place -- no per-group pieces, no
+                    #  torch.cat behind the loop.  The decision does not depend on the group: taken at the first one.)
+                    if k == 0 and P._heads_accept(decoded):
+                        patch = self.audio_samples_per_patch
+                        bufs = {"image": torch.empty((b, img_chunk * n_chunks, c), dtype=torch.float32, device=dev),
+                                "audio": torch.empty((b, aud_chunk * n_chunks, patch), dtype=torch.float32, device=dev)}
+                    out = None
+                    if bufs is not None:
+                        into = {"image": bufs["image"][:, img_chunk * k:img_chunk * (k + g)],
+                                "audio": bufs["audio"][:, aud_chunk * k:aud_chunk * (k + g)]}
+                        out = P._project_heads(decoded, qsizes, into=into)
+                        if out is not None:
+                            tied += [out["image"], out["audio"]]
+                    if out is None:
+                        per_mod = restructure(qsizes, decoded)
+                        out = {m: post(per_mod[m], pos=None, modality_sizes=None)
+                               for m, post in P._output_postprocessors.items()}
+                        if bufs is not None:
+                            for m in into:
+                                into[m].copy_(out[m].reshape(into[m].shape))
+            if bufs is None:
+                rec["image"].append(out["image"])
+                rec["audio"].append(out["audio"])
             rec["label"].extend([out["label"][:, None]] * g)      # (one label estimate per chunk, as the reference has)
-        return {"image": torch.cat(rec["image"], dim=1).reshape([b, t, h, w, c]).moveaxis(-1, -3),
-                "audio": torch.cat(rec["audio"], dim=1).reshape(audio.shape),
+        if bufs is not None:
+            from . import runtime as R
+            image, sound = R.forward_only(bufs["image"], *tied), R.forward_only(bufs["audio"], *tied)
+        else:
+            image, sound = torch.cat(rec["image"], dim=1), torch.cat(rec["audio"], dim=1)
+        return {"image": image.reshape([b, t, h, w, c]).moveaxis(-1, -3),
+                "audio": sound.reshape(audio.shape),
                 "label": torch.cat(rec["label"], dim=1).mean(dim=1)}

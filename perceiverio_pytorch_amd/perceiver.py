@@ -743,6 +743,122 @@ class PerceiverIO(nn.Module):
         y = R.forward_only(y, *deps)
         return torch.broadcast_to(y, (inputs.shape[0], qtot, cq)), {m: plan[m].M for m in names}
 
+    # One HIP launch (pio_project_heads) instead of one runtime.hip_linear chain per narrow output head (row slice copy,
+    # 16-bit cast, GEMM, result copied into place), for a multi-modality model: see _project_heads.  fp32 products of the
+    # unrounded decoder output.  False, and every configuration it declines, runs the chain exactly as before.
+    fused_heads = True
+
+    @staticmethod
+    def _head_linear(post):
+        """The nn.Linear of a narrow head pio_project_heads can stand for, or None."""
+        from .io_processors import AudioPostprocessor, ProjectionPostprocessor
+        if type(post) is ProjectionPostprocessor:
+            return post.projection
+        if type(post) is AudioPostprocessor:
+            return post.linear
+        return None
+
+    def _heads_eligible(self, k: int) -> bool:
+        """The part of _project_heads' decision that the modules alone settle, for decoder rows of k channels: the switch, at
+        least two output modalities, no active range probe (the chain then keeps its "cast" records), every postprocessor a
+        ProjectionPostprocessor / AudioPostprocessor with fp32 [n_out <= 16, k] weights or a ClassificationPostprocessor,
+        at least one and at most four of the former, k a multiple of 4 in [4, 1024].  Row counts, the batch and the chunk
+        grouping play no part: a forward takes one path for all of its decoder calls."""
+        from .io_processors import ClassificationPostprocessor
+        posts = self._output_postprocessors
+        if not self.fused_heads or posts is None or len(posts) < 2 or LP.range_active():
+            return False
+        if k < 4 or k > 1024 or k % 4:
+            return False
+        narrow = 0
+        for post in posts.values():
+            if type(post) is ClassificationPostprocessor:
+                continue
+            lin = self._head_linear(post)
+            if lin is None:
+                return False
+            w, b = lin.weight, lin.bias
+            if (w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] != k or not 1 <= w.shape[0] <= 16
+                    or (b is not None and (b.dtype != torch.float32 or b.device != w.device))):
+                return False
+            narrow += 1
+        return 1 <= narrow <= L.PIO_MAX_HEAD_SEGMENTS
+
+    def _heads_accept(self, outputs) -> bool:
+        """True when _project_heads takes this decoder output: the hip backend, a CUDA fp32 [B, Q, K] tensor with unit channel
+        stride and 16-byte aligned rows, heads on its device, and _heads_eligible(K)."""
+        if (R.get_backend() != "hip" or not isinstance(outputs, torch.Tensor) or not outputs.is_cuda
+                or outputs.dtype != torch.float32 or outputs.dim() != 3 or outputs.stride(2) != 1):
+            return False
+        if not self._heads_eligible(outputs.shape[2]):
+            return False
+        if outputs.data_ptr() % 16 or outputs.stride(1) % 4 or (outputs.shape[0] > 1 and outputs.stride(0) % 4):
+            return False
+        return all(lin is None or lin.weight.device == outputs.device
+                   for lin in map(self._head_linear, self._output_postprocessors.values()))
+
+    def _project_heads(self, outputs, query_sizes, into=None):
+        """The dict of postprocessed outputs of a decoder output [B, Q, K] from ONE pio_project_heads call for the narrow
+        heads (plus the ClassificationPostprocessor's own hip_linear on row 0, unchanged), or None when it declines
+        (_heads_accept).  `into`: optional {modality: fp32 [B, rows, n_out] view with unit last stride} -- that head's rows are
+        written there, in place (MultiModalPerceiver: the group's rows of the final output array), and the view is what the
+        dict holds for it; without it a ProjectionPostprocessor returns a fresh [B, rows, n_out] array and an
+        AudioPostprocessor a fresh [B, rows * n_out], as the chain does."""
+        from .io_processors import AudioPostprocessor
+        posts = self._output_postprocessors
+        if not self._heads_accept(outputs) or sorted(query_sizes.keys()) != sorted(posts.keys()):
+            return None
+        if sum(query_sizes.values()) > outputs.shape[1]:
+            return None
+        batch, qtot, k = outputs.shape
+        dev = outputs.device
+        row0, start = {}, 0
+        for m in sorted(query_sizes.keys()):
+            row0[m] = start
+            start += query_sizes[m]
+        plan, keep, ys = [], [], {}
+        for m, post in posts.items():
+            lin = self._head_linear(post)
+            if lin is None:
+                continue
+            w = lin.weight.detach()
+            if w.stride(1) != 1 or w.stride(0) % 4 or w.data_ptr() % 16:
+                w = w.contiguous()
+            b = None if lin.bias is None else lin.bias.detach().contiguous()
+            rows, n_out = query_sizes[m], w.shape[0]
+            y = into.get(m) if into is not None else None
+            if y is None:
+                y = torch.empty((batch, rows, n_out), dtype=torch.float32, device=dev)
+            elif (tuple(y.shape) != (batch, rows, n_out) or y.dtype != torch.float32 or y.device != dev
+                    or (rows > 0 and y.stride(2) != 1)):
+                raise ValueError(f"_project_heads: into[{m!r}] must be a float32 [{batch}, {rows}, {n_out}] view on {dev} "
+                                 "with unit last stride")
+            ys[m] = R.forward_only(y, outputs, lin.weight, lin.bias)
+            if rows < 1:
+                continue
+            seg = L.HeadSegment()
+            seg.row0, seg.rows, seg.n_out = row0[m], rows, n_out
+            seg.w, seg.ldw, seg.bias = w.data_ptr(), w.stride(0), None if b is None else b.data_ptr()
+            seg.y, seg.y_sb, seg.y_rs = y.data_ptr(), y.stride(0) if batch > 1 else 0, y.stride(1)
+            plan.append(seg)
+            keep += [w, b, y]
+        if plan:
+            segs = (L.HeadSegment * len(plan))(*plan)
+            with R.on_device(dev):
+                L.check(L.lib().pio_project_heads(segs, len(plan), outputs.data_ptr(),
+                                                  outputs.stride(0) if batch > 1 else 0, outputs.stride(1), batch, qtot, k,
+                                                  R.stream_ptr(dev)), "pio_project_heads")
+        per_mod = restructure(query_sizes, outputs)
+        result = {}
+        for m, post in posts.items():
+            if m not in ys:
+                result[m] = post(per_mod[m], pos=None, modality_sizes=None)
+            elif type(post) is AudioPostprocessor and (into is None or m not in into):
+                result[m] = ys[m].reshape(batch, -1)
+            else:
+                result[m] = ys[m]
+        return result
+
     def decoder_query(self, inputs, modality_sizes, inputs_without_pos=None, subsampled_points=None):
         per_mod = restructure(modality_sizes, inputs)
         subsampled_points = subsampled_points or {}
@@ -837,10 +953,13 @@ class PerceiverIO(nn.Module):
             else:
                 outputs = self._decoder(query, latents, query_mask=query_mask)
         if self._output_postprocessors:
-            per_mod = restructure(query_sizes, outputs)
             with R.precision(self.decoder_policy):       # (the heads behind the decoder belong to its half)
-                outputs = {m: post(per_mod[m], pos=None, modality_sizes=None)
-                           for m, post in self._output_postprocessors.items()}
+                heads = self._project_heads(outputs, query_sizes)
+                if heads is None:
+                    per_mod = restructure(query_sizes, outputs)
+                    heads = {m: post(per_mod[m], pos=None, modality_sizes=None)
+                             for m, post in self._output_postprocessors.items()}
+            outputs = heads
         if type(outputs) is not torch.Tensor and list(outputs.keys()) == ["__default"]:
             outputs = outputs["__default"]
         return outputs

@@ -9,6 +9,9 @@
                                                 16-chunk group [1, 100593, 1026] and the 8 groups of a 128-chunk forward,
                                                 the sine / cosine error of chain and kernel over tests/query_cases.py, and
                                                 the whole model with and without the query cache; prints one JSON line
+    python tools/prep_bench.py --multimodal-heads   the multimodal output heads (pio_project_heads) on one 16-chunk decoder
+                                                call [B, 100593, 512], B = 1 and B = 4, against the hip_linear chain;
+                                                prints one JSON line
     python tools/prep_bench.py --language-front     the language front end (pio_embed_tokens) at full size ([B, 2048, 768],
                                                 V = 262, int64 ids), B = 1, 8 and 100; prints one JSON line
     python tools/prep_bench.py --flow-blend         the tile blend of tiled flow inference (pio_flow_blend_tiles) against the
@@ -320,6 +323,106 @@ def decoder_queries(repeats, launches):
     print(json.dumps(result))
 
 
+def _device_ops(f):
+    """(kernels, copies) the device runs for one call of f, from torch.profiler's device events; None where the profiler
+    gives none (not measured)."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        f()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            f()
+            torch.cuda.synchronize()
+        names = [e.name for e in prof.events() if str(e.device_type).endswith("CUDA")]
+    except Exception as exc:                             # noqa: BLE001 (a tool: report, do not guess)
+        print(f"torch.profiler unavailable: {exc!r}", file=sys.stderr)
+        return None
+    if not names:
+        return None
+    copies = [n for n in names if "memcpy" in n.lower() or "memset" in n.lower() or "copy" in n.lower()]
+    return {"kernels": len(names) - len(copies), "copies": len(copies), "names": sorted(set(names))}
+
+
+def multimodal_heads(repeats, launches):
+    """The output heads of the default MultiModalPerceiver on ONE decoder call of a 16-chunk group ([B, 100 593, 512] fp32:
+    240 audio + 100 352 image + 1 label rows), B = 1 and B = 4, timed like multimodal_front, the ways alternating inside
+    every repeat, under the model's decoder policy:
+      chain -- fused_heads = False: restructure + the three postprocessors through runtime.hip_linear (row slice copy for
+               B > 1, 16-bit cast(s), GEMM, a fresh result per head); the torch.cat behind the model's loop is NOT included
+      fused -- PerceiverIO._project_heads with into= views of the final image / audio arrays (one pio_project_heads launch +
+               the label head's hip_linear on row 0)
+      entry -- pio_project_heads alone, into resident outputs: the kernel's read bandwidth over the bytes of the covered rows
+    Reported per way: median and (min, max) of the repeats in microseconds, the peak memory above the inputs, the device
+    kernels and copies of one call (torch.profiler; null where it reports nothing)."""
+    from perceiverio_pytorch_amd import _lib as L
+    from perceiverio_pytorch_amd.models import MultiModalPerceiver, split_policy
+    from perceiverio_pytorch_amd.perceiver import restructure
+    from perceiverio_pytorch_amd.runtime import precision
+    torch.manual_seed(3)
+    model = MultiModalPerceiver().to(dev).eval()
+    P = model.perceiver
+    posts = P._output_postprocessors
+    sizes = {"audio": 240, "image": 100352, "label": 1}
+    q, k = sum(sizes.values()), 512
+    result = {"tool": "tools/prep_bench.py --multimodal-heads", "repeats": repeats, "launches_per_repeat": launches,
+              "unit": "us", "policy": model.precision_policy, "rows": sizes, "K": k, "cases": {}}
+    lib, stream = L.lib(), torch.cuda.current_stream().cuda_stream
+    for b in (1, 4):
+        x = torch.randn(b, q, k, device=dev)
+        final = {"image": torch.empty(b, 8 * sizes["image"], 3, device=dev),
+                 "audio": torch.empty(b, 8 * sizes["audio"], 16, device=dev)}
+        into = {m: final[m][:, 3 * sizes[m]:4 * sizes[m]] for m in final}
+        segs = (L.HeadSegment * 2)()
+        for i, (m, lin, row0) in enumerate((("audio", posts["audio"].linear, 0), ("image", posts["image"].projection, 240))):
+            s = segs[i]
+            s.row0, s.rows, s.n_out, s.w, s.ldw, s.bias = row0, sizes[m], lin.weight.shape[0], lin.weight.data_ptr(), k, lin.bias.data_ptr()
+            s.y, s.y_sb, s.y_rs = into[m].data_ptr(), into[m].stride(0), into[m].stride(1)
+
+        def chain():
+            P.fused_heads = False
+            per_mod = restructure(sizes, x)
+            return {m: post(per_mod[m], pos=None, modality_sizes=None) for m, post in posts.items()}
+
+        def fused():
+            P.fused_heads = True
+            return P._project_heads(x, sizes, into=into)
+
+        def entry():
+            L.check(lib.pio_project_heads(segs, 2, x.data_ptr(), x.stride(0), x.stride(1), b, q, k, stream), "pio_project_heads")
+        ways = {"chain": chain, "fused": fused, "entry": entry}
+        with precision(split_policy(model.precision_policy)[1]):
+            a, f = chain(), fused()
+            assert f is not None, "the fused path declined"
+            diff = {m: float((a[m].reshape(f[m].shape) - f[m]).abs().max()) for m in ("image", "audio", "label")}
+            del a, f
+            peak, ops = {}, {}
+            for name, fn in ways.items():
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                base = torch.cuda.memory_allocated()
+                torch.cuda.reset_peak_memory_stats()
+                fn()
+                torch.cuda.synchronize()
+                peak[name] = torch.cuda.max_memory_allocated() - base
+                ops[name] = _device_ops(fn)
+            times = {name: [] for name in ways}
+            for _ in range(repeats):
+                for name, fn in ways.items():
+                    times[name].append(timed(fn, launches))
+        case = {name: {"median": statistics.median(v), "min": min(v), "max": max(v), "peak_bytes_above_inputs": peak[name],
+                       "device_ops_per_call": ops[name]} for name, v in times.items()}
+        read = 4.0 * b * (sizes["audio"] + sizes["image"]) * k
+        case["entry"]["read_bytes"] = read
+        case["entry"]["read_GB_per_s_at_median"] = read / (case["entry"]["median"] * 1e-6) / 1e9
+        spread = (case["chain"]["max"] - case["chain"]["min"]) + (case["fused"]["max"] - case["fused"]["min"])
+        case.update(x_shape=[b, q, k], max_abs_chain_minus_fused=diff, chain_minus_fused_median=case["chain"]["median"] -
+                    case["fused"]["median"], both_spreads=spread)
+        result["cases"][f"B={b}"] = case
+        del x, final, into
+        torch.cuda.empty_cache()
+    print(json.dumps(result))
+
+
 def language_front(repeats, launches):
     """The encoder input of the default LanguagePerceiver (T = 2048, C = 768, V = 262, int64 ids) for B = 1, 8 and 100, timed
     like multimodal_front (device events around `launches` back-to-back calls after 3 warm-up calls, `repeats` times, the
@@ -528,6 +631,7 @@ if __name__ == "__main__":
     ap.add_argument("--flow-front", action="store_true", help="time pio_flow_patch_tokens against the torch chain")
     ap.add_argument("--multimodal-front", action="store_true", help="time pio_assemble_tokens against the torch chain")
     ap.add_argument("--decoder-queries", action="store_true", help="time pio_build_queries against the torch chain")
+    ap.add_argument("--multimodal-heads", action="store_true", help="time pio_project_heads against the hip_linear chain")
     ap.add_argument("--language-front", action="store_true", help="time pio_embed_tokens against the torch chain")
     ap.add_argument("--flow-blend", action="store_true", help="time pio_flow_blend_tiles against the torch chain")
     ap.add_argument("--flow-blend-forward", action="store_true", help="time the whole tiled forward of the flow model")
@@ -542,6 +646,8 @@ if __name__ == "__main__":
             multimodal_front(args.repeats, args.launches)
         elif args.decoder_queries:
             decoder_queries(args.repeats, args.launches)
+        elif args.multimodal_heads:
+            multimodal_heads(args.repeats, args.launches)
         elif args.language_front:
             language_front(args.repeats, args.launches)
         elif args.flow_blend:
