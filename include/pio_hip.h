@@ -524,6 +524,33 @@ typedef struct pio_flow_blend_t {
 } pio_flow_blend_t;
 int pio_flow_blend_tiles(const pio_flow_blend_t *p, float *out, int64_t on, int64_t oc, int64_t oy, void *stream);
 
+/* Optical-flow visualisation (utils/flow_utils.py flow_to_image, flow_utils.py:91-153 of the reference: the Middlebury
+ * colour wheel, every image scaled by its own largest radius) for a batch, as a memset of the b maxima words and TWO
+ * launches on the stream.  flow: fp32, element (n, y, x, component) at flow[n*sn + y*sy + x*sx + component*sc], read in
+ * place ([b, 2, h, w] and a permuted [h, w, 2] view alike; the stride of a dimension of size 1 is not read); out: contiguous
+ * uint8 [b, h, w, 3]; rad_max: b device words of scratch, overwritten (afterwards: each image's largest radius as an fp32
+ * bit pattern).  Per image n and pixel, (u, v) the two components:
+ *   has_clip:  u = u < 0 ? +0 : u, then u = u > clip_flow ? clip_flow : u, v likewise (np.clip; the lower bound IS 0; -0 stays)
+ *   rad  = sqrt_rn(fadd_rn(fmul_rn(u, u), fmul_rn(v, v)));   rad_max[n] = max over the pixels of image n, never of the batch
+ *   s    = fadd_rn(rad_max[n], 1e-5f);   un = fdiv_rn(u, s), vn = fdiv_rn(v, s);   radn = the rad of (un, vn)
+ *   fk   = (atan2f(-vn, -un) / pi + 1) / 2 * 54;   k0 = floor(fk) clamped to [0, 54];   k1 = k0 + 1, 55 -> 0;   f = fk - k0
+ *   col  = (1 - f) wheel[k0][ch] / 255 + f wheel[k1][ch] / 255;   col = radn <= 1 ? 1 - radn (1 - col) : 0.75 col
+ *   out[n, y, x, bgr ? 2 - ch : ch] = floor(255 col)
+ * Up to radn and the test radn <= 1 these are numpy's fp32 bits (every operation rounded on its own, no FMA; the maximum of
+ * non-negative floats is taken with an integer atomic max on the bit pattern, so it is exact and the same in every run).
+ * The wheel position and the colour run in fp32 where numpy goes through float64: a byte can differ from numpy's by one
+ * where 255 col lies within about 1e-3 of an integer.  The sign of a zero component is honoured (atan2(-0, -u) against
+ * atan2(+0, -u): wheel entry 0 against entry 54).  A non-finite flow value is undefined in the reference; here it yields
+ * unspecified bytes for its image and nothing else: k0 and the byte are clamped before they index or convert anything.
+ * The wheel (segments 15, 6, 4, 11, 13, 6) is a compile-time constant of the library.  A lane writes four consecutive
+ * pixels of the flat [b*h*w] list as three dwords when out is 4-byte aligned (the last, partial group byte by byte), bytes
+ * otherwise.  Only the 3*b*h*w bytes of out and the b words of rad_max are written.  No device allocation, no
+ * synchronisation; the call can be captured into a graph.
+ * PIO_E_ARG: NULL flow / out / rad_max; PIO_E_SHAPE: b, h or w < 1, h*w beyond 2^31 - 1, ceil(b*h*w / 1024) workgroups
+ * beyond 2^31 - 1; PIO_E_ALIGN: flow or rad_max not 4-byte aligned.  A refused call launches nothing. */
+int pio_flow_to_image(const float *flow, int64_t sn, int64_t sy, int64_t sx, int64_t sc, int32_t b, int32_t h, int32_t w,
+                      float clip_flow, int32_t has_clip, int32_t bgr, uint8_t *out, uint32_t *rad_max, void *stream);
+
 /* C = epilogue(alpha * A B^T): A [M,K], B [N,K] operand dtype, K contiguous (multiple of 8).
  * Batched over z = zb*nh + zh with element strides; bias_mode 0 none / 1 per column / 2 per row;
  * act 0 none / 1 exact-erf GELU (F.gelu, transformer_primitives.py:214); optional fp32 residual R

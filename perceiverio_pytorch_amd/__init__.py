@@ -5,5 +5,10 @@ from .runtime import (get_backend, get_precision_policy, invalidate_packed_weigh
 from ._lib import PioError, build, lib  # noqa: F401
 from .probe import (logit_probe, range_probe, recommend_operand_dtype,  # noqa: F401
                     recommend_precision_policy)
+from .flow_image import flow_to_image  # noqa: F401
+
+# flow_to_image of a CUDA fp32 tensor under the hip backend: pio_flow_to_image (two launches, nothing read back) when True;
+# False sends it down the torch restatement of the same formula (flow_image.restatement), which every other input takes
+fused_flow_image = True
 
 __version__ = "0.1.0"

@@ -229,6 +229,11 @@ int pio_flow_blend_tiles(const pio_flow_blend_t *p, float *out, int64_t on, int6
     return flow_blend_tiles_launch(p, out, on, oc, oy, (hipStream_t)stream);
 }
 
+int pio_flow_to_image(const float *flow, int64_t sn, int64_t sy, int64_t sx, int64_t sc, int32_t b, int32_t h, int32_t w,
+                      float clip_flow, int32_t has_clip, int32_t bgr, uint8_t *out, uint32_t *rad_max, void *stream) {
+    return flow_to_image_launch(flow, sn, sy, sx, sc, b, h, w, clip_flow, has_clip, bgr, out, rad_max, (hipStream_t)stream);
+}
+
 int pio_gemm_nt(const pio_gemm_t *g, void *stream) {
     if (!g) return PIO_E_ARG;
     return gemm_nt_launch(*g, (hipStream_t)stream);

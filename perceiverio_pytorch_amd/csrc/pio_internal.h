@@ -145,6 +145,9 @@ int embed_tokens_launch(const void *ids, int id_bytes, int64_t ids_sb, const flo
                         int64_t ldtok, int32_t *bad_ids, int B, int T, int C, hipStream_t s);
 // tiled flow inference: ramp-weighted sum of all tile flows over the summed ramps, in tile order
 int flow_blend_tiles_launch(const pio_flow_blend_t *p, float *out, int64_t on, int64_t oc, int64_t oy, hipStream_t s);
+// flow visualisation: the Middlebury colour wheel of a batch of flow fields, one maximum radius per image (two launches)
+int flow_to_image_launch(const float *flow, int64_t sn, int64_t sy, int64_t sx, int64_t sc, int b, int h, int w,
+                         float clip_flow, int has_clip, int bgr, uint8_t *out, uint32_t *rad_max, hipStream_t s);
 // decoder queries: Fourier features of index points | learned table, each with its padding embedding, up to 4 row segments
 int build_queries_launch(const pio_query_segment_t *segs, int nseg, float *y, int64_t ldy, int Qtot, int Cq, hipStream_t s);
 // output heads: up to 4 row segments of the decoder output, each through its own narrow fp32 linear head, written in place

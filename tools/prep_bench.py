@@ -20,6 +20,9 @@
     python tools/prep_bench.py --flow-blend-forward [--package-root DIR]   the whole test_mode forward of the full-size
                                                 FlowPerceiver at 436 x 1024 with the package under DIR (default: this tree):
                                                 run it alternately on two checkouts to compare them; prints one JSON line
+    python tools/prep_bench.py --flow-image         flow_to_image on the device (pio_flow_to_image) against .cpu().numpy() plus
+                                                the numpy function at 368 x 496, 436 x 1024 and 1080 x 1920, b = 1; prints
+                                                one JSON line
 """
 import argparse
 import json
@@ -626,6 +629,65 @@ def flow_blend_forward(repeats, launches):
                       "max": max(t), "output_sha1": hashlib.sha1(out.cpu().numpy().tobytes()).hexdigest()}))
 
 
+def flow_image(repeats, launches):
+    """flow_to_image of one flow field (b = 1) at 368 x 496, 436 x 1024 and 1080 x 1920, the field resident on the device as
+    the model leaves it ([1, 2, h, w], handed over as the permuted [h, w, 2] view):
+      device -- perceiverio_pytorch_amd.flow_to_image: two allocations, the memset and the two launches; the image stays
+                on the device (device events around `launches` back-to-back calls after 3 warm-up calls)
+      entry  -- pio_flow_to_image alone into a resident image (timed the same way)
+      host   -- today's path: .cpu().numpy() and utils.flow_utils.flow_to_image (host clock, the copy synchronises)
+      copy   -- the .cpu().numpy() of that path alone
+    `repeats` alternating runs each: median and (min, max) in microseconds.  The entry's bytes per second are over one read of
+    the flow and one write of the image (11 bytes per pixel; the entry reads the flow twice, once per launch)."""
+    import time
+    import perceiverio_pytorch_amd as P
+    from perceiverio_pytorch_amd import _lib as L
+    from utils import flow_utils as FU
+    lib, stream = L.lib(), torch.cuda.current_stream().cuda_stream
+    result = {"tool": "tools/prep_bench.py --flow-image", "b": 1, "repeats": repeats, "launches_per_repeat": launches,
+              "unit": "us", "cases": {}}
+    for h, w in ((368, 496), (436, 1024), (1080, 1920)):
+        flow = torch.randn(1, 2, h, w, device=dev) * 3.0
+        view = flow[0].permute(1, 2, 0)
+        img = torch.empty(h, w, 3, dtype=torch.uint8, device=dev)
+        rad = torch.empty(1, dtype=torch.int32, device=dev)
+
+        def entry():
+            L.check(lib.pio_flow_to_image(flow.data_ptr(), 0, w, 1, h * w, 1, h, w, 0.0, False, False, img.data_ptr(),
+                                          rad.data_ptr(), stream), "pio_flow_to_image")
+
+        def host_clock(f, n):
+            f()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                f()
+            return (time.perf_counter() - t0) / n * 1e6
+        n_host = max(2, launches // 5)
+        ways = {"device": lambda: timed(lambda: P.flow_to_image(view), launches), "entry": lambda: timed(entry, launches),
+                "host": lambda: host_clock(lambda: FU.flow_to_image(view.cpu().numpy()), n_host),
+                "copy": lambda: host_clock(lambda: view.cpu().numpy(), n_host)}
+        a, b = P.flow_to_image(view), FU.flow_to_image(view.cpu().numpy())
+        entry()
+        torch.cuda.synchronize()
+        assert torch.equal(a, img), "public function and raw entry disagree"
+        differ = int((a.cpu().numpy() != b).sum())
+        times = {k: [] for k in ways}
+        for _ in range(repeats):
+            for k, f in ways.items():
+                times[k].append(f())
+        case = {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in times.items()}
+        need = 11.0 * h * w
+        case["entry"]["algorithm_bytes"] = need
+        case["entry"]["GB_per_s_at_median"] = need / (case["entry"]["median"] * 1e-6) / 1e9
+        case["device"]["one_call"] = _kernel_launches(lambda: P.flow_to_image(view))
+        case.update(image=[h, w], bytes_differing_from_numpy=differ, bytes=3 * h * w)
+        result["cases"][f"{h}x{w}"] = case
+        del flow, view, img
+        torch.cuda.empty_cache()
+    print(json.dumps(result))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--flow-front", action="store_true", help="time pio_flow_patch_tokens against the torch chain")
@@ -635,6 +697,7 @@ if __name__ == "__main__":
     ap.add_argument("--language-front", action="store_true", help="time pio_embed_tokens against the torch chain")
     ap.add_argument("--flow-blend", action="store_true", help="time pio_flow_blend_tiles against the torch chain")
     ap.add_argument("--flow-blend-forward", action="store_true", help="time the whole tiled forward of the flow model")
+    ap.add_argument("--flow-image", action="store_true", help="time flow_to_image on the device against the numpy path")
     ap.add_argument("--package-root", default=None, help="--flow-blend-forward: the checkout whose package is timed")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--launches", type=int, default=20)
@@ -654,5 +717,7 @@ if __name__ == "__main__":
             flow_blend(args.repeats, args.launches)
         elif args.flow_blend_forward:
             flow_blend_forward(args.repeats, args.launches)
+        elif args.flow_image:
+            flow_image(args.repeats, args.launches)
         else:
             conv_tail()

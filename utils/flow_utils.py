@@ -1,5 +1,7 @@
 """Optical-flow visualisation (Middlebury colour wheel: Baker et al., "A Database and Evaluation Methodology for
 Optical Flow", ICCV 2007) for example_opt_flow.py."""
+import sys
+
 import numpy as np
 
 _SEGMENTS = ((15, (255, None, 0)), (6, (None, 255, 0)), (4, (0, 255, None)), (11, (0, None, 255)),
@@ -36,6 +38,12 @@ def flow_uv_to_colors(u, v, convert_to_bgr=False):
 
 
 def flow_to_image(flow_uv, clip_flow=None, convert_to_bgr=False):
+    """A numpy [H, W, 2] flow gives a numpy image; a torch tensor ([H, W, 2] or [B, H, W, 2]) is handed to
+    perceiverio_pytorch_amd.flow_to_image and a tensor on its device comes back."""
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(flow_uv, torch.Tensor):
+        from perceiverio_pytorch_amd import flow_to_image as on_device
+        return on_device(flow_uv, clip_flow, convert_to_bgr)
     assert flow_uv.ndim == 3 and flow_uv.shape[2] == 2, "input flow must have shape [H,W,2]"
     if clip_flow is not None:
         flow_uv = np.clip(flow_uv, 0, clip_flow)
