@@ -13,7 +13,6 @@ from typing import Optional
 
 import torch
 
-from . import _lib as L
 from . import runtime as R
 
 SEGMENTS = (15, 6, 4, 11, 13, 6)          # RY YG GC CB BM MR
@@ -99,9 +98,7 @@ def flow_to_image(flow: torch.Tensor, clip_flow: Optional[float] = None, convert
         img = torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev)
         rad_max = torch.empty(b, dtype=torch.int32, device=dev)
         sn, sy, sx, sc = f4.stride()
-        with R.on_device(dev):
-            L.check(L.lib().pio_flow_to_image(f4.data_ptr(), sn, sy, sx, sc, b, h, w,
-                                              0.0 if clip_flow is None else float(clip_flow), clip_flow is not None,
-                                              bool(convert_to_bgr), img.data_ptr(), rad_max.data_ptr(), R.stream_ptr(dev)),
-                    "pio_flow_to_image")
+        R.call(dev, "pio_flow_to_image", f4.data_ptr(), sn, sy, sx, sc, b, h, w,
+               0.0 if clip_flow is None else float(clip_flow), clip_flow is not None, bool(convert_to_bgr),
+               img.data_ptr(), rad_max.data_ptr())
     return img[0] if flow.dim() == 3 else img

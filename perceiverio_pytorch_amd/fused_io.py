@@ -1,0 +1,471 @@
+"""The fused input / output paths: one HIP launch each in place of a chain of torch ops of the I/O plumbing.  Every function
+takes the module it serves first, decides whether the launch stands for the chain exactly, and returns None when it declines
+-- its caller (a one-line hook of the module: _assemble, _fused, _project_heads, ...) then runs the chain, which stays in the
+model files with the switches.  The decline rules are the specification: a wrong accept gives silently wrong tokens."""
+import itertools
+import math
+
+import torch
+
+from . import _lib as L, probe as LP, runtime as R
+from . import io_processors as IO, output_queries as OQ, perceiver as PV, position_encoding as PE
+
+
+def gate(on, *tensors, dtypes=(torch.float32,)) -> bool:
+    """In front of every path: the switch is on, the backend is hip, `tensors` are CUDA tensors of `dtypes` (None: any)."""
+    if not on or R.get_backend() != "hip":
+        return False
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or not (dtypes is None or t.dtype in dtypes):
+            return False
+    return True
+
+
+def rows(t, *, min_stride=False, stride4=False, aligned=False):
+    """`t` as a kernel reads its rows: `t` itself when the last stride is 1 and what the entry point asks for beyond that
+    holds (min_stride: row stride >= row length; stride4: row stride a multiple of 4 elements; aligned: 16-byte aligned
+    pointer), a detached contiguous copy otherwise.  Only pointers and strides are taken from the result."""
+    ok = t.stride(-1) == 1 and not ((min_stride and t.stride(-2) < t.shape[-1]) or (stride4 and t.stride(-2) % 4)
+                                    or (aligned and t.data_ptr() % 16))
+    return t if ok else t.detach().contiguous()
+
+
+def param_row(p, width, dev):
+    """A learned (1, width) fp32 parameter on `dev` (padding embedding, mask token) as a kernel reads it: `p` itself, or a
+    detached contiguous copy; None for width 0 (the segment carries no pointer), False when `p` is anything else (decline)."""
+    if tuple(p.shape) != (1, width) or p.dtype != torch.float32 or p.device != dev:
+        return False
+    return None if width < 1 else p if p.is_contiguous() else p.detach().contiguous()
+
+
+def place(segs):
+    """{name: segment} -> (ctypes array of the segments in sorted-name order with row0 assigned along it, total rows); the
+    array is None when the total reaches 2^31 (row indices are int32): decline."""
+    arr, row0 = (type(next(iter(segs.values()))) * len(segs))(), 0
+    for i, m in enumerate(sorted(segs)):
+        segs[m].row0 = row0
+        arr[i] = segs[m]
+        row0 += segs[m].M
+    return (arr if row0 < 2 ** 31 else None), row0
+
+
+def embed_tokens(prep, inputs):
+    """(embed(inputs) + pos, embed(inputs) or None) from ONE pio_embed_tokens call, or None.  Taken under the hip
+    backend for a 2-D CUDA int32 / int64 id tensor with unit stride along t whose length equals the position table's,
+    fp32 embedding and position tables on that device, no padding_idx and no max_norm.  y is one fresh [B, T, C]
+    allocation and equals the chain's bit for bit (one rounded fp32 add of the same operands).  Unlike ATen, which
+    raises a device-side assert, an id outside [0, vocab_size) gives a NaN row in both outputs and sets the word of
+    bad_ids_flag(device)."""
+    w, p = prep.embed.weight, prep.input_pos_encoding.pos_embs
+    if not gate(prep.fused_embedding, inputs, dtypes=(torch.int32, torch.int64)) or inputs.dim() != 2:
+        return None
+    dev, (b, t) = inputs.device, inputs.shape
+    if (b < 1 or t < 1 or (t > 1 and inputs.stride(1) != 1) or t != p.shape[0]
+            or (b > 1 and inputs.stride(0) < t)):
+        return None
+    if (w.dtype != torch.float32 or p.dtype != torch.float32 or w.device != dev or p.device != dev
+            or p.dim() != 2 or p.shape[1] != w.shape[1] or w.shape[1] < 1
+            or prep.embed.padding_idx is not None or prep.embed.max_norm is not None):
+        return None
+    # (min_stride: the entry point refuses tables whose rows overlap -- an expanded parameter -- instead of reading them)
+    table, ptab = rows(w, min_stride=True), rows(p, min_stride=True)
+    v, c = table.shape
+    y = torch.empty((b, t, c), dtype=torch.float32, device=dev)
+    tokens = torch.empty((b, t, c), dtype=torch.float32, device=dev) if prep.need_tokens else None
+    flag = prep.bad_ids_flag(dev).zero_()
+    R.call(dev, "pio_embed_tokens", inputs.data_ptr(), inputs.element_size(), inputs.stride(0), table.data_ptr(),
+           table.stride(0), v, ptab.data_ptr(), ptab.stride(0), y.data_ptr(), t * c, c,
+           None if tokens is None else tokens.data_ptr(), t * c, c, flag.data_ptr(), b, t, c)
+    y = R.forward_only(y, w, p)
+    return y, (None if tokens is None else R.forward_only(tokens, w, p))
+
+
+def flow_patch_tokens(prep, pair):
+    """The optical-flow front end on a RAW frame pair [N, 2, C, H, W] by ONE HIP kernel (pio_flow_patch_tokens):
+    patches_for_flow (3x3 zero-padded neighbourhoods), the channels-last copy, space_to_depth (the two frames side by
+    side: 18 C channels) and the Linear of conv_after_patching, without any of their temporaries.  Returns the feature
+    array [N, H*W, out] -- without the Linear the 18 C patch channels, as a view of rows padded to a multiple of 4
+    -- or None when this configuration or input is not the covered one (the caller's ordinary path then runs: it
+    expects the PATCHED frames [N, 2, 9 C, H, W])."""
+    if (prep._prep_type != "patches" or prep._spatial_downsample != 1 or prep._temporal_downsample != 2
+            or not gate(True, pair) or pair.dim() != 5 or pair.shape[1] != 2):
+        return None
+    n, _, c, h, w = pair.shape
+    if not 1 <= c <= 4 or [h, w] != list(prep.index_dims):
+        return None
+    if prep._conv_after_patching:
+        lin = prep._conv_after_patch_layer
+        out = lin.out_features
+        if lin.in_features != 18 * c or out % 4 or out > 128 or lin.weight.dtype != torch.float32:
+            return None
+        wt, bias = lin.weight.detach().contiguous(), lin.bias.detach().contiguous()    # (the entry takes no row stride)
+        deps = (pair, lin.weight, lin.bias)
+    else:
+        out = 18 * c
+        if prep._patch_channels != out:
+            return None
+        wt, bias, deps = None, None, (pair,)
+    pair = rows(pair) if w > 1 else pair        # (one pixel per image row: its stride is never used)
+    ldy = (out + 3) // 4 * 4
+    y = torch.empty((n, h * w, ldy), dtype=torch.float32, device=pair.device)
+    R.call(pair.device, "pio_flow_patch_tokens", pair[:, 0].data_ptr(), pair[:, 1].data_ptr(), pair.stride(0),
+           pair.stride(2), pair.stride(3), pair.stride(0), pair.stride(2), pair.stride(3),
+           None if wt is None else wt.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), ldy, n, c, h,
+           w, out)
+    return R.forward_only(y if ldy == out else y[:, :, :out], *deps)
+
+
+def bn_relu_pool_tokens(convnet, x):
+    """The tail of Conv2DDownsample.forward_tokens: the last layer's BatchNorm (inference statistics) -> ReLU -> 3x3 stride-2
+    max-pool (SAME) -> channels-last tokens [B, OH*OW, C] of its conv output `x` by ONE pio_bn_relu_maxpool_tokens call."""
+    x = x.float().contiguous()
+    b, c, h, w = x.shape
+    if convnet.norms is not None:
+        bn = convnet.norms[len(convnet.convs) - 1]
+        scale = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).float()
+        shift = (bn.bias - bn.running_mean * scale).float()
+    else:
+        scale, shift = torch.ones(c, device=x.device), torch.zeros(c, device=x.device)
+    pads = IO.same_padding(x.shape[1:], 3, 2)          # [left, right, top, bottom]
+    y = torch.empty((b, ((h + 1) // 2) * ((w + 1) // 2), c), dtype=torch.float32, device=x.device)
+    R.call(x.device, "pio_bn_relu_maxpool_tokens", x.data_ptr(), scale.contiguous().data_ptr(),
+           shift.contiguous().data_ptr(), y.data_ptr(), b, c, h, w, pads[2], pads[0])
+    return R.forward_only(y, x, *convnet.parameters())     # (x carries the network input's and the convs' autograd)
+
+
+def assemble_tokens(mm, inputs, pos):
+    """(x, sizes, without_pos) of forward() from ONE pio_assemble_tokens call, or None.  Taken under the hip backend
+    for pos=None, CUDA fp32 inputs, mask probabilities <= 0 or >= 1 and modalities that only move values:
+    ImagePreprocessor "patches" (temporal_downsample 1, no conv_after_patching; a space-to-depth segment) or "pixels"
+    without subsampling, AudioPreprocessor, OneHotPreprocessor -- image / audio with a concatenated, batch-invariant
+    position table and no extra position MLPs.  A masked space-to-depth modality takes the chain.  The result is
+    bit-identical to the chain's; without_pos[m] is a view of x (of the modality's own features where it is masked)."""
+    if not mm.fused_assembly or pos is not None or mm._preprocessors is None:
+        return None
+    names = list(mm._preprocessors.keys())
+    if not 1 <= len(names) <= L.PIO_MAX_TOKEN_SEGMENTS or not gate(True, *[inputs.get(m) for m in names]):
+        return None
+    dev, batch, cc = None, None, mm._common_channels
+    deps, plan, views = [], {}, {}      # (deps: what the launch reads, kept alive, and what the result is tied to)
+    for m in names:
+        prep, x = mm._preprocessors[m], inputs[m]
+        if x.dim() < 2:
+            return None
+        if dev is None:
+            dev, batch = x.device, x.shape[0]
+        if x.device != dev or x.shape[0] != batch or batch < 1:
+            return None
+        p = 0.0 if mm._mask_probs is None else float(mm._mask_probs[m])
+        if 0.0 < p < 1.0:
+            return None
+        seg = L.TokenSegment()
+        if isinstance(prep, IO.OneHotPreprocessor):
+            if x.dim() != 2:
+                return None
+            feats = x[:, None, :]
+        elif isinstance(prep, IO.AudioPreprocessor):
+            feats = x.reshape(batch, -1, prep._samples_per_patch)
+        elif isinstance(prep, IO.ImagePreprocessor):
+            s = prep._spatial_downsample
+            if prep._prep_type == "patches":
+                if prep._temporal_downsample != 1 or prep._conv_after_patching:
+                    return None
+            elif prep._prep_type != "pixels" or s != 1 or (x.dim() == 5 and prep._temporal_downsample != 1):
+                return None
+            if x.dim() not in (4, 5) or p >= 1.0:
+                return None
+            t = x.shape[1] if x.dim() == 5 else 1
+            c, h, w = x.shape[-3:]
+            if not (1 <= s <= 8 and 1 <= c <= 4) or h % s or w % s or min(t, h, w) < 1:
+                return None
+            if t * (h // s) * (w // s) != int(math.prod(prep.index_dims)):
+                return None
+            x = rows(x)
+            feats = None
+            seg.kind, seg.feature, seg.M, seg.C1 = L.PIO_TOKENS_S2D, x.data_ptr(), t * (h // s) * (w // s), s * s * c
+            seg.sb, seg.st, seg.sc, seg.sy = x.stride(0), x.stride(1) if x.dim() == 5 else 0, x.stride(-3), x.stride(-2)
+            seg.T, seg.C, seg.H, seg.W, seg.s = t, c, h, w, s
+            deps.append(x)
+        else:
+            return None
+        if feats is not None:
+            f = rows(feats)
+            seg.kind, seg.feature, seg.M, seg.C1 = L.PIO_TOKENS_ROWS, f.data_ptr(), f.shape[1], f.shape[2]
+            seg.sb, seg.sm = f.stride(0), f.stride(1)
+            deps.append(f)
+        if seg.M < 1 or seg.C1 < 1:
+            return None
+        if not isinstance(prep, IO.OneHotPreprocessor):
+            if prep._concat_or_add_pos != "concat" or prep._n_extra_pos_mlp > 0:
+                return None
+            enc = prep._positional_encoding(batch_size=batch, pos=None, device=dev).to(dev)
+            if (enc.dim() != 3 or (enc.shape[0] > 1 and enc.stride(0) != 0) or enc.shape[1] != seg.M
+                    or enc.dtype != torch.float32):
+                return None
+            if enc.shape[2] > 0:
+                table = rows(enc[0])            # (any row stride: the entry point takes it as ldt)
+                seg.table, seg.ldt, seg.C2 = table.data_ptr(), table.stride(0), table.shape[1]
+                deps += [table, enc]
+        cp = cc - seg.C1 - seg.C2
+        if cp < 0 or (cp > 0 and mm.padding_embeddings is None):
+            return None
+        params = [(mm.padding_embeddings[m].pos_embs, cp, "pad")] if mm.padding_embeddings is not None else []
+        if p >= 1.0:
+            params.append((mm.mask_tokens[m].pos_embs, cc, "token"))
+        for w_, width, field in params:
+            w_c = param_row(w_, width, dev)
+            if w_c is False:
+                return None
+            if w_c is not None:
+                setattr(seg, field, w_c.data_ptr())
+                deps += [w_c, w_]
+        plan[m], views[m] = seg, feats      # (feats: the caller's own view, as the chain returns it, not the kernel's copy)
+        deps.append(inputs[m])
+    segs, mtot = place(plan)
+    if segs is None:
+        return None
+    y = torch.empty((batch, mtot, cc), dtype=torch.float32, device=dev)
+    R.call(dev, "pio_assemble_tokens", segs, len(names), y.data_ptr(), cc, mtot * cc, batch, mtot, cc)
+    x = R.forward_only(y, *deps)
+    without_pos = {m: views[m] if s.token else x[:, s.row0:s.row0 + s.M, :s.C1] for m, s in plan.items()}
+    return x, {m: s.M for m, s in plan.items()}, without_pos
+
+
+def query_tables(io, name, enc, device):
+    """(axis tables, bands [d, K]) of a Fourier query on `device`, built once per module and device with the chain's own
+    arithmetic: axis[j][i] = -1 + 2 * i / dims[j] as BasicQuery._encode computes it (int64 -> fp32 division on that
+    device), bands from the torch.linspace calls of generate_fourier_features."""
+    store = io.__dict__.setdefault("_query_table_cache", {})
+    key = (name, str(device))
+    hit = store.get(key)
+    if hit is None:
+        with torch.no_grad():
+            axes = [(-1 + 2 * torch.arange(int(n), device=device) / torch.tensor(int(n), device=device)).contiguous()
+                    for n in enc._index_dims]
+            bands = torch.stack([torch.linspace(1.0, res / 2, steps=enc._num_bands) for res in enc._max_resolution],
+                                dim=0).to(device).contiguous()
+        hit = store[key] = (axes, bands)
+    return hit
+
+
+def build_queries(io, inputs, subsampled_points):
+    """(query, sizes) of decoder_query from ONE pio_build_queries call, or None.  Taken under the hip backend on a CUDA
+    device for two to four output queries, every one a BasicQuery with concat_preprocessed_input=False over either an
+    unprojected FourierPositionEncoding (d <= 3) with a 1-D int64 `subsampled_points` tensor on that device, or a
+    TrainablePositionEncoding (fp32) without points; at least one Fourier; fp32 padding embeddings.  The array is
+    batch-invariant: ONE [1, Q, Cq] allocation returned as a stride-0 view over the batch (the decoder projects such
+    views once).  Position, table and padding channels equal the chain's bit for bit, sine / cosine to the device
+    library's accuracy."""
+    names = list(io._output_queries.keys())
+    # (dtypes=None: the inputs only say where the queries go)
+    if not gate(io.fused_queries, inputs, dtypes=None) or not 2 <= len(names) <= L.PIO_MAX_QUERY_SEGMENTS:
+        return None
+    dev, cq = inputs.device, io.query_channels
+    plan, deps, n_fourier = {}, [], 0
+    for m in names:
+        q = io._output_queries[m]
+        if not isinstance(q, OQ.BasicQuery) or q._concat_preprocessed_input:
+            return None
+        enc, points = q._position_encoding, subsampled_points.get(m)
+        seg = L.QuerySegment()
+        if type(enc) is PE.FourierPositionEncoding:
+            dims, d, k = tuple(enc._index_dims), len(enc._index_dims), int(enc._num_bands)
+            if (not 1 <= d <= 3 or len(enc._max_resolution) != d or k < 1 or min(dims) < 1
+                    or math.prod(dims) >= 2 ** 31):
+                return None
+            if (not isinstance(points, torch.Tensor) or points.dim() != 1 or points.dtype != torch.int64
+                    or points.device != dev or points.numel() < 1):
+                return None
+            feats = d * k * (1 if enc._sine_only else 2)
+            if 4 * (288 + d * k + 32 * feats) > 65536:      # (a strip's feature rows have to fit the kernel's LDS)
+                return None
+            axes, bands = query_tables(io, m, enc, dev)
+            points = rows(points)
+            seg.kind, seg.M, seg.d, seg.K, seg.ldb = L.PIO_QUERY_FOURIER, points.numel(), d, k, bands.stride(0)
+            seg.concat_pos, seg.sine_only = int(bool(enc._concat_pos)), int(bool(enc._sine_only))
+            for j in range(d):
+                seg.dims[j], seg.axis[j] = dims[j], axes[j].data_ptr()
+            seg.bands, seg.points = bands.data_ptr(), points.data_ptr()
+            width = enc.n_output_channels()
+            deps.append(points)
+            n_fourier += 1
+        elif type(enc) is PE.TrainablePositionEncoding:
+            w = enc.pos_embs
+            if points is not None or w.dim() != 2 or w.dtype != torch.float32 or w.device != dev or w.shape[0] < 1:
+                return None
+            table = rows(w)     # (any row stride: ldt; a zero-width table is contiguous as it stands and has no pointer)
+            seg.kind, seg.M, seg.C, seg.ldt = L.PIO_QUERY_TABLE, table.shape[0], table.shape[1], table.stride(0)
+            seg.table = table.data_ptr() if table.shape[1] > 0 else None
+            width = table.shape[1]
+            deps += [table, w]
+        else:
+            return None
+        pad = io.padding_embeddings[m].pos_embs
+        pad_c = param_row(pad, cq - width, dev)
+        if width != q.n_query_channels() or pad_c is False:
+            return None
+        if pad_c is not None:
+            seg.pad = pad_c.data_ptr()
+            deps += [pad_c, pad]
+        plan[m] = seg
+    segs, qtot = place(plan)
+    if n_fourier < 1 or segs is None:
+        return None
+    y = torch.empty((1, qtot, cq), dtype=torch.float32, device=dev)
+    R.call(dev, "pio_build_queries", segs, len(names), y.data_ptr(), cq, qtot, cq)
+    y = R.forward_only(y, *deps)
+    return torch.broadcast_to(y, (inputs.shape[0], qtot, cq)), {m: plan[m].M for m in names}
+
+
+def head_linear(post):
+    """The nn.Linear of a narrow head pio_project_heads can stand for, or None."""
+    kind = type(post)
+    return post.projection if kind is IO.ProjectionPostprocessor else post.linear if kind is IO.AudioPostprocessor else None
+
+
+def heads_eligible(io, k: int) -> bool:
+    """The part of project_heads' decision that the modules alone settle, for decoder rows of k channels: the switch, at
+    least two output modalities, no active range probe (the chain then keeps its "cast" records), every postprocessor a
+    ProjectionPostprocessor / AudioPostprocessor with fp32 [n_out <= 16, k] weights or a ClassificationPostprocessor,
+    at least one and at most four of the former, k a multiple of 4 in [4, 1024].  Row counts, the batch and the chunk
+    grouping play no part: a forward takes one path for all of its decoder calls."""
+    posts = io._output_postprocessors
+    if not io.fused_heads or posts is None or len(posts) < 2 or LP.range_active() or k < 4 or k > 1024 or k % 4:
+        return False
+    narrow = 0
+    for post in posts.values():
+        if type(post) is IO.ClassificationPostprocessor:
+            continue
+        lin = head_linear(post)
+        if lin is None:
+            return False
+        w, b = lin.weight, lin.bias
+        if (w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] != k or not 1 <= w.shape[0] <= 16
+                or (b is not None and (b.dtype != torch.float32 or b.device != w.device))):
+            return False
+        narrow += 1
+    return 1 <= narrow <= L.PIO_MAX_HEAD_SEGMENTS
+
+
+def heads_accept(io, outputs) -> bool:
+    """True when project_heads takes this decoder output: the hip backend, a CUDA fp32 [B, Q, K] tensor with unit channel
+    stride and 16-byte aligned rows, heads on its device, and heads_eligible(K)."""
+    if not gate(True, outputs) or outputs.dim() != 3 or outputs.stride(2) != 1:
+        return False
+    if (not heads_eligible(io, outputs.shape[2]) or outputs.data_ptr() % 16 or outputs.stride(1) % 4
+            or (outputs.shape[0] > 1 and outputs.stride(0) % 4)):
+        return False
+    return all(lin is None or lin.weight.device == outputs.device
+               for lin in map(head_linear, io._output_postprocessors.values()))
+
+
+def project_heads(io, outputs, query_sizes, into=None):
+    """The dict of postprocessed outputs of a decoder output [B, Q, K] from ONE pio_project_heads call for the narrow
+    heads (plus the ClassificationPostprocessor's own hip_linear on row 0, unchanged), or None when it declines
+    (heads_accept).  `into`: optional {modality: fp32 [B, rows, n_out] view with unit last stride} -- that head's rows are
+    written there, in place (MultiModalPerceiver: the group's rows of the final output array), and the view is what the
+    dict holds for it; without it a ProjectionPostprocessor returns a fresh [B, rows, n_out] array and an
+    AudioPostprocessor a fresh [B, rows * n_out], as the chain does."""
+    posts = io._output_postprocessors
+    order = sorted(query_sizes)
+    if not heads_accept(io, outputs) or order != sorted(posts.keys()) or sum(query_sizes.values()) > outputs.shape[1]:
+        return None
+    (batch, qtot, k), dev = outputs.shape, outputs.device
+    # (not place(): the rows of EVERY modality count, the label's included, and only the narrow heads become segments)
+    row0 = dict(zip(order, itertools.accumulate([0] + [query_sizes[m] for m in order])))
+    plan, keep, ys = [], [], {}
+    for m, post in posts.items():
+        lin = head_linear(post)
+        if lin is None:
+            continue
+        w = rows(lin.weight, stride4=True, aligned=True)        # (the kernel reads weight rows as 16-byte vectors)
+        b = None if lin.bias is None else lin.bias.detach().contiguous()
+        nrows, n_out = query_sizes[m], w.shape[0]
+        y = into.get(m) if into is not None else None
+        if y is None:
+            y = torch.empty((batch, nrows, n_out), dtype=torch.float32, device=dev)
+        elif (tuple(y.shape) != (batch, nrows, n_out) or y.dtype != torch.float32 or y.device != dev
+                or (nrows > 0 and y.stride(2) != 1)):
+            raise ValueError(f"_project_heads: into[{m!r}] must be a float32 [{batch}, {nrows}, {n_out}] view on {dev} "
+                             "with unit last stride")
+        ys[m] = R.forward_only(y, outputs, lin.weight, lin.bias)
+        if nrows < 1:
+            continue
+        seg = L.HeadSegment()
+        seg.row0, seg.rows, seg.n_out = row0[m], nrows, n_out
+        seg.w, seg.ldw, seg.bias = w.data_ptr(), w.stride(0), None if b is None else b.data_ptr()
+        seg.y, seg.y_sb, seg.y_rs = y.data_ptr(), y.stride(0) if batch > 1 else 0, y.stride(1)
+        plan.append(seg)
+        keep += [w, b, y]
+    if plan:
+        R.call(dev, "pio_project_heads", (L.HeadSegment * len(plan))(*plan), len(plan), outputs.data_ptr(),
+               outputs.stride(0) if batch > 1 else 0, outputs.stride(1), batch, qtot, k)
+    per_mod = PV.restructure(query_sizes, outputs)
+    result = {}
+    for m, post in posts.items():
+        if m not in ys:
+            result[m] = post(per_mod[m], pos=None, modality_sizes=None)
+        elif type(post) is IO.AudioPostprocessor and (into is None or m not in into):
+            result[m] = ys[m].reshape(batch, -1)
+        else:
+            result[m] = ys[m]
+    return result
+
+
+def _covers(corners, length, size):
+    """True when the intervals [c, c + length) of the corners cover [0, size)."""
+    pos = 0
+    while pos < size:
+        reach = max([c + length for c in corners if c <= pos], default=pos)
+        if reach <= pos:
+            return False
+        pos = reach
+    return True
+
+
+def blend_tiles(model, pair, h, w, min_overlap):
+    """Tiled inference with the blend as ONE pio_flow_blend_tiles call, or None when this call is not the covered one
+    (the caller then runs the chain from the start).  The tile groups go through the model exactly as in the chain
+    (torch.cat of the tiles, tiles_per_call); nothing is multiplied, padded or added, every group's flows are kept,
+    and one launch behind the last group writes the [b, 2, h, w] result: no host tensor, no copy to the device.
+    Taken under the hip backend for CUDA fp32 frames when the corner lists and the groups fit the entry's tables (64
+    each), every pixel is covered by a tile and every group's flows are CUDA fp32 [g*b, 2, H, W] with the same
+    non-negative strides in allocations that do not overlap (checked, not assumed: a model that handed out views of
+    one reused buffer would have overwritten the earlier groups)."""
+    if not gate(model.fused_blend, pair):
+        return None
+    ys, xs = model._grid_axes((h, w), min_overlap)
+    corners = list(itertools.product(ys, xs))
+    b, dev = pair.shape[0], pair.device
+    step = max(1, int(model.tiles_per_call))
+    ngroups = (len(corners) + step - 1) // step
+    if (b < 1 or len(ys) > L.PIO_MAX_BLEND_AXIS or len(xs) > L.PIO_MAX_BLEND_AXIS or ngroups > L.PIO_MAX_BLEND_GROUPS
+            or not _covers(ys, model.H, h) or not _covers(xs, model.W, w)):
+        return None
+    keep, spans = [], []
+    for i in range(0, len(corners), step):
+        group = corners[i:i + step]
+        tiles = torch.cat([pair[..., y:y + model.H, x:x + model.W] for y, x in group], dim=0)
+        flows = model._predict_patch(tiles)
+        if (not isinstance(flows, torch.Tensor) or flows.device != dev or flows.dtype != torch.float32
+                or tuple(flows.shape) != (len(group) * b, 2, model.H, model.W) or min(flows.stride()) < 0
+                or (keep and flows.stride() != keep[0].stride()) or flows.data_ptr() % 4):
+            return None
+        lo = flows.data_ptr()
+        hi = lo + 4 * (1 + sum((n - 1) * s for n, s in zip(flows.shape, flows.stride())))
+        if any(lo < b1 and a1 < hi for a1, b1 in spans):
+            return None
+        keep.append(flows)
+        spans.append((lo, hi))
+    p = L.FlowBlend()
+    for i, flows in enumerate(keep):
+        p.group[i] = flows.data_ptr()
+    p.sn, p.sc, p.sy, p.sx = keep[0].stride()
+    p.ngroups, p.tiles_per_group, p.ny, p.nx = len(keep), step, len(ys), len(xs)
+    p.ys[:len(ys)], p.xs[:len(xs)] = ys, xs
+    p.N, p.H, p.W, p.h, p.w = b, model.H, model.W, h, w
+    out = torch.empty((b, 2, h, w), dtype=torch.float32, device=dev)
+    # (PIO_E_SHAPE / PIO_E_ALIGN: a refusal, nothing was launched -- the chain)
+    if not R.call(dev, "pio_flow_blend_tiles", p, out.data_ptr(), 2 * h * w, h * w, w, declines=(-1, -2)):
+        return None
+    return R.forward_only(out, *keep)

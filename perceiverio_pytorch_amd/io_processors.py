@@ -3,7 +3,7 @@ ATen) plumbing, "next" rows of SURVEY.md section 8f.  They produce the [B, M, C]
 and turn decoder outputs into task outputs.  Same class names, constructor arguments, parameter names and
 (inputs_with_pos, inputs_without_pos) protocol as the reference's
 perceiver_io/io_processors/{preprocessors,postprocessors,processor_utils}.py, so reference checkpoints load.
-"""
+The fused paths in front of them (_fused, _flow_front, forward_tokens' tail) are hooks into fused_io.py."""
 from __future__ import annotations
 
 import math
@@ -141,8 +141,6 @@ class Conv2DDownsample(nn.Module):
         configuration is not covered (CPU tensor, training-mode BatchNorm)."""
         if not inputs.is_cuda or inputs.dim() != 4 or (self.norms is not None and self.training):
             return None
-        from . import _lib as L
-        from . import runtime as R
         x = inputs
         last = len(self.convs) - 1
         for layer, conv in enumerate(self.convs):
@@ -151,23 +149,7 @@ class Conv2DDownsample(nn.Module):
                 if self.norms is not None:
                     x = self.norms[layer](x)
                 x = F.max_pool2d(F.pad(F.relu(x), same_padding(x.shape[1:], 3, 2)), kernel_size=3, stride=2)
-        x = x.float().contiguous()
-        b, c, h, w = x.shape
-        if self.norms is not None:
-            bn = self.norms[last]
-            scale = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).float()
-            shift = (bn.bias - bn.running_mean * scale).float()
-        else:
-            scale = torch.ones(c, device=x.device)
-            shift = torch.zeros(c, device=x.device)
-        pads = same_padding(x.shape[1:], 3, 2)          # [left, right, top, bottom]
-        y = torch.empty((b, ((h + 1) // 2) * ((w + 1) // 2), c), dtype=torch.float32, device=x.device)
-        with R.on_device(x.device):
-            L.check(L.lib().pio_bn_relu_maxpool_tokens(x.data_ptr(), scale.contiguous().data_ptr(),
-                                                       shift.contiguous().data_ptr(), y.data_ptr(), b, c, h, w,
-                                                       pads[2], pads[0], R.stream_ptr(x.device)),
-                    "pio_bn_relu_maxpool_tokens")
-        return R.forward_only(y, inputs, *self.parameters())
+        return FIO.bn_relu_pool_tokens(self, x)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -249,44 +231,7 @@ class EmbeddingPreprocessor(nn.Module):
         return store[idx]
 
     def _fused(self, inputs):
-        """(embed(inputs) + pos, embed(inputs) or None) from ONE pio_embed_tokens call, or None.  Taken under the hip
-        backend for a 2-D CUDA int32 / int64 id tensor with unit stride along t whose length equals the position table's,
-        fp32 embedding and position tables on that device, no padding_idx and no max_norm.  y is one fresh [B, T, C]
-        allocation and equals the chain's bit for bit (one rounded fp32 add of the same operands).  Unlike ATen, which
-        raises a device-side assert, an id outside [0, vocab_size) gives a NaN row in both outputs and sets the word of
-        bad_ids_flag(device)."""
-        from . import _lib as L
-        from . import runtime as R
-        w, p = self.embed.weight, self.input_pos_encoding.pos_embs
-        if (not self.fused_embedding or R.get_backend() != "hip" or not isinstance(inputs, torch.Tensor)
-                or not inputs.is_cuda or inputs.dim() != 2 or inputs.dtype not in (torch.int32, torch.int64)):
-            return None
-        dev = inputs.device
-        b, t = inputs.shape
-        if (b < 1 or t < 1 or (t > 1 and inputs.stride(1) != 1) or t != p.shape[0]
-                or (b > 1 and inputs.stride(0) < t)):
-            return None
-        if (w.dtype != torch.float32 or p.dtype != torch.float32 or w.device != dev or p.device != dev
-                or p.dim() != 2 or p.shape[1] != w.shape[1] or w.shape[1] < 1
-                or self.embed.padding_idx is not None or self.embed.max_norm is not None):
-            return None
-        table, ptab = w.detach(), p.detach()
-        if table.stride(1) != 1 or table.stride(0) < table.shape[1]:
-            table = table.contiguous()
-        if ptab.stride(1) != 1 or ptab.stride(0) < ptab.shape[1]:
-            ptab = ptab.contiguous()
-        v, c = table.shape
-        y = torch.empty((b, t, c), dtype=torch.float32, device=dev)
-        tokens = torch.empty((b, t, c), dtype=torch.float32, device=dev) if self.need_tokens else None
-        flag = self.bad_ids_flag(dev)
-        with R.on_device(dev):
-            flag.zero_()
-            L.check(L.lib().pio_embed_tokens(inputs.data_ptr(), inputs.element_size(), inputs.stride(0), table.data_ptr(),
-                                             table.stride(0), v, ptab.data_ptr(), ptab.stride(0), y.data_ptr(), t * c, c,
-                                             None if tokens is None else tokens.data_ptr(), t * c, c, flag.data_ptr(),
-                                             b, t, c, R.stream_ptr(dev)), "pio_embed_tokens")
-        y = R.forward_only(y, w, p)
-        return y, (None if tokens is None else R.forward_only(tokens, w, p))
+        return FIO.embed_tokens(self, inputs)
 
     def forward(self, inputs: torch.Tensor, *, pos: Optional[torch.Tensor] = None):
         fused = self._fused(inputs)
@@ -353,45 +298,7 @@ class ImagePreprocessor(nn.Module, _PosMixin):
         return self.output_channels
 
     def _flow_front(self, pair: torch.Tensor):
-        """The optical-flow front end on a RAW frame pair [N, 2, C, H, W] by ONE HIP kernel (pio_flow_patch_tokens):
-        patches_for_flow (3x3 zero-padded neighbourhoods), the channels-last copy, space_to_depth (the two frames side by
-        side: 18 C channels) and the Linear of conv_after_patching, without any of their temporaries.  Returns the feature
-        array [N, H*W, out] -- without the Linear the 18 C patch channels, as a view of rows padded to a multiple of 4
-        -- or None when this configuration or input is not the covered one (the caller's ordinary path then runs: it
-        expects the PATCHED frames [N, 2, 9 C, H, W])."""
-        if (self._prep_type != "patches" or self._spatial_downsample != 1 or self._temporal_downsample != 2
-                or pair.dim() != 5 or pair.shape[1] != 2 or not pair.is_cuda or pair.dtype != torch.float32):
-            return None
-        from . import _lib as L
-        from . import runtime as R
-        n, _, c, h, w = pair.shape
-        if R.get_backend() != "hip" or not 1 <= c <= 4 or [h, w] != list(self.index_dims):
-            return None
-        if self._conv_after_patching:
-            lin = self._conv_after_patch_layer
-            out = lin.out_features
-            if lin.in_features != 18 * c or out % 4 or out > 128 or lin.weight.dtype != torch.float32:
-                return None
-            wt, bias = lin.weight.detach().contiguous(), lin.bias.detach().contiguous()
-            deps = (pair, lin.weight, lin.bias)
-        else:
-            out = 18 * c
-            if self._patch_channels != out:
-                return None
-            wt = bias = None
-            deps = (pair,)
-        if pair.stride(4) != 1 and w > 1:
-            pair = pair.contiguous()
-        ldy = (out + 3) // 4 * 4
-        y = torch.empty((n, h * w, ldy), dtype=torch.float32, device=pair.device)
-        f0, f1 = pair[:, 0], pair[:, 1]
-        with R.on_device(pair.device):
-            L.check(L.lib().pio_flow_patch_tokens(f0.data_ptr(), f1.data_ptr(), pair.stride(0), pair.stride(2),
-                                                  pair.stride(3), pair.stride(0), pair.stride(2), pair.stride(3),
-                                                  None if wt is None else wt.data_ptr(),
-                                                  None if bias is None else bias.data_ptr(), y.data_ptr(), ldy, n, c, h,
-                                                  w, out, R.stream_ptr(pair.device)), "pio_flow_patch_tokens")
-        return R.forward_only(y if ldy == out else y[:, :, :out], *deps)
+        return FIO.flow_patch_tokens(self, pair)
 
     def _features(self, inputs: torch.Tensor) -> torch.Tensor:
         x = inputs
@@ -496,7 +403,6 @@ def _linear(mod: nn.Linear, x: torch.Tensor, cache: dict) -> torch.Tensor:
         from .runtime import hip_linear
         return hip_linear(x, mod.weight, mod.bias, cache)
     return mod(x)
-
 
 
 class EmbeddingPostprocessor(nn.Module):
@@ -615,3 +521,6 @@ class FlowPostprocessor(nn.Module):
 
     def forward(self, inputs: torch.Tensor, *, pos=None, modality_sizes: Optional[Mapping[str, int]] = None):
         return (inputs * self.flow_scale_factor).reshape([inputs.shape[0], *self.img_size, 2]).permute(0, 3, 1, 2)
+
+
+from . import fused_io as FIO  # noqa: E402  (behind the classes fused_io and output_queries read from here)

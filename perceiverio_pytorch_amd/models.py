@@ -1,7 +1,8 @@
 """The four task models of the reference, assembled from the HIP-backed PerceiverIO core and the torch I/O plumbing:
 ClassificationPerceiver (classification_perceiver.py), LanguagePerceiver (language_perceiver.py), FlowPerceiver
 (flow_perceiver.py), MultiModalPerceiver (multimodal_perceiver.py).  Same constructor arguments, `self.perceiver`
-attribute and state_dict keys, so `load_state_dict(ckpt["model_state_dict"])` of a reference checkpoint works."""
+attribute and state_dict keys, so `load_state_dict(ckpt["model_state_dict"])` of a reference checkpoint works.  The fused
+tile blend of FlowPerceiver (_blend_tiles_fused) is a hook into fused_io.py."""
 from __future__ import annotations
 
 import itertools
@@ -12,6 +13,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import fused_io as FIO
 from . import io_processors
 from .io_processors import (AudioPostprocessor, AudioPreprocessor, ClassificationPostprocessor,
                             EmbeddingPostprocessor, EmbeddingPreprocessor, FlowPostprocessor, ImagePreprocessor,
@@ -227,17 +229,6 @@ class LanguagePerceiver(nn.Module):
             return self.perceiver(inputs, input_mask=input_masks, query_mask=input_masks)
 
 
-def _covers(corners, length, size):
-    """True when the intervals [c, c + length) of the corners cover [0, size)."""
-    pos = 0
-    while pos < size:
-        reach = max([c + length for c in corners if c <= pos], default=pos)
-        if reach <= pos:
-            return False
-        pos = reach
-    return True
-
-
 class FlowPerceiver(nn.Module):
     """Optical flow: 3x3 patches of a frame pair in, dense per-pixel queries out (reference flow_perceiver.py:20-199)."""
 
@@ -306,56 +297,7 @@ class FlowPerceiver(nn.Module):
             return self.perceiver(x, query_shard=self.query_shard)
 
     def _blend_tiles_fused(self, pair, h, w, min_overlap):
-        """Tiled inference with the blend as ONE pio_flow_blend_tiles call, or None when this call is not the covered one
-        (the caller then runs the chain from the start).  The tile groups go through the model exactly as in the chain
-        (torch.cat of the tiles, tiles_per_call); nothing is multiplied, padded or added, every group's flows are kept,
-        and one launch behind the last group writes the [b, 2, h, w] result: no host tensor, no copy to the device.
-        Taken under the hip backend for CUDA fp32 frames when the corner lists and the groups fit the entry's tables (64
-        each), every pixel is covered by a tile and every group's flows are CUDA fp32 [g*b, 2, H, W] with the same
-        non-negative strides in allocations that do not overlap (checked, not assumed: a model that handed out views of
-        one reused buffer would have overwritten the earlier groups)."""
-        from . import _lib as L
-        from . import runtime as R
-        if not self.fused_blend or get_backend() != "hip" or not pair.is_cuda or pair.dtype != torch.float32:
-            return None
-        ys, xs = self._grid_axes((h, w), min_overlap)
-        corners = list(itertools.product(ys, xs))
-        b = pair.shape[0]
-        step = max(1, int(self.tiles_per_call))
-        ngroups = (len(corners) + step - 1) // step
-        if (b < 1 or len(ys) > L.PIO_MAX_BLEND_AXIS or len(xs) > L.PIO_MAX_BLEND_AXIS or ngroups > L.PIO_MAX_BLEND_GROUPS
-                or not _covers(ys, self.H, h) or not _covers(xs, self.W, w)):
-            return None
-        dev = pair.device
-        keep, spans = [], []
-        for i in range(0, len(corners), step):
-            group = corners[i:i + step]
-            tiles = torch.cat([pair[..., y:y + self.H, x:x + self.W] for y, x in group], dim=0)
-            flows = self._predict_patch(tiles)
-            if (not isinstance(flows, torch.Tensor) or flows.device != dev or flows.dtype != torch.float32
-                    or tuple(flows.shape) != (len(group) * b, 2, self.H, self.W) or min(flows.stride()) < 0
-                    or (keep and flows.stride() != keep[0].stride()) or flows.data_ptr() % 4):
-                return None
-            lo = flows.data_ptr()
-            hi = lo + 4 * (1 + sum((n - 1) * s for n, s in zip(flows.shape, flows.stride())))
-            if any(lo < b1 and a1 < hi for a1, b1 in spans):
-                return None
-            keep.append(flows)
-            spans.append((lo, hi))
-        p = L.FlowBlend()
-        for i, flows in enumerate(keep):
-            p.group[i] = flows.data_ptr()
-        p.sn, p.sc, p.sy, p.sx = keep[0].stride()
-        p.ngroups, p.tiles_per_group, p.ny, p.nx = len(keep), step, len(ys), len(xs)
-        p.ys[:len(ys)], p.xs[:len(xs)] = ys, xs
-        p.N, p.H, p.W, p.h, p.w = b, self.H, self.W, h, w
-        out = torch.empty((b, 2, h, w), dtype=torch.float32, device=dev)
-        with R.on_device(dev):
-            code = L.lib().pio_flow_blend_tiles(p, out.data_ptr(), 2 * h * w, h * w, w, R.stream_ptr(dev))
-        if code in (-1, -2):        # PIO_E_SHAPE / PIO_E_ALIGN: a refusal, nothing was launched
-            return None
-        L.check(code, "pio_flow_blend_tiles")
-        return R.forward_only(out, *keep)
+        return FIO.blend_tiles(self, pair, h, w, min_overlap)
 
     def forward(self, image1: torch.Tensor, image2: torch.Tensor, test_mode: bool = False, min_overlap: int = 20):
         h, w = image1.shape[2], image1.shape[3]

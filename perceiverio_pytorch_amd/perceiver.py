@@ -3,17 +3,18 @@
 Same constructor arguments, sub-module names and forward signatures as the reference.  ``forward``
 is ONE C call each (``pio_encoder_fwd`` / ``pio_decoder_fwd``): the whole cross-attend + num_blocks x
 num_self_attends_per_block stack is enqueued on the current HIP stream without returning to Python.
+The fused paths around them (_assemble, _fused_decoder_query, _project_heads) are hooks into fused_io.py.
 """
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import fused_io as FIO
 from . import probe as LP
 from . import runtime as R
 from .position_encoding import TrainablePositionEncoding
@@ -124,10 +125,9 @@ class PerceiverEncoder(nn.Module):
             LP.expect("cross", *["stack"] * (Lyr * self._num_blocks))    # (one attention call per block, this order)
             LP.mark_range("cross")           # (range probe: the library marks "stack" behind the cross-attend itself)
             try:
-                with R.on_device(dev):
-                    L.check(lib.pio_encoder_fwd_opts(cross, layers, Lyr, self._num_blocks, int(per_block), R.tensor3(x),
-                                                     tail3, R.tensor3(z0), im_ptr, out.data_ptr(), ws.data_ptr(),
-                                                     ws.numel(), R.stream_ptr(dev), opts), "pio_encoder_fwd")
+                R.call(dev, "pio_encoder_fwd_opts", cross, layers, Lyr, self._num_blocks, int(per_block), R.tensor3(x),
+                       tail3, R.tensor3(z0), im_ptr, out.data_ptr(), ws.data_ptr(), ws.numel(), tail=(opts,),
+                       what="pio_encoder_fwd")
             finally:
                 LP.mark_range("attention")
             return self._finish(out, flag, inputs, inputs_tail, latents, input_mask)
@@ -147,13 +147,13 @@ class PerceiverEncoder(nn.Module):
             LP.expect("cross", *["stack"] * (Lyr * self._num_blocks))
             LP.mark_range("cross")
             try:
-                with R.on_device(dev), torch.cuda.stream(side):
+                with torch.cuda.stream(side):
                     xs, zs = x[i * bs:(i + 1) * bs], z0[i * bs:(i + 1) * bs]
                     ws = R.workspace(dev, lib.pio_encoder_workspace_bytes(cross, layers, Lyr, bs, M, N))
                     mp = im_ptr + i * bs * M if im_ptr is not None else None
-                    L.check(lib.pio_encoder_fwd_opts(cross, layers, Lyr, self._num_blocks, 0, R.tensor3(xs), None,
-                                                     R.tensor3(zs), mp, out[i * bs:(i + 1) * bs].data_ptr(),
-                                                     ws.data_ptr(), ws.numel(), side.cuda_stream, opts), "pio_encoder_fwd")
+                    R.call(dev, "pio_encoder_fwd_opts", cross, layers, Lyr, self._num_blocks, 0, R.tensor3(xs), None,
+                           R.tensor3(zs), mp, out[i * bs:(i + 1) * bs].data_ptr(), ws.data_ptr(), ws.numel(),
+                           stream=side.cuda_stream, tail=(opts,), what="pio_encoder_fwd")
             finally:
                 LP.mark_range("attention")
         for side in sides:                   # ... and `cur` continues behind ALL of them (a wait queued between
@@ -304,15 +304,12 @@ class PerceiverDecoder(nn.Module):
         LP.expect("decoder")
         LP.mark_range("decoder")
         try:
-            with R.on_device(dev):
-                if query_tail is not None:
-                    L.check(lib.pio_decoder_fwd_split(cross, fin_ptr, out_ch, R.tensor3(q), R.tensor3(query_tail),
-                                                      R.tensor3(z), qm_ptr, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                      R.stream_ptr(dev)), "pio_decoder_fwd_split")
-                else:
-                    L.check(lib.pio_decoder_fwd_qcache(cross, fin_ptr, out_ch, R.tensor3(q), R.tensor3(z), qm_ptr,
-                                                       out.data_ptr(), ws.data_ptr(), ws.numel(), R.stream_ptr(dev), qhi,
-                                                       qlo, valid), "pio_decoder_fwd")
+            if query_tail is not None:
+                R.call(dev, "pio_decoder_fwd_split", cross, fin_ptr, out_ch, R.tensor3(q), R.tensor3(query_tail),
+                       R.tensor3(z), qm_ptr, out.data_ptr(), ws.data_ptr(), ws.numel())
+            else:
+                R.call(dev, "pio_decoder_fwd_qcache", cross, fin_ptr, out_ch, R.tensor3(q), R.tensor3(z), qm_ptr,
+                       out.data_ptr(), ws.data_ptr(), ws.numel(), tail=(qhi, qlo, valid), what="pio_decoder_fwd")
         finally:
             LP.mark_range("attention")
         if qhi is not None:
@@ -378,123 +375,7 @@ class MultimodalPreprocessor(nn.Module):
     fused_assembly = True
 
     def _assemble(self, inputs, pos):
-        """(x, sizes, without_pos) of forward() from ONE pio_assemble_tokens call, or None.  Taken under the hip backend
-        for pos=None, CUDA fp32 inputs, mask probabilities <= 0 or >= 1 and modalities that only move values:
-        ImagePreprocessor "patches" (temporal_downsample 1, no conv_after_patching; a space-to-depth segment) or "pixels"
-        without subsampling, AudioPreprocessor, OneHotPreprocessor -- image / audio with a concatenated, batch-invariant
-        position table and no extra position MLPs.  A masked space-to-depth modality takes the chain.  The result is
-        bit-identical to the chain's; without_pos[m] is a view of x (of the modality's own features where it is masked)."""
-        from .io_processors import AudioPreprocessor, ImagePreprocessor, OneHotPreprocessor
-        if not self.fused_assembly or pos is not None or self._preprocessors is None or R.get_backend() != "hip":
-            return None
-        names = list(self._preprocessors.keys())
-        if not 1 <= len(names) <= L.PIO_MAX_TOKEN_SEGMENTS or any(m not in inputs for m in names):
-            return None
-        dev, batch, cc = None, None, self._common_channels
-        keep, deps, plan = [], [], {}
-        for m in names:
-            prep, x = self._preprocessors[m], inputs[m]
-            if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() < 2:
-                return None
-            if dev is None:
-                dev, batch = x.device, x.shape[0]
-            if x.device != dev or x.shape[0] != batch or batch < 1:
-                return None
-            p = 0.0 if self._mask_probs is None else float(self._mask_probs[m])
-            if 0.0 < p < 1.0:
-                return None
-            seg = L.TokenSegment()
-            if isinstance(prep, OneHotPreprocessor):
-                if x.dim() != 2:
-                    return None
-                feats = x[:, None, :]
-            elif isinstance(prep, AudioPreprocessor):
-                feats = x.reshape(batch, -1, prep._samples_per_patch)
-            elif isinstance(prep, ImagePreprocessor):
-                s = prep._spatial_downsample
-                if prep._prep_type == "patches":
-                    if prep._temporal_downsample != 1 or prep._conv_after_patching:
-                        return None
-                elif prep._prep_type != "pixels" or s != 1 or (x.dim() == 5 and prep._temporal_downsample != 1):
-                    return None
-                if x.dim() not in (4, 5) or p >= 1.0:
-                    return None
-                t = x.shape[1] if x.dim() == 5 else 1
-                c, h, w = x.shape[-3:]
-                if not (1 <= s <= 8 and 1 <= c <= 4) or h % s or w % s or min(t, h, w) < 1:
-                    return None
-                if t * (h // s) * (w // s) != int(math.prod(prep.index_dims)):
-                    return None
-                if x.stride(-1) != 1:
-                    x = x.contiguous()
-                feats = None
-                seg.kind, seg.feature, seg.M, seg.C1 = L.PIO_TOKENS_S2D, x.data_ptr(), t * (h // s) * (w // s), s * s * c
-                seg.sb, seg.st, seg.sc, seg.sy = x.stride(0), x.stride(1) if x.dim() == 5 else 0, x.stride(-3), x.stride(-2)
-                seg.T, seg.C, seg.H, seg.W, seg.s = t, c, h, w, s
-                keep.append(x)
-            else:
-                return None
-            if feats is not None:
-                if feats.stride(2) != 1:
-                    feats = feats.contiguous()
-                seg.kind, seg.feature, seg.M, seg.C1 = L.PIO_TOKENS_ROWS, feats.data_ptr(), feats.shape[1], feats.shape[2]
-                seg.sb, seg.sm = feats.stride(0), feats.stride(1)
-                keep.append(feats)
-            if seg.M < 1 or seg.C1 < 1:
-                return None
-            if not isinstance(prep, OneHotPreprocessor):
-                if prep._concat_or_add_pos != "concat" or prep._n_extra_pos_mlp > 0:
-                    return None
-                enc = prep._positional_encoding(batch_size=batch, pos=None, device=dev).to(dev)
-                if (enc.dim() != 3 or (enc.shape[0] > 1 and enc.stride(0) != 0) or enc.shape[1] != seg.M
-                        or enc.dtype != torch.float32):
-                    return None
-                table = enc[0].detach()
-                if table.shape[1] > 0:
-                    if table.stride(1) != 1:
-                        table = table.contiguous()
-                    seg.table, seg.ldt, seg.C2 = table.data_ptr(), table.stride(0), table.shape[1]
-                    keep.append(table)
-                    deps.append(enc)
-            cp = cc - seg.C1 - seg.C2
-            if cp < 0 or (cp > 0 and self.padding_embeddings is None):
-                return None
-            params = []
-            if self.padding_embeddings is not None:
-                params.append((self.padding_embeddings[m].pos_embs, cp, "pad"))
-            if p >= 1.0:
-                params.append((self.mask_tokens[m].pos_embs, cc, "token"))
-            for w_, width, field in params:
-                if tuple(w_.shape) != (1, width) or w_.dtype != torch.float32 or w_.device != dev:
-                    return None
-                if width > 0:
-                    w_c = w_.detach().contiguous()
-                    setattr(seg, field, w_c.data_ptr())
-                    keep.append(w_c)
-                    deps.append(w_)
-            plan[m] = (seg, feats)
-            deps.append(inputs[m])
-        order = sorted(names)
-        mtot = sum(plan[m][0].M for m in order)
-        if mtot >= 2 ** 31:
-            return None
-        segs = (L.TokenSegment * len(order))()
-        row0 = 0
-        for i, m in enumerate(order):
-            plan[m][0].row0 = row0
-            segs[i] = plan[m][0]
-            row0 += plan[m][0].M
-        y = torch.empty((batch, mtot, cc), dtype=torch.float32, device=dev)
-        with R.on_device(dev):
-            L.check(L.lib().pio_assemble_tokens(segs, len(order), y.data_ptr(), cc, mtot * cc, batch, mtot, cc,
-                                                R.stream_ptr(dev)), "pio_assemble_tokens")
-        x = R.forward_only(y, *deps)
-        sizes = {m: plan[m][0].M for m in names}
-        without_pos = {}
-        for m in names:
-            seg, feats = plan[m]
-            without_pos[m] = feats if seg.token else x[:, seg.row0:seg.row0 + seg.M, :seg.C1]
-        return x, sizes, without_pos
+        return FIO.assemble_tokens(self, inputs, pos)
 
     def _single_embedding(self, inputs):
         """(x, sizes, without_pos) of forward() for ONE EmbeddingPreprocessor without padding embeddings or mask
@@ -641,223 +522,22 @@ class PerceiverIO(nn.Module):
     # declines, runs the chain exactly as before.
     fused_queries = True
 
-    def _query_tables(self, name, enc, device):
-        """(axis tables, bands [d, K]) of a Fourier query on `device`, built once per module and device with the chain's own
-        arithmetic: axis[j][i] = -1 + 2 * i / dims[j] as BasicQuery._encode computes it (int64 -> fp32 division on that
-        device), bands from the torch.linspace calls of generate_fourier_features."""
-        store = self.__dict__.setdefault("_query_table_cache", {})
-        key = (name, str(device))
-        hit = store.get(key)
-        if hit is None:
-            with torch.no_grad():
-                axes = [(-1 + 2 * torch.arange(int(n), device=device) / torch.tensor(int(n), device=device)).contiguous()
-                        for n in enc._index_dims]
-                bands = torch.stack([torch.linspace(1.0, res / 2, steps=enc._num_bands) for res in enc._max_resolution],
-                                    dim=0).to(device).contiguous()
-            hit = store[key] = (axes, bands)
-        return hit
-
     def _fused_decoder_query(self, inputs, subsampled_points):
-        """(query, sizes) of decoder_query from ONE pio_build_queries call, or None.  Taken under the hip backend on a CUDA
-        device for two to four output queries, every one a BasicQuery with concat_preprocessed_input=False over either an
-        unprojected FourierPositionEncoding (d <= 3) with a 1-D int64 `subsampled_points` tensor on that device, or a
-        TrainablePositionEncoding (fp32) without points; at least one Fourier; fp32 padding embeddings.  The array is
-        batch-invariant: ONE [1, Q, Cq] allocation returned as a stride-0 view over the batch (the decoder projects such
-        views once).  Position, table and padding channels equal the chain's bit for bit, sine / cosine to the device
-        library's accuracy."""
-        from .output_queries import BasicQuery
-        from .position_encoding import FourierPositionEncoding
-        if not self.fused_queries or R.get_backend() != "hip" or not isinstance(inputs, torch.Tensor) or not inputs.is_cuda:
-            return None
-        names = list(self._output_queries.keys())
-        if not 2 <= len(names) <= L.PIO_MAX_QUERY_SEGMENTS:
-            return None
-        dev, cq = inputs.device, self.query_channels
-        plan, keep, deps, n_fourier = {}, [], [], 0
-        for m in names:
-            q = self._output_queries[m]
-            if not isinstance(q, BasicQuery) or q._concat_preprocessed_input:
-                return None
-            enc, points = q._position_encoding, subsampled_points.get(m)
-            seg = L.QuerySegment()
-            if type(enc) is FourierPositionEncoding:
-                dims, d, k = tuple(enc._index_dims), len(enc._index_dims), int(enc._num_bands)
-                if (not 1 <= d <= 3 or len(enc._max_resolution) != d or k < 1 or min(dims) < 1
-                        or math.prod(dims) >= 2 ** 31):
-                    return None
-                if (not isinstance(points, torch.Tensor) or points.dim() != 1 or points.dtype != torch.int64
-                        or points.device != dev or points.numel() < 1):
-                    return None
-                feats = d * k * (1 if enc._sine_only else 2)
-                if 4 * (288 + d * k + 32 * feats) > 65536:      # (a strip's feature rows have to fit the kernel's LDS)
-                    return None
-                axes, bands = self._query_tables(m, enc, dev)
-                if points.stride(0) != 1:
-                    points = points.contiguous()
-                seg.kind, seg.M, seg.d, seg.K, seg.ldb = L.PIO_QUERY_FOURIER, points.numel(), d, k, bands.stride(0)
-                seg.concat_pos, seg.sine_only = int(bool(enc._concat_pos)), int(bool(enc._sine_only))
-                for j in range(d):
-                    seg.dims[j], seg.axis[j] = dims[j], axes[j].data_ptr()
-                seg.bands, seg.points = bands.data_ptr(), points.data_ptr()
-                width = enc.n_output_channels()
-                keep.append(points)
-                n_fourier += 1
-            elif type(enc) is TrainablePositionEncoding:
-                w = enc.pos_embs
-                if points is not None or w.dim() != 2 or w.dtype != torch.float32 or w.device != dev or w.shape[0] < 1:
-                    return None
-                table = w.detach()
-                if table.shape[1] > 0 and table.stride(1) != 1:
-                    table = table.contiguous()
-                seg.kind, seg.M, seg.C, seg.ldt = L.PIO_QUERY_TABLE, table.shape[0], table.shape[1], table.stride(0)
-                seg.table = table.data_ptr() if table.shape[1] > 0 else None
-                width = table.shape[1]
-                keep.append(table)
-                deps.append(w)
-            else:
-                return None
-            pad = self.padding_embeddings[m].pos_embs
-            if (width != q.n_query_channels() or tuple(pad.shape) != (1, cq - width) or pad.dtype != torch.float32
-                    or pad.device != dev):
-                return None
-            if cq > width:
-                pad_c = pad.detach().contiguous()
-                seg.pad = pad_c.data_ptr()
-                keep.append(pad_c)
-                deps.append(pad)
-            plan[m] = seg
-        qtot = sum(plan[m].M for m in names)
-        if n_fourier < 1 or qtot >= 2 ** 31:
-            return None
-        order = sorted(names)
-        segs = (L.QuerySegment * len(order))()
-        row0 = 0
-        for i, m in enumerate(order):
-            plan[m].row0 = row0
-            segs[i] = plan[m]
-            row0 += plan[m].M
-        y = torch.empty((1, qtot, cq), dtype=torch.float32, device=dev)
-        with R.on_device(dev):
-            L.check(L.lib().pio_build_queries(segs, len(order), y.data_ptr(), cq, qtot, cq, R.stream_ptr(dev)),
-                    "pio_build_queries")
-        y = R.forward_only(y, *deps)
-        return torch.broadcast_to(y, (inputs.shape[0], qtot, cq)), {m: plan[m].M for m in names}
+        return FIO.build_queries(self, inputs, subsampled_points)
 
     # One HIP launch (pio_project_heads) instead of one runtime.hip_linear chain per narrow output head (row slice copy,
     # 16-bit cast, GEMM, result copied into place), for a multi-modality model: see _project_heads.  fp32 products of the
     # unrounded decoder output.  False, and every configuration it declines, runs the chain exactly as before.
     fused_heads = True
 
-    @staticmethod
-    def _head_linear(post):
-        """The nn.Linear of a narrow head pio_project_heads can stand for, or None."""
-        from .io_processors import AudioPostprocessor, ProjectionPostprocessor
-        if type(post) is ProjectionPostprocessor:
-            return post.projection
-        if type(post) is AudioPostprocessor:
-            return post.linear
-        return None
-
     def _heads_eligible(self, k: int) -> bool:
-        """The part of _project_heads' decision that the modules alone settle, for decoder rows of k channels: the switch, at
-        least two output modalities, no active range probe (the chain then keeps its "cast" records), every postprocessor a
-        ProjectionPostprocessor / AudioPostprocessor with fp32 [n_out <= 16, k] weights or a ClassificationPostprocessor,
-        at least one and at most four of the former, k a multiple of 4 in [4, 1024].  Row counts, the batch and the chunk
-        grouping play no part: a forward takes one path for all of its decoder calls."""
-        from .io_processors import ClassificationPostprocessor
-        posts = self._output_postprocessors
-        if not self.fused_heads or posts is None or len(posts) < 2 or LP.range_active():
-            return False
-        if k < 4 or k > 1024 or k % 4:
-            return False
-        narrow = 0
-        for post in posts.values():
-            if type(post) is ClassificationPostprocessor:
-                continue
-            lin = self._head_linear(post)
-            if lin is None:
-                return False
-            w, b = lin.weight, lin.bias
-            if (w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] != k or not 1 <= w.shape[0] <= 16
-                    or (b is not None and (b.dtype != torch.float32 or b.device != w.device))):
-                return False
-            narrow += 1
-        return 1 <= narrow <= L.PIO_MAX_HEAD_SEGMENTS
+        return FIO.heads_eligible(self, k)
 
     def _heads_accept(self, outputs) -> bool:
-        """True when _project_heads takes this decoder output: the hip backend, a CUDA fp32 [B, Q, K] tensor with unit channel
-        stride and 16-byte aligned rows, heads on its device, and _heads_eligible(K)."""
-        if (R.get_backend() != "hip" or not isinstance(outputs, torch.Tensor) or not outputs.is_cuda
-                or outputs.dtype != torch.float32 or outputs.dim() != 3 or outputs.stride(2) != 1):
-            return False
-        if not self._heads_eligible(outputs.shape[2]):
-            return False
-        if outputs.data_ptr() % 16 or outputs.stride(1) % 4 or (outputs.shape[0] > 1 and outputs.stride(0) % 4):
-            return False
-        return all(lin is None or lin.weight.device == outputs.device
-                   for lin in map(self._head_linear, self._output_postprocessors.values()))
+        return FIO.heads_accept(self, outputs)
 
     def _project_heads(self, outputs, query_sizes, into=None):
-        """The dict of postprocessed outputs of a decoder output [B, Q, K] from ONE pio_project_heads call for the narrow
-        heads (plus the ClassificationPostprocessor's own hip_linear on row 0, unchanged), or None when it declines
-        (_heads_accept).  `into`: optional {modality: fp32 [B, rows, n_out] view with unit last stride} -- that head's rows are
-        written there, in place (MultiModalPerceiver: the group's rows of the final output array), and the view is what the
-        dict holds for it; without it a ProjectionPostprocessor returns a fresh [B, rows, n_out] array and an
-        AudioPostprocessor a fresh [B, rows * n_out], as the chain does."""
-        from .io_processors import AudioPostprocessor
-        posts = self._output_postprocessors
-        if not self._heads_accept(outputs) or sorted(query_sizes.keys()) != sorted(posts.keys()):
-            return None
-        if sum(query_sizes.values()) > outputs.shape[1]:
-            return None
-        batch, qtot, k = outputs.shape
-        dev = outputs.device
-        row0, start = {}, 0
-        for m in sorted(query_sizes.keys()):
-            row0[m] = start
-            start += query_sizes[m]
-        plan, keep, ys = [], [], {}
-        for m, post in posts.items():
-            lin = self._head_linear(post)
-            if lin is None:
-                continue
-            w = lin.weight.detach()
-            if w.stride(1) != 1 or w.stride(0) % 4 or w.data_ptr() % 16:
-                w = w.contiguous()
-            b = None if lin.bias is None else lin.bias.detach().contiguous()
-            rows, n_out = query_sizes[m], w.shape[0]
-            y = into.get(m) if into is not None else None
-            if y is None:
-                y = torch.empty((batch, rows, n_out), dtype=torch.float32, device=dev)
-            elif (tuple(y.shape) != (batch, rows, n_out) or y.dtype != torch.float32 or y.device != dev
-                    or (rows > 0 and y.stride(2) != 1)):
-                raise ValueError(f"_project_heads: into[{m!r}] must be a float32 [{batch}, {rows}, {n_out}] view on {dev} "
-                                 "with unit last stride")
-            ys[m] = R.forward_only(y, outputs, lin.weight, lin.bias)
-            if rows < 1:
-                continue
-            seg = L.HeadSegment()
-            seg.row0, seg.rows, seg.n_out = row0[m], rows, n_out
-            seg.w, seg.ldw, seg.bias = w.data_ptr(), w.stride(0), None if b is None else b.data_ptr()
-            seg.y, seg.y_sb, seg.y_rs = y.data_ptr(), y.stride(0) if batch > 1 else 0, y.stride(1)
-            plan.append(seg)
-            keep += [w, b, y]
-        if plan:
-            segs = (L.HeadSegment * len(plan))(*plan)
-            with R.on_device(dev):
-                L.check(L.lib().pio_project_heads(segs, len(plan), outputs.data_ptr(),
-                                                  outputs.stride(0) if batch > 1 else 0, outputs.stride(1), batch, qtot, k,
-                                                  R.stream_ptr(dev)), "pio_project_heads")
-        per_mod = restructure(query_sizes, outputs)
-        result = {}
-        for m, post in posts.items():
-            if m not in ys:
-                result[m] = post(per_mod[m], pos=None, modality_sizes=None)
-            elif type(post) is AudioPostprocessor and (into is None or m not in into):
-                result[m] = ys[m].reshape(batch, -1)
-            else:
-                result[m] = ys[m]
-        return result
+        return FIO.project_heads(self, outputs, query_sizes, into)
 
     def decoder_query(self, inputs, modality_sizes, inputs_without_pos=None, subsampled_points=None):
         per_mod = restructure(modality_sizes, inputs)

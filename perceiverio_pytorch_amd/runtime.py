@@ -568,6 +568,18 @@ class on_device:
         return self._ctx.__exit__(*exc)
 
 
+def call(dev, name, *args, stream=None, what=None, declines=(), tail=()):
+    """One launch through the C-ABI with `dev` current: entry point `name` with `args`, then the stream (the current one of
+    `dev` unless given), then `tail` (what pio_encoder_fwd_opts / pio_decoder_fwd_qcache take behind their stream).  An error
+    code raises PioError labelled `what or name`; a code in `declines` (the entry refused, nothing launched) returns False."""
+    with on_device(dev):
+        code = getattr(L.lib(), name)(*args, stream_ptr(dev) if stream is None else stream, *tail)
+    if code in declines:
+        return False
+    L.check(code, what or name)
+    return True
+
+
 def layernorm_desc(ln: torch.nn.LayerNorm, keep: list) -> L.LayerNorm:
     w, b = ln.weight.detach(), ln.bias.detach()
     if w.dtype != torch.float32:
@@ -584,9 +596,7 @@ def layernorm_desc(ln: torch.nn.LayerNorm, keep: list) -> L.LayerNorm:
 def hip_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], cache: dict) -> torch.Tensor:
     """y[..., out] = x[..., in] W^T + b on the MI355X under the current precision policy (weights split from level
     "x2w" on, activations under "x3").  `cache` keeps the packed weight image between calls."""
-    import ctypes as C
     require_device(x, "hip_linear")
-    lib = L.lib()
     dev = x.device
     dtype, wlevel, split = policy_dtype()
     key = param_key(weight, bias)
@@ -602,23 +612,21 @@ def hip_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     x16 = torch.empty((rows, lin.k), dtype=tdt, device=dev)
     x16lo = torch.empty((rows, lin.k), dtype=tdt, device=dev) if split else None
     out = torch.empty((rows, n_out), dtype=torch.float32, device=dev)
-    with on_device(dev):
-        L.check(lib.pio_layernorm_cast(tensor3(x3), None, x16.data_ptr(), x16lo.data_ptr() if split else None, lin.k,
-                                       dtype, stream_ptr(dev)), "pio_layernorm_cast")
-        g = L.Gemm()
-        g.A, g.B = x16.data_ptr(), lin.hi.data_ptr()
-        g.A_lo = x16lo.data_ptr() if split else None
-        g.B_lo = lin.lo.data_ptr() if lin.lo is not None else None
-        g.C = out.data_ptr()
-        g.M, g.N, g.K = rows, n_out, lin.k
-        g.lda = g.ldb = lin.k
-        g.ldc = n_out
-        g.batch = g.nh = 1
-        g.bias = lin.bias.data_ptr()
-        g.bias_mode = 1
-        g.alpha = 1.0
-        g.out_f32 = 1
-        g.n_store = n_out
-        g.dtype = dtype
-        L.check(lib.pio_gemm_nt(C.byref(g), stream_ptr(dev)), "pio_gemm_nt")
+    call(dev, "pio_layernorm_cast", tensor3(x3), None, x16.data_ptr(), x16lo.data_ptr() if split else None, lin.k, dtype)
+    g = L.Gemm()
+    g.A, g.B = x16.data_ptr(), lin.hi.data_ptr()
+    g.A_lo = x16lo.data_ptr() if split else None
+    g.B_lo = lin.lo.data_ptr() if lin.lo is not None else None
+    g.C = out.data_ptr()
+    g.M, g.N, g.K = rows, n_out, lin.k
+    g.lda = g.ldb = lin.k
+    g.ldc = n_out
+    g.batch = g.nh = 1
+    g.bias = lin.bias.data_ptr()
+    g.bias_mode = 1
+    g.alpha = 1.0
+    g.out_f32 = 1
+    g.n_store = n_out
+    g.dtype = dtype
+    call(dev, "pio_gemm_nt", C.byref(g))
     return forward_only(out.reshape(lead + (n_out,)), x, weight, bias)

@@ -230,11 +230,9 @@ class Attention(_HipModule):
         ws = R.workspace(dev, nbytes)
         tq, tk, tv = R.tensor3(xq), R.tensor3(xk), R.tensor3(xv)
         LP.expect("attention")
-        with R.on_device(dev):
-            L.check(lib.pio_attention_fwd(d, tq, tk, tv, None, None, fm_ptr,
-                                          bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
-                                          probs.data_ptr() if probs is not None else None, ws.data_ptr(),
-                                          ws.numel(), R.stream_ptr(dev)), "pio_attention_fwd")
+        R.call(dev, "pio_attention_fwd", d, tq, tk, tv, None, None, fm_ptr,
+               bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
+               probs.data_ptr() if probs is not None else None, ws.data_ptr(), ws.numel())
         out = R.forward_only(out, inputs_q, inputs_k, inputs_v, *self._params())
         if return_matrix:
             return probs, out
@@ -290,9 +288,7 @@ class MLP(_HipModule):
         out = torch.empty(x3.shape[:2] + (self.fc2.out_features,), dtype=torch.float32, device=dev)
         rows = x3.shape[0] * x3.shape[1]
         ws = R.workspace(dev, lib.pio_mlp_workspace_bytes(d, rows))
-        with R.on_device(dev):
-            L.check(lib.pio_mlp_fwd(d, R.tensor3(x3), out.data_ptr(), ws.data_ptr(), ws.numel(), R.stream_ptr(dev)),
-                    "pio_mlp_fwd")
+        R.call(dev, "pio_mlp_fwd", d, R.tensor3(x3), out.data_ptr(), ws.data_ptr(), ws.numel())
         out = R.forward_only(out, x, *self._params())
         return out.reshape(shape[:-1] + (self.fc2.out_features,))
 
@@ -425,11 +421,9 @@ class SelfAttention(_HipModule):
         probs = torch.empty((B, H, N, N), dtype=torch.float32, device=dev) if return_matrix else None
         ws = R.workspace(dev, lib.pio_self_attention_workspace_bytes(d, B, N))
         LP.expect("attention")
-        with R.on_device(dev):
-            L.check(lib.pio_self_attention_fwd(d, R.tensor3(x), None, None, fm_ptr,
-                                               bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
-                                               probs.data_ptr() if probs is not None else None, ws.data_ptr(),
-                                               ws.numel(), R.stream_ptr(dev)), "pio_self_attention_fwd")
+        R.call(dev, "pio_self_attention_fwd", d, R.tensor3(x), None, None, fm_ptr,
+               bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
+               probs.data_ptr() if probs is not None else None, ws.data_ptr(), ws.numel())
         out = R.forward_only(out, inputs, *self._params())
         if return_matrix:
             return probs, out
@@ -508,11 +502,9 @@ class CrossAttention(_HipModule):
         probs = torch.empty((B, H, Tq, Tk), dtype=torch.float32, device=dev) if return_matrix else None
         ws = R.workspace(dev, lib.pio_cross_attention_workspace_bytes(d, B, Tq, Tk))
         LP.expect("attention")
-        with R.on_device(dev):
-            L.check(lib.pio_cross_attention_fwd(d, R.tensor3(xq), R.tensor3(xkv), None, None, fm_ptr,
-                                                bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
-                                                probs.data_ptr() if probs is not None else None, ws.data_ptr(),
-                                                ws.numel(), R.stream_ptr(dev)), "pio_cross_attention_fwd")
+        R.call(dev, "pio_cross_attention_fwd", d, R.tensor3(xq), R.tensor3(xkv), None, None, fm_ptr,
+               bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
+               probs.data_ptr() if probs is not None else None, ws.data_ptr(), ws.numel())
         out = R.forward_only(out, inputs_q, inputs_kv, *self._params())
         if return_matrix:
             return probs, out

@@ -170,8 +170,9 @@ def test_refusals_launch_nothing(dev, what, changes, code):
 # the model
 # ----------------------------------------------------------------------------------------------------
 def _counting_cat(monkeypatch):
-    """torch.cat as models.py sees it: the shapes of every call's first piece (the stand-in of
-    tests/test_mm_front_gpu.py, applied to `models`)."""
+    """torch.cat as models.py and fused_io.py see it: the shapes of every call's first piece (the stand-in of
+    tests/test_mm_front_gpu.py, applied to `models` and `fused_io`)."""
+    from perceiverio_pytorch_amd import fused_io as FIO
     from perceiverio_pytorch_amd import models as M
     calls = []
 
@@ -183,6 +184,7 @@ def _counting_cat(monkeypatch):
             calls.append(tuple(tensors[0].shape))
             return torch.cat(tensors, *a, **kw)
     monkeypatch.setattr(M, "torch", _Torch())
+    monkeypatch.setattr(FIO, "torch", M.torch)
     return calls
 
 

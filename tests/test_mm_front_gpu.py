@@ -109,8 +109,9 @@ def test_refusals_launch_nothing(dev, what, changes, code):
 
 
 def _counting_cat(monkeypatch):
-    """torch.cat as perceiver.py sees it, counted (the module's `torch` name is replaced by a stand-in that forwards
-    everything else)."""
+    """torch.cat as perceiver.py and fused_io.py see it, counted (the modules' `torch` name is replaced by a stand-in that
+    forwards everything else)."""
+    from perceiverio_pytorch_amd import fused_io as FIO
     from perceiverio_pytorch_amd import perceiver as PV
     calls = []
 
@@ -122,6 +123,7 @@ def _counting_cat(monkeypatch):
             calls.append(1)
             return torch.cat(*a, **kw)
     monkeypatch.setattr(PV, "torch", _Torch())
+    monkeypatch.setattr(FIO, "torch", PV.torch)
     return calls
 
 

@@ -103,9 +103,10 @@ def test_refusals_launch_nothing(dev, what, changes, code):
 
 
 def _counting(monkeypatch):
-    """torch.cat as perceiver.py sees it (the hook of tests/test_mm_front_gpu.py) and pio_build_queries as every module sees
-    it, both counted."""
+    """torch.cat as perceiver.py and fused_io.py see it (the hook of tests/test_mm_front_gpu.py) and pio_build_queries as
+    every module sees it, both counted."""
     from perceiverio_pytorch_amd import _lib as L
+    from perceiverio_pytorch_amd import fused_io as FIO
     from perceiverio_pytorch_amd import perceiver as PV
     calls = {"cat": 0, "kernel": 0}
     real = L.lib()
@@ -127,6 +128,7 @@ def _counting(monkeypatch):
             return real.pio_build_queries(*a)
     proxy = _Lib()
     monkeypatch.setattr(PV, "torch", _Torch())
+    monkeypatch.setattr(FIO, "torch", PV.torch)
     monkeypatch.setattr(L, "lib", lambda: proxy)
     return calls
 
