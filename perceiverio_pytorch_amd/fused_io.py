@@ -234,7 +234,8 @@ def assemble_tokens(mm, inputs, pos):
 def query_tables(io, name, enc, device):
     """(axis tables, bands [d, K]) of a Fourier query on `device`, built once per module and device with the chain's own
     arithmetic: axis[j][i] = -1 + 2 * i / dims[j] as BasicQuery._encode computes it (int64 -> fp32 division on that
-    device), bands from the torch.linspace calls of generate_fourier_features."""
+    device), bands from the torch.linspace calls of generate_fourier_features.  Constants of the module's configuration:
+    they depend on no parameter, so no write can make them stale and `io` is no runtime.PackedOwner for them."""
     store = io.__dict__.setdefault("_query_table_cache", {})
     key = (name, str(device))
     hit = store.get(key)

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 from . import position_encoding as PE
 from .position_encoding import PosEncodingType, TrainablePositionEncoding
+from .runtime import PackedOwner, hip_linear
 from .transformer_primitives import lecun_normal_
 
 
@@ -396,16 +397,16 @@ class AudioPreprocessor(nn.Module, _PosMixin):
 # ---------------------------------------------------------------------------------------------------
 # postprocessors: forward(inputs, *, pos=None, modality_sizes=None)
 # ---------------------------------------------------------------------------------------------------
-def _linear(mod: nn.Linear, x: torch.Tensor, cache: dict) -> torch.Tensor:
+def _linear(mod: nn.Linear, x: torch.Tensor, cache) -> torch.Tensor:
     """The nn.Linear heads right behind the decoder run through libpio_hip.so (runtime.hip_linear: pio_gemm_nt under
-    the current -- decoder -- precision policy) on the GPU; on CPU tensors the stock torch path (plumbing tests)."""
+    the current -- decoder -- precision policy) on the GPU; on CPU tensors the stock torch path (plumbing tests).
+    `cache`: the owning postprocessor's (runtime.PackedOwner), which holds the packed image of the head."""
     if x.is_cuda:
-        from .runtime import hip_linear
         return hip_linear(x, mod.weight, mod.bias, cache)
     return mod(x)
 
 
-class EmbeddingPostprocessor(nn.Module):
+class EmbeddingPostprocessor(PackedOwner):
     """Logits against the (tied) token embedding + bias (postprocessors.py:12-34)."""
 
     def __init__(self, embedding: nn.Embedding):
@@ -413,15 +414,13 @@ class EmbeddingPostprocessor(nn.Module):
         self._embedding = embedding
         self._vocab_size, self._d_model = embedding.weight.shape
         self.bias = nn.Parameter(torch.zeros(self._vocab_size))
-        self._pio_linear = {}       # packed image of the tied weight (runtime.hip_linear)
 
     def forward(self, inputs: torch.Tensor, *, pos=None, modality_sizes=None) -> torch.Tensor:
         b, t, _ = inputs.shape
         if inputs.is_cuda:
             # the step right behind the decoder: [B*T, d_model] x [vocab, d_model]^T through libpio_hip.so
             # (pio_gemm_nt) under the model's precision policy, not a torch matmul
-            from .runtime import hip_linear
-            return hip_linear(inputs, self._embedding.weight, self.bias, self._pio_linear)
+            return hip_linear(inputs, self._embedding.weight, self.bias, self._packed)
         return (inputs.reshape(-1, self._d_model) @ self._embedding.weight.T + self.bias).reshape(b, t,
                                                                                                  self._vocab_size)
 
@@ -455,7 +454,7 @@ class ImagePostprocessor(nn.Module):
         return inputs
 
 
-class AudioPostprocessor(nn.Module):
+class AudioPostprocessor(PackedOwner):
     """Linear to ``samples_per_patch`` then flatten to a waveform (postprocessors.py:125-149)."""
 
     def __init__(self, postproc_type: str = "patches", in_channels: int = 1024, samples_per_patch: int = 96):
@@ -466,10 +465,9 @@ class AudioPostprocessor(nn.Module):
         self.linear = nn.Linear(in_channels, samples_per_patch)
         lecun_normal_(self.linear.weight)
         nn.init.constant_(self.linear.bias, 0)
-        self._pio_linear = {}
 
     def forward(self, inputs: torch.Tensor, *, pos=None, modality_sizes=None) -> torch.Tensor:
-        return _linear(self.linear, inputs, self._pio_linear).reshape(inputs.shape[0], -1)
+        return _linear(self.linear, inputs, self._packed).reshape(inputs.shape[0], -1)
 
 
 class IdentityPostprocessor(nn.Module):
@@ -477,14 +475,13 @@ class IdentityPostprocessor(nn.Module):
         return inputs
 
 
-class ClassificationPostprocessor(nn.Module):
+class ClassificationPostprocessor(PackedOwner):
     """Optional linear head, then the logits of query row 0 (postprocessors.py:164-187)."""
 
     def __init__(self, num_input_channels: int, num_classes: int, project: bool = True):
         super().__init__()
         self._num_classes = num_classes
         self._project = project
-        self._pio_linear = {}
         if project:
             self.linear = nn.Linear(num_input_channels, num_classes)
             lecun_normal_(self.linear.weight)
@@ -493,10 +490,10 @@ class ClassificationPostprocessor(nn.Module):
     def forward(self, inputs: torch.Tensor, *, pos=None, modality_sizes=None) -> torch.Tensor:
         # (rows are independent: the head is applied to the one row that is kept)
         row0 = inputs[:, 0:1, :]
-        return (_linear(self.linear, row0, self._pio_linear) if self._project else row0)[:, 0, :]
+        return (_linear(self.linear, row0, self._packed) if self._project else row0)[:, 0, :]
 
 
-class ProjectionPostprocessor(nn.Module):
+class ProjectionPostprocessor(PackedOwner):
     """A linear projection of every output row (postprocessors.py:190-208)."""
 
     def __init__(self, num_inputs: int, num_outputs: int):
@@ -505,10 +502,9 @@ class ProjectionPostprocessor(nn.Module):
         self.projection = nn.Linear(num_inputs, num_outputs)
         lecun_normal_(self.projection.weight)
         nn.init.constant_(self.projection.bias, 0)
-        self._pio_linear = {}
 
     def forward(self, inputs: torch.Tensor, *, pos=None, modality_sizes=None) -> torch.Tensor:
-        return _linear(self.projection, inputs, self._pio_linear)
+        return _linear(self.projection, inputs, self._packed)
 
 
 class FlowPostprocessor(nn.Module):

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 from . import fused_io as FIO
 from . import io_processors
+from . import runtime as R
 from .io_processors import (AudioPostprocessor, AudioPreprocessor, ClassificationPostprocessor,
                             EmbeddingPostprocessor, EmbeddingPreprocessor, FlowPostprocessor, ImagePreprocessor,
                             OneHotPreprocessor, ProjectionPostprocessor)
@@ -338,7 +339,7 @@ class FlowPerceiver(nn.Module):
         return total / weight
 
 
-class MultiModalPerceiver(nn.Module):
+class MultiModalPerceiver(R.PackedOwner):
     """Video + audio + label auto-encoder (reference multimodal_perceiver.py:12-167).  The output is decoded in
     ``n_chunks`` query chunks.  The encoder input does not depend on the chunk (mask probabilities are 0 / 0 / 1), so
     by default the preprocess + encode step runs ONCE and only the decoder runs per chunk (`encode_once=False`
@@ -455,24 +456,23 @@ class MultiModalPerceiver(nn.Module):
         P = self.perceiver
         if not self.cache_queries:
             return P.decoder_query(x, sizes, without_pos, subsampled_points=points) + (None,)
-        from . import runtime as R
         params = [p for q in P._output_queries.values() for p in q.parameters()] + list(P.padding_embeddings.parameters())
         key = (chunk_key, str(x.device), tuple(sorted(sizes.items())), R.param_key(*params)[:-1])
-        store = self.__dict__.setdefault("_query_cache", {})
-        hit = store.get(key)
-        if hit is None:
+
+        def build():
             with torch.inference_mode(False), torch.no_grad():
                 # (the queries read the batch size and the device from their input, nothing else: a ONE-sample stand-in of
                 #  the right length keeps the cached array batch-invariant and an ordinary -- not inference-mode -- tensor)
                 shape_only = torch.zeros((1, x.shape[1], 1), device=x.device)
                 q, qsizes = P.decoder_query(shape_only, sizes, None, subsampled_points=points)
             nbytes = q.numel() * q.element_size()
-            held = sum(v[0].numel() * v[0].element_size() for v in store.values())
+            held = sum(v[0].numel() * v[0].element_size() for v in self._packed.values())
             if held + nbytes > self.query_cache_max_bytes:
-                store.clear()
-            hit = (q, qsizes, {})          # ({}: the decoder's cache of the PROJECTED queries of this array)
-            store[key] = hit
-        q, qsizes, qc = hit
+                self._packed.clear()
+            return (q, qsizes, {}), None          # ({}: the decoder's cache of the PROJECTED queries of this array)
+
+        # (one slot per key: the arrays of every chunk group and parameter version stay side by side, up to the byte cap)
+        q, qsizes, qc = self._packed.get(key, build, slot=key)
         return torch.broadcast_to(q, (x.shape[0],) + tuple(q.shape[1:])), qsizes, qc
 
     def _forward(self, images, audio, n_chunks):
@@ -533,7 +533,6 @@ class MultiModalPerceiver(nn.Module):
                 rec["audio"].append(out["audio"])
             rec["label"].extend([out["label"][:, None]] * g)      # (one label estimate per chunk, as the reference has)
         if bufs is not None:
-            from . import runtime as R
             image, sound = R.forward_only(bufs["image"], *tied), R.forward_only(bufs["audio"], *tied)
         else:
             image, sound = torch.cat(rec["image"], dim=1), torch.cat(rec["audio"], dim=1)

@@ -21,7 +21,7 @@ from .position_encoding import TrainablePositionEncoding
 from .transformer_primitives import CrossAttention, SelfAttention, lecun_normal_, make_cross_attention_mask  # noqa: F401
 
 
-class PerceiverEncoder(nn.Module):
+class PerceiverEncoder(R.PackedOwner):
     """Cross-attend inputs into the latent array, then num_blocks x (weight-shared) self-attend block."""
 
     def __init__(self, num_input_channels: int, num_self_attends_per_block: int = 6, num_blocks: int = 8,
@@ -105,9 +105,7 @@ class PerceiverEncoder(nn.Module):
             flag.zero_()
         # the descriptor array handed to the library: rebuilt only when a descriptor or the guard word changes (the
         # cached descriptor objects are replaced whenever their parameters / the policy change)
-        lkey = (tuple(id(d) for ds in descs for d in ds), flag.data_ptr() if guard else 0)
-        lc = self.__dict__.get("_layers_cache")
-        if lc is None or lc[0] != lkey:
+        def build_layers():
             layers = (L.SelfAttention * max(Lyr * nset, 1))()
             for i, ds in enumerate(descs):
                 for b, d in enumerate(ds):
@@ -115,21 +113,26 @@ class PerceiverEncoder(nn.Module):
             if guard:
                 for i in range(Lyr * nset):
                     layers[i].fold.range_flag = flag.data_ptr()
-            self.__dict__["_layers_cache"] = lc = (lkey, layers, descs)     # (descs: keeps the ids alive)
-        layers = lc[1]
-        nsplit = R.batch_streams()
-        if nsplit <= 1 or B < 2 * nsplit or B % nsplit or inputs_tail is not None or per_block:
-            ws = R.workspace(dev, lib.pio_encoder_workspace_bytes(cross, layers, Lyr, B, M, N))
-            # (the un-folded repeat of the range guard is a PER-CALL option: no process state changes around the call)
-            opts = L.CallOpts(1 if self._range_fallback else 0, 0)
+            return layers, descs     # (descs: keeps the ids of the key alive)
+
+        layers = self._packed.get((tuple(id(d) for ds in descs for d in ds), flag.data_ptr() if guard else 0), build_layers)
+
+        def launch(xs, tail, zs, mask_ptr, out_ptr, blockwise, opts, stream=None):
+            """One pio_encoder_fwd_opts call on the current stream's workspace (the whole batch, or one batch slice)."""
             LP.expect("cross", *["stack"] * (Lyr * self._num_blocks))    # (one attention call per block, this order)
             LP.mark_range("cross")           # (range probe: the library marks "stack" behind the cross-attend itself)
             try:
-                R.call(dev, "pio_encoder_fwd_opts", cross, layers, Lyr, self._num_blocks, int(per_block), R.tensor3(x),
-                       tail3, R.tensor3(z0), im_ptr, out.data_ptr(), ws.data_ptr(), ws.numel(), tail=(opts,),
+                ws = R.workspace(dev, lib.pio_encoder_workspace_bytes(cross, layers, Lyr, xs.shape[0], M, N))
+                R.call(dev, "pio_encoder_fwd_opts", cross, layers, Lyr, self._num_blocks, blockwise, R.tensor3(xs), tail,
+                       R.tensor3(zs), mask_ptr, out_ptr, ws.data_ptr(), ws.numel(), stream=stream, tail=(opts,),
                        what="pio_encoder_fwd")
             finally:
                 LP.mark_range("attention")
+
+        nsplit = R.batch_streams()
+        if nsplit <= 1 or B < 2 * nsplit or B % nsplit or inputs_tail is not None or per_block:
+            # (the un-folded repeat of the range guard is a PER-CALL option: no process state changes around the call)
+            launch(x, tail3, z0, im_ptr, out.data_ptr(), int(per_block), L.CallOpts(1 if self._range_fallback else 0, 0))
             return self._finish(out, flag, inputs, inputs_tail, latents, input_mask)
         # Samples are independent: run `nsplit` batch slices as independent kernel chains on side streams so that
         # one chain's fill / drain / HBM-bound kernels overlap the other's MFMA-bound ones (each slice still fills
@@ -144,18 +147,10 @@ class PerceiverEncoder(nn.Module):
         for side in sides:                   # every slice starts behind the work already queued on `cur` ...
             side.wait_stream(cur)
         for i, side in enumerate(sides):
-            LP.expect("cross", *["stack"] * (Lyr * self._num_blocks))
-            LP.mark_range("cross")
-            try:
-                with torch.cuda.stream(side):
-                    xs, zs = x[i * bs:(i + 1) * bs], z0[i * bs:(i + 1) * bs]
-                    ws = R.workspace(dev, lib.pio_encoder_workspace_bytes(cross, layers, Lyr, bs, M, N))
-                    mp = im_ptr + i * bs * M if im_ptr is not None else None
-                    R.call(dev, "pio_encoder_fwd_opts", cross, layers, Lyr, self._num_blocks, 0, R.tensor3(xs), None,
-                           R.tensor3(zs), mp, out[i * bs:(i + 1) * bs].data_ptr(), ws.data_ptr(), ws.numel(),
-                           stream=side.cuda_stream, tail=(opts,), what="pio_encoder_fwd")
-            finally:
-                LP.mark_range("attention")
+            with torch.cuda.stream(side):
+                launch(x[i * bs:(i + 1) * bs], None, z0[i * bs:(i + 1) * bs],
+                       im_ptr + i * bs * M if im_ptr is not None else None, out[i * bs:(i + 1) * bs].data_ptr(), 0, opts,
+                       stream=side.cuda_stream)
         for side in sides:                   # ... and `cur` continues behind ALL of them (a wait queued between
             cur.wait_stream(side)            # two slices would chain them one after the other)
         for t in (x, z0, out):
@@ -194,7 +189,7 @@ class PerceiverEncoder(nn.Module):
             self._range_fallback = False
 
 
-class PerceiverDecoder(nn.Module):
+class PerceiverDecoder(R.PackedOwner):
     """Cross-attention decoder (queries attend to latents) with an optional final nn.Linear."""
 
     def __init__(self, query_channels: int, final_project_out_channels: int, num_latent_channels: int = 1024,
@@ -214,7 +209,6 @@ class PerceiverDecoder(nn.Module):
                                                   shape_for_attn="kv", qk_channels=self._qk_channels,
                                                   v_channels=self._v_channels,
                                                   use_query_residual=self._use_query_residual)
-        self._final_cache = None
         if self._final_project:
             self.final_layer = nn.Linear(query_channels, self._output_num_channels)
             if self._output_w_init == "lecun_normal":
@@ -225,21 +219,13 @@ class PerceiverDecoder(nn.Module):
                 raise ValueError(f"{self._output_w_init} not supported as output_w_init")
             nn.init.constant_(self.final_layer.bias, 0)
 
-    def _apply(self, fn, *a, **k):
-        self._final_cache = None
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._final_cache = None
-        return super()._load_from_state_dict(*a, **k)
-
     def _final_desc(self):
-        key = R.param_key(self.final_layer.weight, self.final_layer.bias)
-        if self._final_cache is None or self._final_cache[0] != key:
-            dtype, wlevel, _split = R.policy_dtype()
-            two = wlevel >= 2 or "final_layer" in R.policy_fine_split()
-            self._final_cache = (key, R.PackedLinear(self.final_layer.weight, self.final_layer.bias, 1, 1, dtype, two))
-        return self._final_cache[1]
+        return self._packed.get(R.param_key(self.final_layer.weight, self.final_layer.bias), self._build_final)
+
+    def _build_final(self):
+        dtype, wlevel, _split = R.policy_dtype()
+        two = wlevel >= 2 or "final_layer" in R.policy_fine_split()
+        return R.PackedLinear(self.final_layer.weight, self.final_layer.bias, 1, 1, dtype, two), None
 
     def forward(self, query, latents, *, query_mask=None, q_cache=None):
         """Reference signature (perceiver.py:166) plus `q_cache`: a dict the CALLER keeps per query array whose content

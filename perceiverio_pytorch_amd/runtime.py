@@ -519,15 +519,67 @@ def param_key(*params) -> tuple:
     return tuple((p.data_ptr(), _version_of(p), str(p.device)) if p is not None else None for p in params) + (_policy,)
 
 
+class PackedCache:
+    """What a module derives from its parameters (packed images, descriptors, parameter-only arrays), by slot:
+    slot -> (key, value, keep).  `keep` is whatever the value points into without owning it; it lives exactly as long as
+    the entry.  A plain object: no parameter, no buffer, nothing in state_dict().  A deepcopy or pickle of the owner
+    carries an EMPTY cache (ctypes descriptors cannot be copied, and a copy's parameters live elsewhere): it repacks on
+    first use."""
+
+    def __init__(self):
+        self._entries = {}
+
+    def get(self, key, build, slot=None):
+        """The value of `slot`, from `build() -> (value, keep)` when there is none under `key` yet."""
+        e = self._entries.get(slot)
+        if e is None or e[0] != key:
+            value, keep = build()
+            self._entries[slot] = e = (key, value, keep)
+        return e[1]
+
+    def held(self, slot=None):
+        """The current entry of `slot` as one object: what a parent's entry lists in its `keep` to hold a child's images."""
+        return self._entries.get(slot)
+
+    def values(self):
+        return [e[1] for e in self._entries.values()]
+
+    def clear(self) -> None:
+        self._entries.clear()
+
+    def __len__(self) -> int:
+        return len(self._entries)
+
+    def __getstate__(self):         # (copy.deepcopy and pickle both come through here)
+        return {"_entries": {}}
+
+
+class PackedOwner(torch.nn.Module):
+    """A module that keeps something derived from parameters: ONE cache, dropped by everything that can change a
+    parameter behind the key's back."""
+
+    def __init__(self):
+        super().__init__()
+        self._packed = PackedCache()
+
+    def clear_packed(self) -> None:
+        self._packed.clear()
+
+    def _apply(self, fn, *a, **k):       # .to()/.cuda()/.float() invalidate packed images
+        self._packed.clear()
+        return super()._apply(fn, *a, **k)
+
+    def _load_from_state_dict(self, *a, **k):   # load_state_dict copies through .data on some paths: repack
+        self._packed.clear()
+        return super()._load_from_state_dict(*a, **k)
+
+
 def invalidate_packed_weights(module: torch.nn.Module) -> None:
-    """Drop every packed / folded weight image cached under ``module`` (they are rebuilt on the next forward)."""
+    """Drop everything cached from parameters under ``module``: packed / folded weight images, descriptors, parameter-only
+    query arrays and their projections (all rebuilt on the next forward)."""
     for m in module.modules():
-        if hasattr(m, "_pio_cache"):
-            m._pio_cache = None
-        if hasattr(m, "_pio_block_cache"):
-            m._pio_block_cache = None
-        if hasattr(m, "_final_cache"):
-            m._final_cache = None
+        if isinstance(m, PackedOwner):
+            m.clear_packed()
 
 
 class _ForwardOnly(torch.autograd.Function):
@@ -593,18 +645,14 @@ def layernorm_desc(ln: torch.nn.LayerNorm, keep: list) -> L.LayerNorm:
 # a plain nn.Linear through the C-ABI primitives (pio_layernorm_cast as the operand cast + pio_gemm_nt): used by the
 # I/O plumbing right behind the decoder (tied-embedding vocabulary projection of the language model)
 # ------------------------------------------------------------------------------------------------
-def hip_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], cache: dict) -> torch.Tensor:
+def hip_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], cache: PackedCache) -> torch.Tensor:
     """y[..., out] = x[..., in] W^T + b on the MI355X under the current precision policy (weights split from level
-    "x2w" on, activations under "x3").  `cache` keeps the packed weight image between calls."""
+    "x2w" on, activations under "x3").  `cache` (the owner's) keeps the packed weight image between calls."""
     require_device(x, "hip_linear")
     dev = x.device
     dtype, wlevel, split = policy_dtype()
-    key = param_key(weight, bias)
-    pk = cache.get("packed")
-    if pk is None or pk[0] != key:
-        pk = (key, PackedLinear(weight, bias, 1, 1, dtype, wlevel >= 2 or "post" in policy_fine_split()))
-        cache["packed"] = pk
-    lin = pk[1]
+    lin = cache.get(param_key(weight, bias), lambda: (
+        PackedLinear(weight, bias, 1, 1, dtype, wlevel >= 2 or "post" in policy_fine_split()), None))
     lead = x.shape[:-1]
     x3 = as_f32_3d(x.reshape(1, -1, x.shape[-1]))
     rows, n_out = x3.shape[1], weight.shape[0]

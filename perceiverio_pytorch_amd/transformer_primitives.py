@@ -70,28 +70,38 @@ def _no_training_dropout(mod: nn.Module, *probs: float) -> None:
         raise NotImplementedError("the HIP path is forward/inference only: call .eval() or use dropout_prob=0")
 
 
-class _HipModule(nn.Module):
-    """Shared packed-weight cache handling."""
+def _block_call(entry, ws_entry, ws_args, d, tensors, dims, out_channels, mask, bias, return_matrix, deps):
+    """The common tail of the three block forwards: full mask to bytes, bias broadcast over `dims` = (B, H, Tq, Tk), the
+    `out` / `probs` buffers, the workspace of `ws_entry(d, *ws_args)`, the launch of `entry` on `tensors`, and the
+    result tied to `deps` (runtime.forward_only).  Returns out, or (probs, out) with `return_matrix`."""
+    B, H, Tq, Tk = dims
+    dev = tensors[0].device
+    fm, fm_ptr = R.mask_u8(mask, (B, Tq, Tk), dev)
+    bias_t = None
+    if bias is not None:
+        bias_t = torch.broadcast_to(bias.to(device=dev, dtype=torch.float32), dims).contiguous()
+    out = torch.empty((B, Tq, out_channels), dtype=torch.float32, device=dev)
+    probs = torch.empty(dims, dtype=torch.float32, device=dev) if return_matrix else None
+    ws = R.workspace(dev, getattr(L.lib(), ws_entry)(d, *ws_args))
+    LP.expect("attention")
+    R.call(dev, entry, d, *[R.tensor3(t) for t in tensors], None, None, fm_ptr,
+           bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
+           probs.data_ptr() if probs is not None else None, ws.data_ptr(), ws.numel())
+    out = R.forward_only(out, *deps)
+    return (probs, out) if return_matrix else out
 
-    def __init__(self):
-        super().__init__()
-        self._pio_cache = None      # (key, descriptor, keep-alive list)
-        self._pio_block_cache = None    # (key, [descriptor per block], keep-alive list): policy "fp16sd"
 
-    def _cached(self, key, builder):
-        c = self._pio_cache
-        if c is None or c[0] != key:
-            desc, keep = builder()
-            self._pio_cache = c = (key, desc, keep)
-        return c[1]
+class _HipModule(R.PackedOwner):
+    """A block module: its descriptor (and the images behind it) under its parameters' key."""
 
-    def _apply(self, fn, *a, **k):       # .to()/.cuda()/.float() invalidate packed images
-        self._pio_cache = self._pio_block_cache = None
-        return super()._apply(fn, *a, **k)
+    def _desc(self):
+        return self._packed.get(R.param_key(*self._params()), self._build_desc)
 
-    def _load_from_state_dict(self, *a, **k):   # load_state_dict copies through .data on some paths: repack
-        self._pio_cache = self._pio_block_cache = None
-        return super()._load_from_state_dict(*a, **k)
+    def _child_entries(self):
+        """For a parent's `keep`.  INVARIANT: parent entry alive => child images alive.  The parent's descriptor holds raw
+        pointers into the images of attention / mlp; it names the children's current entries -- the ones their _desc()
+        calls just returned -- as dependencies, so a child that repacks cannot free what a live parent entry points to."""
+        return [self.attention._packed.held(), self.mlp._packed.held()]
 
 
 # ==================================================================================================
@@ -200,9 +210,6 @@ class Attention(_HipModule):
         return (self.proj_q.weight, self.proj_q.bias, self.proj_k.weight, self.proj_k.bias, self.proj_v.weight,
                 self.proj_v.bias, self.final.weight, self.final.bias)
 
-    def _desc(self) -> L.Attention:
-        return self._cached(R.param_key(*self._params()), self._build_desc)
-
     def forward(self, inputs_q, inputs_k, inputs_v, attention_mask=None, attention_bias=None,
                 return_matrix=False):
         if R.cpu_plumbing(inputs_q, "Attention.forward"):
@@ -210,33 +217,14 @@ class Attention(_HipModule):
             return CP.attention(self, inputs_q, inputs_k, inputs_v, attention_mask, attention_bias, return_matrix)
         R.require_device(inputs_q, "Attention.forward")
         _no_training_dropout(self, self.dropout.p)
-        lib = L.lib()
         xq, xk, xv = R.as_f32_3d(inputs_q), R.as_f32_3d(inputs_k), R.as_f32_3d(inputs_v)
         if inputs_v is inputs_k:
             xv = xk
         B, Tq, _ = xq.shape
         Tk = xk.shape[1]
-        dev = xq.device
-        d = self._desc()
-        H = self._num_heads
-        fm, fm_ptr = R.mask_u8(attention_mask, (B, Tq, Tk), dev)
-        bias_t = None
-        if attention_bias is not None:
-            bias_t = torch.broadcast_to(attention_bias.to(device=dev, dtype=torch.float32),
-                                        (B, H, Tq, Tk)).contiguous()
-        out = torch.empty((B, Tq, self.final.out_features), dtype=torch.float32, device=dev)
-        probs = torch.empty((B, H, Tq, Tk), dtype=torch.float32, device=dev) if return_matrix else None
-        nbytes = lib.pio_attention_workspace_bytes(d, B, Tq, Tk)
-        ws = R.workspace(dev, nbytes)
-        tq, tk, tv = R.tensor3(xq), R.tensor3(xk), R.tensor3(xv)
-        LP.expect("attention")
-        R.call(dev, "pio_attention_fwd", d, tq, tk, tv, None, None, fm_ptr,
-               bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
-               probs.data_ptr() if probs is not None else None, ws.data_ptr(), ws.numel())
-        out = R.forward_only(out, inputs_q, inputs_k, inputs_v, *self._params())
-        if return_matrix:
-            return probs, out
-        return out
+        return _block_call("pio_attention_fwd", "pio_attention_workspace_bytes", (B, Tq, Tk), self._desc(), (xq, xk, xv),
+                           (B, self._num_heads, Tq, Tk), self.final.out_features, attention_mask, attention_bias,
+                           return_matrix, (inputs_q, inputs_k, inputs_v) + self._params())
 
 
 # ==================================================================================================
@@ -270,9 +258,6 @@ class MLP(_HipModule):
 
     def _params(self):
         return (self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
-
-    def _desc(self) -> L.Mlp:
-        return self._cached(R.param_key(*self._params()), self._build_desc)
 
     def forward(self, x):
         if R.cpu_plumbing(x, "MLP.forward"):
@@ -325,34 +310,32 @@ class SelfAttention(_HipModule):
         m = self.mlp._desc()
         d = L.SelfAttention(R.layernorm_desc(self.layer_norm1, keep), R.layernorm_desc(self.layer_norm2, keep), a, m)
         self._build_ln_fold(d, a, keep)
-        return d, keep + [self.attention._pio_cache, self.mlp._pio_cache]
+        return d, keep + self._child_entries()
 
     def _desc_blocks(self, nblk: int):
         """Policy "fp16sd": one descriptor per block of a weight-shared stack, block b packed from the b-th
         error-feedback rounding of every weight (runtime.feedback_images) -- of W for the plain images, of W * gamma
         for the images of the LayerNorm fold (the feedback runs over what the GEMM actually multiplies with)."""
-        key = R.param_key(*self._params()) + (nblk,)
-        c = self._pio_block_cache
-        if c is None or c[0] != key:
-            dtype, _wlevel, _split = R.policy_dtype()
-            att, mlp = self.attention, self.mlp
-            lins = (att.proj_q, att.proj_k, att.proj_v, att.final, mlp.fc1, mlp.fc2)
-            descs, keep = [], []
-            with torch.no_grad():
-                g1, g2 = self.layer_norm1.weight.float(), self.layer_norm2.weight.float()
-                plain = {lin: R.feedback_images(lin.weight, nblk, dtype) for lin in lins}
-                fold = {lin: R.feedback_images(lin.weight.float() * g[None, :], nblk, dtype)
-                        for lin, g in ((att.proj_q, g1), (att.proj_k, g1), (att.proj_v, g1), (mlp.fc1, g2))}
-                for b in range(nblk):
-                    a, ka = att._build_desc({lin: plain[lin][b] for lin in lins[:4]})
-                    m, km = mlp._build_desc({lin: plain[lin][b] for lin in lins[4:]})
-                    d = L.SelfAttention(R.layernorm_desc(self.layer_norm1, keep), R.layernorm_desc(self.layer_norm2, keep),
-                                        a, m)
-                    self._build_ln_fold(d, a, keep, {lin: imgs[b] for lin, imgs in fold.items()})
-                    descs.append(d)
-                    keep.extend([ka, km])
-            self._pio_block_cache = c = (key, descs, keep)
-        return c[1]
+        return self._packed.get(R.param_key(*self._params()) + (nblk,), lambda: self._build_blocks(nblk), slot="blocks")
+
+    def _build_blocks(self, nblk: int):
+        dtype, _wlevel, _split = R.policy_dtype()
+        att, mlp = self.attention, self.mlp
+        lins = (att.proj_q, att.proj_k, att.proj_v, att.final, mlp.fc1, mlp.fc2)
+        descs, keep = [], []
+        with torch.no_grad():
+            g1, g2 = self.layer_norm1.weight.float(), self.layer_norm2.weight.float()
+            plain = {lin: R.feedback_images(lin.weight, nblk, dtype) for lin in lins}
+            fold = {lin: R.feedback_images(lin.weight.float() * g[None, :], nblk, dtype)
+                    for lin, g in ((att.proj_q, g1), (att.proj_k, g1), (att.proj_v, g1), (mlp.fc1, g2))}
+            for b in range(nblk):
+                a, ka = att._build_desc({lin: plain[lin][b] for lin in lins[:4]})
+                m, km = mlp._build_desc({lin: plain[lin][b] for lin in lins[4:]})
+                d = L.SelfAttention(R.layernorm_desc(self.layer_norm1, keep), R.layernorm_desc(self.layer_norm2, keep), a, m)
+                self._build_ln_fold(d, a, keep, {lin: imgs[b] for lin, imgs in fold.items()})
+                descs.append(d)
+                keep.extend([ka, km])
+        return descs, keep
 
     def _build_ln_fold(self, d, a, keep, fold_ov=None):
         """LayerNorm folded into the consuming GEMMs (pio_ln_fold_t): LN(x) W^T + b = rstd (x W'^T - mean c) + b' with
@@ -391,9 +374,6 @@ class SelfAttention(_HipModule):
         return self.attention._params() + self.mlp._params() + (self.layer_norm1.weight, self.layer_norm1.bias,
                                                                  self.layer_norm2.weight, self.layer_norm2.bias)
 
-    def _desc(self) -> L.SelfAttention:
-        return self._cached(R.param_key(*self._params()), self._build_desc)
-
     def forward(self, inputs, *, attention_mask=None, attention_bias=None, return_matrix: bool = False):
         if R.cpu_plumbing(inputs, "SelfAttention.forward"):
             from . import cpu_plumbing as CP
@@ -407,27 +387,11 @@ class SelfAttention(_HipModule):
             # the residual add of the reference (:290) raises for mismatched widths
             raise RuntimeError(f"The size of tensor a ({self._in_channels}) must match the size of tensor b "
                                f"({self._v_channels}) at non-singleton dimension 2")
-        lib = L.lib()
         x = R.as_f32_3d(inputs)
         B, N, D = x.shape
-        dev = x.device
-        H = self.attention._num_heads
-        d = self._desc()
-        fm, fm_ptr = R.mask_u8(attention_mask, (B, N, N), dev)
-        bias_t = None
-        if attention_bias is not None:
-            bias_t = torch.broadcast_to(attention_bias.to(device=dev, dtype=torch.float32), (B, H, N, N)).contiguous()
-        out = torch.empty((B, N, D), dtype=torch.float32, device=dev)
-        probs = torch.empty((B, H, N, N), dtype=torch.float32, device=dev) if return_matrix else None
-        ws = R.workspace(dev, lib.pio_self_attention_workspace_bytes(d, B, N))
-        LP.expect("attention")
-        R.call(dev, "pio_self_attention_fwd", d, R.tensor3(x), None, None, fm_ptr,
-               bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
-               probs.data_ptr() if probs is not None else None, ws.data_ptr(), ws.numel())
-        out = R.forward_only(out, inputs, *self._params())
-        if return_matrix:
-            return probs, out
-        return out
+        return _block_call("pio_self_attention_fwd", "pio_self_attention_workspace_bytes", (B, N), self._desc(), (x,),
+                           (B, self.attention._num_heads, N, N), D, attention_mask, attention_bias, return_matrix,
+                           (inputs,) + self._params())
 
 
 # ==================================================================================================
@@ -469,15 +433,12 @@ class CrossAttention(_HipModule):
         d = L.CrossAttention(R.layernorm_desc(self.layer_norm_q, keep), R.layernorm_desc(self.layer_norm_kv, keep),
                              R.layernorm_desc(self.layer_norm2, keep), self.attention._desc(), self.mlp._desc(),
                              1 if self._use_query_residual else 0)
-        return d, keep + [self.attention._pio_cache, self.mlp._pio_cache]
+        return d, keep + self._child_entries()
 
     def _params(self):
         return self.attention._params() + self.mlp._params() + (
             self.layer_norm_q.weight, self.layer_norm_q.bias, self.layer_norm_kv.weight, self.layer_norm_kv.bias,
             self.layer_norm2.weight, self.layer_norm2.bias)
-
-    def _desc(self) -> L.CrossAttention:
-        return self._cached(R.param_key(*self._params()), self._build_desc)
 
     def forward(self, inputs_q, inputs_kv, *, attention_mask=None, attention_bias=None,
                 return_matrix: bool = False):
@@ -486,26 +447,9 @@ class CrossAttention(_HipModule):
             return CP.cross_attention(self, inputs_q, inputs_kv, attention_mask, attention_bias, return_matrix)
         R.require_device(inputs_q, "CrossAttention.forward")
         _no_training_dropout(self, self.dropout.p, self.attention.dropout.p, self.mlp.dropout.p)
-        lib = L.lib()
         xq, xkv = R.as_f32_3d(inputs_q), R.as_f32_3d(inputs_kv)
         B, Tq, Cq = xq.shape
         Tk = xkv.shape[1]
-        dev = xq.device
-        H = self.attention._num_heads
-        d = self._desc()
-        fm, fm_ptr = R.mask_u8(attention_mask, (B, Tq, Tk), dev)
-        bias_t = None
-        if attention_bias is not None:
-            bias_t = torch.broadcast_to(attention_bias.to(device=dev, dtype=torch.float32),
-                                        (B, H, Tq, Tk)).contiguous()
-        out = torch.empty((B, Tq, Cq), dtype=torch.float32, device=dev)
-        probs = torch.empty((B, H, Tq, Tk), dtype=torch.float32, device=dev) if return_matrix else None
-        ws = R.workspace(dev, lib.pio_cross_attention_workspace_bytes(d, B, Tq, Tk))
-        LP.expect("attention")
-        R.call(dev, "pio_cross_attention_fwd", d, R.tensor3(xq), R.tensor3(xkv), None, None, fm_ptr,
-               bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
-               probs.data_ptr() if probs is not None else None, ws.data_ptr(), ws.numel())
-        out = R.forward_only(out, inputs_q, inputs_kv, *self._params())
-        if return_matrix:
-            return probs, out
-        return out
+        return _block_call("pio_cross_attention_fwd", "pio_cross_attention_workspace_bytes", (B, Tq, Tk), self._desc(),
+                           (xq, xkv), (B, self.attention._num_heads, Tq, Tk), Cq, attention_mask, attention_bias,
+                           return_matrix, (inputs_q, inputs_kv) + self._params())

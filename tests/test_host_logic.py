@@ -156,15 +156,18 @@ def test_packed_weight_cache_invalidation_hooks():
     from perceiverio_pytorch_amd import invalidate_packed_weights, runtime as R
     from perceiverio_pytorch_amd.perceiver import PerceiverDecoder
     from perceiverio_pytorch_amd.transformer_primitives import MLP
+    stale = lambda: (None, None)  # noqa: E731
     m = MLP(8, widening_factor=1)
-    m._pio_cache = ("stale", None, None)
+    m._packed.get("stale", stale)
+    assert m._packed.held() == ("stale", None, None)
     m.load_state_dict(m.state_dict())               # load_state_dict drops the packed images
-    assert m._pio_cache is None
+    assert m._packed.held() is None
     d = PerceiverDecoder(8, 4, num_latent_channels=8)
-    d._final_cache = ("stale", None)
-    d.decoding_cross_attn.mlp._pio_cache = ("stale", None, None)
+    d._packed.get("stale", stale)
+    d.decoding_cross_attn.mlp._packed.get("stale", stale)
+    assert len(d._packed) == 1 and len(d.decoding_cross_attn.mlp._packed) == 1
     invalidate_packed_weights(d)
-    assert d._final_cache is None and d.decoding_cross_attn.mlp._pio_cache is None
+    assert d._packed.held() is None and d.decoding_cross_attn.mlp._packed.held() is None
     with torch.inference_mode():
         p = torch.nn.Parameter(torch.ones(2))
         assert R.param_key(p)[0][1] == 0            # no version counter under inference_mode: must not raise

@@ -182,7 +182,7 @@ def test_small_golden_fused_on_and_off(dev, monkeypatch):
         assert model.perceiver.fused_queries is on
         for cache in (True, False):
             model.cache_queries = cache
-            model.__dict__.pop("_query_cache", None)
+            model.clear_packed()
             before = calls["kernel"]
             with torch.inference_mode():
                 out = model(ins[0], ins[1], n_chunks=2)

@@ -36,5 +36,5 @@ for g in [int(v) for v in (sys.argv[1:] or ["4", "5", "6", "8"])]:
           "| hipMalloc count:", torch.cuda.memory_stats()["num_device_alloc"], flush=True)
     print(f"decode_chunks_per_call={g}: {elapsed:.2f} ms, "
           f"peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB", flush=True)
-    model.__dict__.pop("_query_cache", None)
+    model.clear_packed()
     torch.cuda.empty_cache()
