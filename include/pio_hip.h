@@ -268,8 +268,7 @@ int pio_ln_fold_enable(int on);
  * for problems with fewer than 192 tiles of 128x128: small batches), 128: 128x128 tile, 256: 256x256 tile,
  * 1: persistent 256x128 streaming kernel wherever it is legal, 2: persistent 256x256 four-wave kernel wherever
  * it is legal.  Returns the previous setting.  (Experiment kernels that measured level with these -- a two-workgroups-
- * per-CU fold producer, MFMA 32x32x16 variants of the fold GEMMs, two more fused self-attention kernels -- are not in
- * this library: tools/experiments, built by `make -C perceiverio_pytorch_amd/csrc experiments`.) */
+ * per-CU fold producer, two more fused self-attention kernels -- are not in this library: tools/experiments, built by `make -C perceiverio_pytorch_amd/csrc experiments`.) */
 int pio_gemm_kernel_override(int which);
 
 /* --- running on a part of the chip ----------------------------------------------------------------- */

@@ -581,9 +581,6 @@ int gemm_nt_launch(const pio_gemm_t &g, hipStream_t s) {
     const int err = gemm_params(g, &p);
     if (err) return err;
     const int forced = gemm_kernel_choice();
-#ifdef PIO_EXPERIMENTS
-    p.mf32 = forced == 4 ? 1 : 0;   // (experiments build: the MFMA 32x32x16 variants of the fold GEMMs)
-#endif
     const GemmRoute r = gemm_route(g, p, forced, cu_budget());
     if (r.err) return r.err;
     p.tiles_n = r.tiles_n;

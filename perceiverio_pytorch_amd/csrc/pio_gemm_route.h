@@ -18,7 +18,7 @@ struct GemmParams {
     int64_t dA1, dB1, dA2, dB2;  // element offsets of the pass-1 / pass-2 operands relative to A / B
     int npass;                   // 1..3 K sweeps accumulating into the same registers
     int staged_epi;              // (gemm_nt_wide, LayerNorm-fold producer) 1: LDS-staged, row-coalesced epilogue
-    int mf32;                    // (experiments build only) gemm_nt_wide fold GEMMs on the MFMA 32x32x16 variants
+    int reserved0;               // nothing reads it: keeps the kernel-argument offsets; goes with the next real change here
     int lo_n0;                   // (gemm_nt_wide only) B_lo exists for columns >= lo_n0 (multiple of 256); 0 = all
     int k_rev;                   // (gemm_nt_wide only) odd tiles of a workgroup sweep K backwards (see its walk)
     void *C, *C_lo;
@@ -96,7 +96,6 @@ inline int gemm_params(const pio_gemm_t &g, GemmParams *pp) {
     p.lo_n0 = g.B_lo ? g.b_lo_n0 : 0;
     p.k_rev = 0;        // (gemm_nt_wide: K walked forwards on every tile)
     p.staged_epi = 1;   // (gemm_nt_wide: the fold producer's staged epilogue)
-    p.mf32 = 0;
     p.ln_slots = g.ln_part ? (g.ln_slots > 0 ? g.ln_slots : g.K / 128) : 0;
     p.ln_inv_k = 1.0f / (float)g.K;
     p.slot_w = g.row_part ? (g.row_slot_w > 0 ? g.row_slot_w : 128) : 0;

@@ -79,7 +79,7 @@ int cu_budget_call(int v);  // per-call (thread-local) budget: v >= 0 sets it (0
 
 // ---- internal launchers (defined in the .hip files) ---------------------------------------------
 int gemm_nt_launch(const pio_gemm_t &g, hipStream_t s);
-int gemm_kernel_override(int which);  // 0 auto, 128, 256, 1 = streaming; returns the previous choice
+int gemm_kernel_override(int which);  // 0 auto, 64 / 128 / 256 tile, 1 = streaming, 2 = wide (experiments build: 3 = duo); returns the previous choice
 int layernorm_cast_launch(const pio_tensor3_t &x, const pio_layernorm_t *ln, void *y, void *y_lo, int c_pad,
                           int dtype, hipStream_t s);
 // LayerNorm over the concatenation [x1 | x2] of two sources (x2 may be one batch-invariant table, B == 1)
