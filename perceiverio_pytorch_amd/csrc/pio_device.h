@@ -16,6 +16,22 @@ __device__ __forceinline__ void static_for(F &&f) {  // compile-time loop: the i
     }
 }
 
+// The hi + lo pair of fp32 values in the operand type: h = round(x), l = round(x - h).  x: a float, or an ext_vector of
+// 2 / 4 floats with h, l the operand vectors of the same width.
+template <int DT, class FV, class OV>
+__device__ __forceinline__ void cast_pair(const FV x, OV &h, OV &l) {
+    if constexpr (std::is_same_v<FV, float>) {
+        h = Op<DT>::from_f32(x);
+        l = Op<DT>::from_f32(x - Op<DT>::to_f32(h));
+    } else {
+#pragma unroll
+        for (int e = 0; e < (int)(sizeof(FV) / sizeof(float)); ++e) {
+            h[e] = Op<DT>::from_f32(x[e]);
+            l[e] = Op<DT>::from_f32(x[e] - Op<DT>::to_f32(h[e]));
+        }
+    }
+}
+
 // One LDS-DMA piece: every lane moves 16 bytes from its own global address to the wave's 1-KiB slice at `lds`.
 __device__ __forceinline__ void lds_dma16(const void *src, void *lds) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,

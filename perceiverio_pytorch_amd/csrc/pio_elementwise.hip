@@ -1,8 +1,25 @@
 // Memory-bound helpers of the hot path (gfx950): weight packing, LayerNorm + cast to the MFMA operand
 // dtype, row softmax with masking.  All arithmetic is fp32; only the stored operand is 16-bit.
-#include "pio_internal.h"
+// Which LayerNorm / softmax kernel a call goes to is decided in pio_rows_route.h (pure, checked on the CPU by
+// tests/test_rows_route.py): the launchers here check their pointers, ask it, and launch what it names.  The (hi, lo)
+// pair is cast_pair (pio_device.h), except in the three kernels whose instruction streams it moves (DESIGN_LOG R5.4).
+#include "pio_device.h"
+#include "pio_rows_route.h"
 
 namespace pio {
+
+// Host-side dispatch of a launcher's run-time choices onto template arguments: f gets the value as an integral_constant
+// (as static_for's index does).  The dtype has been validated by then.
+template <class F>
+static inline void for_dtype(int dtype, F &&f) {
+    if (dtype == PIO_DT_F16) f(std::integral_constant<int, PIO_DT_F16>{});
+    else f(std::integral_constant<int, PIO_DT_BF16>{});
+}
+template <class F>
+static inline void for_bool(bool v, F &&f) {
+    if (v) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 // =====================================================================================================
 // pack_linear: W [out,in] fp32 -> packed [rows_p][k_pad] 16-bit (hi) + optional lo = W - float(hi).
@@ -25,10 +42,11 @@ __global__ void pack_linear_kernel(const float *__restrict__ w, const float *__r
         const int hc = cp / dcp, jc = cp % dcp;
         if (jc < dc) v = w[(int64_t)(hr * dr + jr) * ldw + (hc * dc + jc)];
     }
-    const typename Op<DT>::T h = Op<DT>::from_f32(v);
+    typename Op<DT>::T h, l;
+    cast_pair<DT>(v, h, l);
     const int64_t o = (int64_t)(dst_row0 + rp) * k_pad + cp;
     hi[o] = h;
-    if (lo) lo[o] = Op<DT>::from_f32(v - Op<DT>::to_f32(h));
+    if (lo) lo[o] = l;
     if (cp == 0 && dst_bias) dst_bias[dst_row0 + rp] = (rvalid && bias) ? bias[hr * dr + jr] : 0.f;
 }
 
@@ -132,11 +150,7 @@ __global__ __launch_bounds__(256) void layernorm_cast_kernel(const float *__rest
                 }
             }
             typename Op<DT>::V4 o, l;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                o[j] = Op<DT>::from_f32(f[j]);
-                l[j] = Op<DT>::from_f32(f[j] - Op<DT>::to_f32(o[j]));
-            }
+            cast_pair<DT>(f, o, l);
             *(typename Op<DT>::V4 *)(yr + i) = o;
             if (ylr) *(typename Op<DT>::V4 *)(ylr + i) = l;
         }
@@ -147,9 +161,10 @@ __global__ __launch_bounds__(256) void layernorm_cast_kernel(const float *__rest
                 v = xr[i];
                 if (NORM) v = (v - mean) * rstd * gamma[i] + beta[i];
             }
-            const OT h = Op<DT>::from_f32(v);
+            OT h, l;
+            cast_pair<DT>(v, h, l);
             yr[i] = h;
-            if (ylr) ylr[i] = Op<DT>::from_f32(v - Op<DT>::to_f32(h));
+            if (ylr) ylr[i] = l;
         }
     }
 }
@@ -213,7 +228,7 @@ __global__ __launch_bounds__(256) void layernorm_cast_reg_kernel(const float *__
                     for (int e = 0; e < 4; ++e) f[e] = (f[e] - mean) * rstd * g[e] + b[e];
                 }
             }
-            typename Op<DT>::V4 o, l;
+            typename Op<DT>::V4 o, l;  // (written out: cast_pair here moves the instruction stream, DESIGN_LOG R5.4)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 o[e] = Op<DT>::from_f32(f[e]);
@@ -255,7 +270,7 @@ __global__ __launch_bounds__(256) void rowstats_cast_kernel(const float *__restr
             dst[0] = sm;
             dst[1] = sq;
         }
-        typename Op<DT>::V4 o4, l4;
+        typename Op<DT>::V4 o4, l4;  // (written out: cast_pair here moves the instruction stream, DESIGN_LOG R5.4)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             o4[e] = Op<DT>::from_f32(v[e]);
@@ -273,19 +288,16 @@ int rowstats_cast_launch(const float *x, int64_t rows, int C, int slot_w, void *
     if (((uintptr_t)x & 15) || ((uintptr_t)y16 & 7) || ((uintptr_t)part & 7)) return PIO_E_ALIGN;
     if ((uintptr_t)y16_lo & 7) return PIO_E_ALIGN;
     ProfScope prof(PROF_LAYERNORM, 0.0, (double)rows * C * (y16_lo ? 8.0 : 6.0), s);
-    const unsigned blocks = (unsigned)((rows + 3) / 4);
-#define PIO_RS(DTV, SWV)                                                                                            \
-    hipLaunchKernelGGL((rowstats_cast_kernel<DTV, SWV>), dim3(blocks), dim3(256), 0, s, x, rows, C, (Op<DTV>::T *)y16, \
-                       (Op<DTV>::T *)y16_lo, part)
-    if (dtype == PIO_DT_F16) {
-        if (slot_w == 128) PIO_RS(PIO_DT_F16, 128);
-        else PIO_RS(PIO_DT_F16, 64);
-    } else if (dtype == PIO_DT_BF16) {
-        if (slot_w == 128) PIO_RS(PIO_DT_BF16, 128);
-        else PIO_RS(PIO_DT_BF16, 64);
-    } else
-        return PIO_E_ARG;
-#undef PIO_RS
+    if (!rows_dtype_ok(dtype)) return PIO_E_ARG;
+    for_dtype(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        typedef typename Op<DT>::T OT;
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(rows_blocks4(rows)), dim3(256), 0, s, x, rows, C, (OT *)y16, (OT *)y16_lo, part);
+        };
+        if (slot_w == 128) go(rowstats_cast_kernel<DT, 128>);
+        else go(rowstats_cast_kernel<DT, 64>);
+    });
     return launch_status();
 }
 
@@ -387,10 +399,7 @@ __global__ __launch_bounds__(256) void layernorm_cast_reg2_kernel(const float *_
                 }
             }
             OT2 o, l;
-            o[0] = Op<DT>::from_f32(f[0]);
-            o[1] = Op<DT>::from_f32(f[1]);
-            l[0] = Op<DT>::from_f32(f[0] - Op<DT>::to_f32(o[0]));
-            l[1] = Op<DT>::from_f32(f[1] - Op<DT>::to_f32(o[1]));
+            cast_pair<DT>(f, o, l);
             *(OT2 *)(yr + i) = o;
             if (ylr) *(OT2 *)(ylr + i) = l;
         }
@@ -457,10 +466,7 @@ __global__ __launch_bounds__(256) void layernorm_cast_cat2_kernel(const float *_
                 f[1] = (v[j][1] - mean) * rstd * g[1] + bb[1];
             }
             OT2 o, l;
-            o[0] = Op<DT>::from_f32(f[0]);
-            o[1] = Op<DT>::from_f32(f[1]);
-            l[0] = Op<DT>::from_f32(f[0] - Op<DT>::to_f32(o[0]));
-            l[1] = Op<DT>::from_f32(f[1] - Op<DT>::to_f32(o[1]));
+            cast_pair<DT>(f, o, l);
             *(OT2 *)(yr + i) = o;
             if (ylr) *(OT2 *)(ylr + i) = l;
         }
@@ -470,90 +476,52 @@ __global__ __launch_bounds__(256) void layernorm_cast_cat2_kernel(const float *_
 int layernorm_cast_cat_launch(const pio_tensor3_t &x1, const pio_tensor3_t &x2, const pio_layernorm_t &ln, void *y,
                               void *y_lo, int c_pad, int dtype, hipStream_t s) {
     if (!x1.data || !x2.data || !y || !ln.gamma || !ln.beta) return PIO_E_ARG;
-    const int C = x1.C + x2.C;
-    if (x1.B <= 0 || x1.T <= 0 || x1.C <= 0 || x2.C <= 0 || x2.T != x1.T || (x2.B != x1.B && x2.B != 1) || ln.c != C ||
-        c_pad < C || (c_pad % 8) || c_pad > 2048 || (x1.C & 1) || (x2.C & 1))
-        return PIO_E_SHAPE;
-    if (((uintptr_t)x1.data & 7) || ((uintptr_t)x2.data & 7) || (x1.stride_b & 1) || (x1.stride_t & 1) ||
-        (x2.stride_b & 1) || (x2.stride_t & 1) || ((uintptr_t)y & 3) || ((uintptr_t)y_lo & 3) ||
-        ((uintptr_t)ln.gamma & 7) || ((uintptr_t)ln.beta & 7))
-        return PIO_E_ALIGN;
+    const LnCatCall c = {x1.B, x1.T, x1.C, x2.B, x2.T, x2.C, ln.c, c_pad, x1.stride_b, x1.stride_t, x2.stride_b, x2.stride_t,
+                         dtype, rows_addr_bits(x1.data), rows_addr_bits(x2.data), rows_addr_bits(y), rows_addr_bits(y_lo),
+                         rows_addr_bits(ln.gamma), rows_addr_bits(ln.beta)};
+    if (const int err = ln_cat_check(c)) return err;
     const int64_t rows = (int64_t)x1.B * x1.T;
     const int64_t sb2 = x2.B == 1 ? 0 : x2.stride_b;
-    const unsigned blocks = (unsigned)((rows + 3) / 4);
     ProfScope prof(PROF_LAYERNORM, 0.0, (double)rows * (4.0 * x1.C + (y_lo ? 4.0 : 2.0) * c_pad) + 4.0 * x2.T * x2.C, s);
-    if (dtype == PIO_DT_F16)
-        hipLaunchKernelGGL((layernorm_cast_cat2_kernel<PIO_DT_F16>), dim3(blocks), dim3(256), 0, s, x1.data, x1.stride_b,
-                           x1.stride_t, x1.C, x2.data, sb2, x2.stride_t, x2.C, x1.T, rows, ln.gamma, ln.beta, ln.eps,
-                           (Op<PIO_DT_F16>::T *)y, (Op<PIO_DT_F16>::T *)y_lo, c_pad);
-    else if (dtype == PIO_DT_BF16)
-        hipLaunchKernelGGL((layernorm_cast_cat2_kernel<PIO_DT_BF16>), dim3(blocks), dim3(256), 0, s, x1.data, x1.stride_b,
-                           x1.stride_t, x1.C, x2.data, sb2, x2.stride_t, x2.C, x1.T, rows, ln.gamma, ln.beta, ln.eps,
-                           (Op<PIO_DT_BF16>::T *)y, (Op<PIO_DT_BF16>::T *)y_lo, c_pad);
-    else
-        return PIO_E_ARG;
+    for_dtype(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        typedef typename Op<DT>::T OT;
+        hipLaunchKernelGGL((layernorm_cast_cat2_kernel<DT>), dim3(rows_blocks4(rows)), dim3(256), 0, s, x1.data, x1.stride_b,
+                           x1.stride_t, x1.C, x2.data, sb2, x2.stride_t, x2.C, x1.T, rows, ln.gamma, ln.beta, ln.eps, (OT *)y,
+                           (OT *)y_lo, c_pad);
+    });
     return launch_status();
 }
 
 int layernorm_cast_launch(const pio_tensor3_t &x, const pio_layernorm_t *ln, void *y, void *y_lo, int c_pad,
                           int dtype, hipStream_t s) {
     if (!x.data || !y) return PIO_E_ARG;
-    if (x.B <= 0 || x.T <= 0 || x.C <= 0 || c_pad < x.C || (c_pad % 8)) return PIO_E_SHAPE;
     if (ln && (ln->c != x.C || !ln->gamma || !ln->beta)) return PIO_E_SHAPE;
-    const int64_t rows = (int64_t)x.B * x.T;
-    const bool vec = (x.C % 4 == 0) && (((uintptr_t)x.data & 15) == 0) && (x.stride_b % 4 == 0) &&
-                     (x.stride_t % 4 == 0) && (((uintptr_t)y & 7) == 0) && (((uintptr_t)y_lo & 7) == 0) &&
-                     (!ln || ((((uintptr_t)ln->gamma) & 15) == 0 && (((uintptr_t)ln->beta) & 15) == 0));
-    const unsigned blocks = (unsigned)((rows + 3) / 4);
-    ProfScope prof(PROF_LAYERNORM, 0.0, (double)rows * (4.0 * x.C + (y_lo ? 4.0 : 2.0) * c_pad), s);
     const float eps = ln ? ln->eps : 0.f;
     const float *g = ln ? ln->gamma : nullptr;
     const float *b = ln ? ln->beta : nullptr;
-#define PIO_LN_LAUNCH(DTV, VECV, NORMV)                                                                          \
-    hipLaunchKernelGGL((layernorm_cast_kernel<DTV, VECV, NORMV>), dim3(blocks), dim3(256), 0, s, x.data,          \
-                       x.stride_b, x.stride_t, x.T, rows, x.C, g, b, eps, (typename Op<DTV>::T *)y,                \
-                       (typename Op<DTV>::T *)y_lo, c_pad)
-    if (vec && c_pad <= 2048 && (dtype == PIO_DT_F16 || dtype == PIO_DT_BF16)) {
-    const bool even = x.B == 1 || x.stride_b == (int64_t)x.T * x.stride_t;
-    const int t_arg = even ? 0 : x.T;
-#define PIO_LNR_LAUNCH2(DTV, NORMV, NVV)                                                                               \
-    hipLaunchKernelGGL((layernorm_cast_reg_kernel<DTV, NORMV, NVV>), dim3(blocks), dim3(256), 0, s, x.data, x.stride_b, \
-                       x.stride_t, t_arg, rows, x.C, g, b, eps, (typename Op<DTV>::T *)y,                               \
-                       (typename Op<DTV>::T *)y_lo, c_pad)
-#define PIO_LNR_LAUNCH(DTV, NORMV)                              \
-    do {                                                        \
-        if (c_pad <= 1024) PIO_LNR_LAUNCH2(DTV, NORMV, 4);      \
-        else PIO_LNR_LAUNCH2(DTV, NORMV, 8);                    \
-    } while (0)
-        if (dtype == PIO_DT_F16) { if (ln) PIO_LNR_LAUNCH(PIO_DT_F16, true); else PIO_LNR_LAUNCH(PIO_DT_F16, false); }
-        else                     { if (ln) PIO_LNR_LAUNCH(PIO_DT_BF16, true); else PIO_LNR_LAUNCH(PIO_DT_BF16, false); }
-#undef PIO_LNR_LAUNCH2
-#undef PIO_LNR_LAUNCH
-        return launch_status();
-    }
-    const bool vec2 = (x.C % 2 == 0) && (((uintptr_t)x.data & 7) == 0) && (x.stride_b % 2 == 0) &&
-                      (x.stride_t % 2 == 0) && (((uintptr_t)y & 3) == 0) && (((uintptr_t)y_lo & 3) == 0) &&
-                      (!ln || ((((uintptr_t)ln->gamma) & 7) == 0 && (((uintptr_t)ln->beta) & 7) == 0));
-    if (vec2 && c_pad <= 2048 && (dtype == PIO_DT_F16 || dtype == PIO_DT_BF16)) {
-#define PIO_LNR2_LAUNCH(DTV, NORMV)                                                                               \
-    hipLaunchKernelGGL((layernorm_cast_reg2_kernel<DTV, NORMV>), dim3(blocks), dim3(256), 0, s, x.data, x.stride_b, \
-                       x.stride_t, x.T, rows, x.C, g, b, eps, (typename Op<DTV>::T *)y,                            \
-                       (typename Op<DTV>::T *)y_lo, c_pad)
-        if (dtype == PIO_DT_F16) { if (ln) PIO_LNR2_LAUNCH(PIO_DT_F16, true); else PIO_LNR2_LAUNCH(PIO_DT_F16, false); }
-        else                     { if (ln) PIO_LNR2_LAUNCH(PIO_DT_BF16, true); else PIO_LNR2_LAUNCH(PIO_DT_BF16, false); }
-#undef PIO_LNR2_LAUNCH
-        return launch_status();
-    }
-    if (dtype == PIO_DT_F16) {
-        if (ln) { if (vec) PIO_LN_LAUNCH(PIO_DT_F16, true, true); else PIO_LN_LAUNCH(PIO_DT_F16, false, true); }
-        else    { if (vec) PIO_LN_LAUNCH(PIO_DT_F16, true, false); else PIO_LN_LAUNCH(PIO_DT_F16, false, false); }
-    } else if (dtype == PIO_DT_BF16) {
-        if (ln) { if (vec) PIO_LN_LAUNCH(PIO_DT_BF16, true, true); else PIO_LN_LAUNCH(PIO_DT_BF16, false, true); }
-        else    { if (vec) PIO_LN_LAUNCH(PIO_DT_BF16, true, false); else PIO_LN_LAUNCH(PIO_DT_BF16, false, false); }
-    } else {
-        return PIO_E_ARG;
-    }
-#undef PIO_LN_LAUNCH
+    const LnCall c = {x.B, x.T, x.C, c_pad, x.stride_b, x.stride_t, ln != nullptr, dtype, rows_addr_bits(x.data),
+                      rows_addr_bits(y), rows_addr_bits(y_lo), rows_addr_bits(g), rows_addr_bits(b)};
+    const LnRoute r = ln_route(c);
+    if (r.err) return r.err;
+    const int64_t rows = (int64_t)x.B * x.T;
+    ProfScope prof(PROF_LAYERNORM, 0.0, (double)rows * (4.0 * x.C + (y_lo ? 4.0 : 2.0) * c_pad), s);
+    for_dtype(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        typedef typename Op<DT>::T OT;
+        auto go = [&](auto kernel, int t_arg) {  // (every LayerNorm kernel takes the same arguments)
+            hipLaunchKernelGGL(kernel, dim3(r.blocks), dim3(256), 0, s, x.data, x.stride_b, x.stride_t, t_arg, rows, x.C, g, b,
+                               eps, (OT *)y, (OT *)y_lo, c_pad);
+        };
+        for_bool(ln != nullptr, [&](auto norm) {
+            constexpr bool NORM = decltype(norm)::value;
+            if (r.kind == LnKind::REG4 && r.nv == 4) go(layernorm_cast_reg_kernel<DT, NORM, 4>, r.even_rows ? 0 : x.T);
+            else if (r.kind == LnKind::REG4) go(layernorm_cast_reg_kernel<DT, NORM, 8>, r.even_rows ? 0 : x.T);
+            else if (r.kind == LnKind::REG2) go(layernorm_cast_reg2_kernel<DT, NORM>, x.T);
+            else if (r.kind == LnKind::GEN_VEC) go(layernorm_cast_kernel<DT, true, NORM>, x.T);
+            else go(layernorm_cast_kernel<DT, false, NORM>, x.T);
+        });
+    });
     return launch_status();
 }
 
@@ -635,9 +603,10 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const SoftmaxParams p
     for (int j = t0; j < (int)p.ldp; j += tstep) {
         float v = 0.f;
         if (j < p.Tk && any && valid(j)) v = __expf(score(j) - m) * inv;
-        const OT h = Op<DT>::from_f32(v);
+        OT h, l;
+        cast_pair<DT>(v, h, l);
         pr[j] = h;
-        if (plr) plr[j] = Op<DT>::from_f32(v - Op<DT>::to_f32(h));
+        if (plr) plr[j] = l;
         if (po && j < p.Tk) po[j] = any ? v : uni;  // reference returns the un-wiped (uniform) matrix
     }
 }
@@ -727,7 +696,7 @@ __global__ __launch_bounds__(256) void softmax_rows_reg_kernel(const SoftmaxPara
     for (int j = 0; j < NV4; ++j) {
         const int k = (j * 64 + lane) * 4;
         if (k < (int)p.ldp) {     // ldp % 4 == 0; columns [Tk, ldp) get exact zeros
-            OV4 h, l;
+            OV4 h, l;  // (written out: cast_pair here moves the instruction stream, DESIGN_LOG R5.4)
             f32x4 x;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -749,46 +718,28 @@ int softmax_rows_launch(const float *S, int64_t lds, void *P, void *P_lo, int64_
                         float scale, const uint8_t *kv_mask, const uint8_t *q_mask, const uint8_t *full_mask,
                         const float *bias, int dtype, float *probs_out, hipStream_t s) {
     if (!S || !P) return PIO_E_ARG;
-    if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || ldp < Tk || lds < Tk) return PIO_E_SHAPE;
-    if (dtype != PIO_DT_F16 && dtype != PIO_DT_BF16) return PIO_E_ARG;
+    const SoftmaxCall c = {B, H, Tq, Tk, lds, ldp, dtype, P_lo != nullptr, bias != nullptr, probs_out != nullptr,
+                           kv_mask != nullptr, q_mask != nullptr, full_mask != nullptr, rows_addr_bits(S), rows_addr_bits(P),
+                           rows_addr_bits(P_lo), rows_addr_bits(bias), rows_addr_bits(probs_out), rows_addr_bits(kv_mask),
+                           rows_addr_bits(full_mask)};
+    const SoftmaxRoute r = softmax_route(c);
+    if (r.err) return r.err;
     SoftmaxParams p{S, lds, P, P_lo, ldp, B, H, Tq, Tk, scale, kv_mask, q_mask, full_mask, bias, probs_out};
     const int64_t rows = (int64_t)B * H * Tq;
     ProfScope prof(PROF_SOFTMAX, 0.0, (double)rows * (4.0 * Tk + (P_lo ? 4.0 : 2.0) * ldp), s);
-    const bool plain = !kv_mask && !q_mask && !full_mask && !bias && !P_lo && !probs_out;
-    const bool vec4 = (Tk % 4 == 0) && (ldp % 4 == 0) && (lds % 4 == 0) && (((uintptr_t)S & 15) == 0) &&
-                      (((uintptr_t)P & 7) == 0) && (((uintptr_t)P_lo & 7) == 0) && (((uintptr_t)bias & 15) == 0) &&
-                      (((uintptr_t)probs_out & 15) == 0) && (((uintptr_t)kv_mask & 3) == 0) &&
-                      (((uintptr_t)full_mask & 3) == 0);
-    if (vec4 && ldp <= 16 * 256) {
-        const unsigned blocks = (unsigned)((rows + 3) / 4);
-#define PIO_SMR2(DTV, NVV)                                                                                         \
-    do {                                                                                                           \
-        if (plain) hipLaunchKernelGGL((softmax_rows_reg_kernel<DTV, NVV, true>), dim3(blocks), dim3(256), 0, s, p); \
-        else hipLaunchKernelGGL((softmax_rows_reg_kernel<DTV, NVV, false>), dim3(blocks), dim3(256), 0, s, p);      \
-    } while (0)
-#define PIO_SMR(NVV)                                             \
-    do {                                                         \
-        if (dtype == PIO_DT_F16) PIO_SMR2(PIO_DT_F16, NVV);      \
-        else PIO_SMR2(PIO_DT_BF16, NVV);                         \
-    } while (0)
-        if (ldp <= 2 * 256) PIO_SMR(2);
-        else if (ldp <= 8 * 256) PIO_SMR(8);
-        else PIO_SMR(16);
-#undef PIO_SMR
-#undef PIO_SMR2
-        return launch_status();
-    }
-    if (Tk <= 2048) {
-        const unsigned blocks = (unsigned)((rows + 3) / 4);
-        if (dtype == PIO_DT_F16) hipLaunchKernelGGL((softmax_rows_kernel<PIO_DT_F16, 1>), dim3(blocks), dim3(256), 0, s, p);
-        else if (dtype == PIO_DT_BF16) hipLaunchKernelGGL((softmax_rows_kernel<PIO_DT_BF16, 1>), dim3(blocks), dim3(256), 0, s, p);
-        else return PIO_E_ARG;
-    } else {
-        const unsigned blocks = (unsigned)rows;
-        if (dtype == PIO_DT_F16) hipLaunchKernelGGL((softmax_rows_kernel<PIO_DT_F16, 4>), dim3(blocks), dim3(256), 0, s, p);
-        else if (dtype == PIO_DT_BF16) hipLaunchKernelGGL((softmax_rows_kernel<PIO_DT_BF16, 4>), dim3(blocks), dim3(256), 0, s, p);
-        else return PIO_E_ARG;
-    }
+    for_dtype(dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(r.blocks), dim3(256), 0, s, p); };
+        if (r.kind == SoftmaxKind::GEN_W1) go(softmax_rows_kernel<DT, 1>);
+        else if (r.kind == SoftmaxKind::GEN_W4) go(softmax_rows_kernel<DT, 4>);
+        else
+            for_bool(r.plain, [&](auto plain) {
+                constexpr bool PLAIN = decltype(plain)::value;
+                if (r.nv4 == 2) go(softmax_rows_reg_kernel<DT, 2, PLAIN>);
+                else if (r.nv4 == 8) go(softmax_rows_reg_kernel<DT, 8, PLAIN>);
+                else go(softmax_rows_reg_kernel<DT, 16, PLAIN>);
+            });
+    });
     return launch_status();
 }
 

@@ -5,8 +5,8 @@ Numpy only; shared by tests/test_primitive_cases_host.py (CPU: the references ag
 coverage of the tables) and tests/test_primitives_gpu.py (MI355X: the kernels against the references).
 
 The references restate the DEFINITIONS of include/pio_hip.h in float64, not the kernels.  Each case names the launcher
-branch it is meant to reach; the `*_variant_of` functions restate the launchers' predicates so that the host test can
-check that every branch has a case.
+branch it is meant to reach; tests/test_rows_route.py asks the launchers' own routing header (csrc/pio_rows_route.h) that
+it does.
 """
 import numpy as np
 
@@ -167,18 +167,6 @@ SM_MASK_BYTE_CASES = ("tk512", "tk13")     # one register-kernel shape, one gene
 MASK_TRUE_BYTES = (1, 2, 0x80, 0xFF)
 
 
-def softmax_variant_of(case, form):
-    """Restates softmax_rows_launch's choice of kernel (csrc/pio_elementwise.hip) for buffers that are 16-byte aligned
-    apart from the case's `s_off`.  DOCUMENTATION ONLY: nothing ties it to the launcher, it goes stale when the
-    launcher changes."""
-    Tk, lds, ldp = case["Tk"], case["lds"], case["ldp"]
-    vec4 = Tk % 4 == 0 and ldp % 4 == 0 and lds % 4 == 0 and case["s_off"] % 4 == 0
-    if vec4 and ldp <= 16 * 256:
-        nv = 2 if ldp <= 2 * 256 else 8 if ldp <= 8 * 256 else 16
-        return f"reg_nv{nv}_{'plain' if form == 'plain' else 'masked'}"
-    return "gen_w1" if Tk <= 2048 else "gen_w4"
-
-
 # rows planted in every case (sample 0; in the masked form sample 1 has every key masked by kv_mask)
 SM_ROW_QMASKED, SM_ROW_FULL_EMPTY, SM_ROW_ONE_KEY, SM_ROW_LARGE, SM_ROW_CONST = 1, 2, 3, 4, 5
 
@@ -266,20 +254,6 @@ def ln_strides(case, layout):
         return 0, st, 1
     sb = LN_T * st + (LN_GAP if layout == "uneven_batch" else 0)
     return sb, st, LN_B
-
-
-def layernorm_variant_of(case, layout="contiguous"):
-    """Restates layernorm_cast_launch's choice of kernel for y / gamma / beta 16-byte aligned and x aligned apart from
-    the case's `x_off`.  DOCUMENTATION ONLY: nothing ties it to the launcher, it goes stale when the launcher changes."""
-    C, cp = case["C"], case["c_pad"]
-    sb, st, _ = ln_strides(case, layout)
-    vec = C % 4 == 0 and case["x_off"] % 4 == 0 and sb % 4 == 0 and st % 4 == 0
-    if vec and cp <= 2048:
-        return "reg_nv4" if cp <= 1024 else "reg_nv8"
-    vec2 = C % 2 == 0 and case["x_off"] % 2 == 0 and sb % 2 == 0 and st % 2 == 0
-    if vec2 and cp <= 2048:
-        return "reg2"
-    return "gen_vec" if vec else "gen_scalar"
 
 
 LN_ROW_CONST, LN_ROW_MEAN1E3, LN_ROW_OUTLIER, LN_ROW_ZERO = 0, 1, 2, 3     # rows t of sample 0

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import primitive_cases as PC  # noqa: E402
+import rows_route_driver as RR  # noqa: E402
 
 TOL = 1e-12
 
@@ -118,10 +119,10 @@ def test_ref_bn_relu_maxpool_matches_torch(pads):
 
 
 def test_every_launcher_branch_has_a_case():
-    seen = set()
+    seen, variant = set(), RR.softmax_variants()                    # (the launcher's routing header, through a g++ driver)
     for c in PC.SOFTMAX_CASES:
         for form in PC.SM_FORMS:
-            v = PC.softmax_variant_of(c, form)
+            v = variant[c["id"], form]
             assert v.startswith(c["branch"]), (c["id"], v)          # the case reaches the branch it names
             seen.add(v)
     want = {f"reg_nv{n}_{f}" for n in (2, 8, 16) for f in ("plain", "masked")} | {"gen_w1", "gen_w4"}
@@ -133,10 +134,10 @@ def test_every_launcher_branch_has_a_case():
     for name in PC.SM_MASK_BYTE_CASES:
         assert any(c["id"] == name for c in PC.SOFTMAX_CASES)
 
-    seen = set()
+    seen, variant = set(), RR.ln_variants()
     for c in PC.LAYERNORM_CASES:
         for layout in PC.LN_LAYOUTS:
-            v = PC.layernorm_variant_of(c, layout)
+            v = variant[c["id"], layout]
             assert v == c["branch"], (c["id"], layout, v)           # no layout moves a case to another kernel
             seen.add(v)
     assert seen == set(PC.LN_BRANCHES)

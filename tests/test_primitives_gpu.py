@@ -149,7 +149,7 @@ def test_softmax_rows_branch(dev, case, form):
     ref = PC.ref_softmax_rows(d["S"], d["scale"], d["kv_mask"], d["q_mask"], d["full_mask"], d["bias"])
     ok = np.broadcast_to(PC.softmax_valid(ref.shape, d["kv_mask"], d["q_mask"], d["full_mask"]), ref.shape)
     for dt in PC.DTYPES:
-        what = f"softmax {case['id']} {form} {dt} [{PC.softmax_variant_of(case, form)}]"
+        what = f"softmax {case['id']} {form} {dt} [{case['branch']}]"
         P, Pl = _run_softmax(dev, case, d, dt, with_lo=(form == "full"))
         got = _np(P).reshape(B, H, Tq, ldp)
         assert np.isfinite(got).all(), what
@@ -188,7 +188,7 @@ def test_softmax_rows_mask_bytes(dev, name, dt):
             P1, L1 = _run_softmax(dev, case, e, dt, True)
             if not (torch.equal(_bits(P1), P0) and torch.equal(_bits(L1), L0)):
                 bad.append(f"{which}=0x{v:02X}")
-    print(f"softmax mask bytes {name} {dt} [{PC.softmax_variant_of(case, 'full')}]: differing from the 0/1 run: {bad or 'none'}")
+    print(f"softmax mask bytes {name} {dt} [{case['branch']}]: differing from the 0/1 run: {bad or 'none'}")
     assert not bad, f"{name} {dt}: results differ from the 0 / 1 masks for {bad}"
 
 
@@ -231,7 +231,7 @@ def test_layernorm_cast_branch(dev, case, layout):
     for norm in (True, False):
         for dt in PC.DTYPES:
             for with_lo in (True, False):
-                what = f"layernorm {case['id']} {layout} ln={int(norm)} {dt} lo={int(with_lo)} [{PC.layernorm_variant_of(case, layout)}]"
+                what = f"layernorm {case['id']} {layout} ln={int(norm)} {dt} lo={int(with_lo)} [{case['branch']}]"
                 y = Guarded(dev, (B * T, cp), TDT[dt])
                 yl = Guarded(dev, (B * T, cp), TDT[dt]) if with_lo else None
                 L.check(lib.pio_layernorm_cast(C.byref(t3), C.byref(ln) if norm else None, y.ptr, yl.ptr if yl else None,
