@@ -556,6 +556,14 @@ int pio_flow_to_image(const float *flow, int64_t sn, int64_t sy, int64_t sx, int
  * added after the activation (row m of the flattened problem reads
  * R + (m / r_rows_per_batch)*r_stride_b + (m % r_rows_per_batch)*ldr when r_rows_per_batch > 0);
  * output fp32 (out_f32=1) or operand dtype with zero fill of columns [N, n_store).
+ * The activation, y = gelu(x) of the fp32 pre-activation x = alpha acc + bias (tests/test_gemm_act_gpu.py holds every
+ * kernel that applies it to this, over the whole domain):
+ *   |x| <= 6:   within 1.1e-6 of x Phi(x) before the rounding of the output type (the fp32 model itself: 2.6e-7);
+ *   |x| >  6:   Phi(-|x|) is frozen at Phi(-6) = 9.87e-10: y = x - x Phi(-6) for x > 0 and y = x Phi(-6) for x < 0 --
+ *               not -> 0 --, an absolute error that grows as about 1e-9 |x|;
+ *   the sign of y is the sign of x, gelu(+-0) = 0 and |y| <= |x| everywhere;
+ *   NaN gives NaN; -inf gives -inf and +inf gives NaN (never a finite value: the range guard of the folded stacks
+ *   relies on a non-finite activation staying visible).  gemm_nt_skinny applies no activation: act = 1 routes past it.
  * What a call touches (tests/test_gemm_addr_gpu.py holds every kernel to it, bit for bit, on NaN-surrounded buffers):
  *   read:    A / A_lo rows < M and B / B_lo rows < N of every (zb, zh) slice, columns < K -- never the pitch bytes
  *            [K, lda) / [K, ldb), never the gap between two slices, never rows of B_lo below b_lo_n0; bias entries < N

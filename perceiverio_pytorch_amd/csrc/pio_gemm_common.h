@@ -12,6 +12,11 @@ namespace pio {
 // fp32 over [-10, 10]: 2.6e-7 absolute (the A&S 7.1.26 form it replaces -- v_rcp + v_exp + 5-term polynomial, ~20
 // slots with the hazard padding of two dependent transcendentals: 4.6e-7); the epilogues that call it are bound by the
 // number of instructions a single wave can issue, not by their memory traffic.  tools/gelu_fit.py makes the table.
+// Outside the fit (the contract of pio_gemm_t.act in include/pio_hip.h; tests/test_gemm_act_gpu.py holds every epilogue
+// to it): for |x| > 6 E stays at Phi(-6) = 9.87e-10, so the negative side returns x Phi(-6) rather than -> 0 and the
+// positive side x - x Phi(-6): an absolute error of about 1e-9 |x|.  NaN -> NaN; -inf -> -inf; +inf -> NaN (the final FMA
+// is -inf + inf) -- non-finite in, non-finite out, which is all the folded stacks' range guard needs: no instruction is
+// spent on turning that NaN into +inf.
 __device__ __forceinline__ float gelu_erf(float x) {
     const float a = fminf(fabsf(x), 6.0f);
     float q = 3.152013050566893e-06f;
