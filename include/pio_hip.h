@@ -463,6 +463,33 @@ typedef struct pio_head_segment_t {
 int pio_project_heads(const pio_head_segment_t *segs, int32_t nseg, const float *x, int64_t x_sb, int64_t ldx,
                       int32_t B, int32_t Q, int32_t K, void *stream);
 
+/* The vocabulary head of the language model with its selection as ONE launch: rows r = b*Q + q of x [B, Q, K] fp32 (row pitch
+ * ldx, sample stride x_sb; x_sb is not read when B == 1) against w [V, K] fp32 (row pitch ldw; the tied embedding), V <= 1024:
+ *   logit[r, j]   = bias[j] + sum_k w[j*ldw + k] * x[b*x_sb + q*ldx + k]                    (bias may be NULL)
+ *   lse[r]        = m + log(sum_j exp(logit[r, j] - m)),  m = max_j logit[r, j]
+ *   ids[r*k + t]  = the t-th id of row r in the order: logit descending, the lower id first among equal logits (-0.0 and +0.0
+ *                   are equal);  logprob[r*k + t] = fadd_rn(logit[r, ids[r*k + t]], -lse[r])
+ * Outputs, each optional (NULL): ids int32 [B*Q, k], logprob fp32 [B*Q, k], lse fp32 [B*Q], logits fp32 [B*Q, V] with row
+ * pitch ldl.  x is multiplied as fp32 (nothing is rounded to 16 bits) and only what is asked for is written.
+ * Selection alone: x == w == NULL (bias NULL, K not read) -- logits is then the INPUT, [B*Q, V] with row pitch ldl, and ids,
+ * logprob and lse are what the computing mode returns for those logits, bit for bit.
+ * Summation order (part of the definition): with lane l = (k / 4) % 64 and sweep i = k / 256,
+ *   p_l   = +0;  for i ascending, for k = 4*(l + 64*i) .. + 3 ascending (k < K):  p_l = fmaf(w[j, k], x[k], p_l)
+ *   s     = pairwise tree over the 64 p_l: offsets 32, 16, 8, 4, 2, 1,  p_l = fadd_rn(p_l, p_(l xor offset))
+ *   logit = bias ? fadd_rn(s, bias[j]) : s
+ *   m     = fmaxf over j;  e_l = +0, for j = l, l + 64, .. ascending: e_l = fadd_rn(e_l, expf(fsub_rn(logit_j, m)));  S = the
+ *           same tree over the 64 e_l;  lse = fadd_rn(m, logf(S))
+ * so the bits of a row's results depend only on that row of x, w, bias, V, K and k -- not on B, Q, the strides or the
+ * position of the row in the launch; there are no atomics.  A row holding a NaN logit has unspecified ids, all in [0, V),
+ * and unspecified values; other rows are not affected.  No workspace, no device allocation, no synchronisation.
+ * PIO_E_ARG: exactly one of x / w NULL, selection alone without logits or with a bias, no output pointer at all;
+ * PIO_E_SHAPE: B or Q < 1, B*Q > 2^31 - 1, V outside [1, 1024], k outside [1, min(8, V)], logits given with ldl < V, and
+ * when computing K outside [4, 1024] or not a multiple of 4, ldx < K, ldw < K; PIO_E_ALIGN: x or w not 16-byte aligned, ldx,
+ * ldw or (B > 1) x_sb not a multiple of 4, any other pointer not 4-byte aligned.  A refused call launches nothing. */
+int pio_vocab_topk(const float *x, int64_t x_sb, int64_t ldx, const float *w, int64_t ldw, const float *bias, int32_t B,
+                   int32_t Q, int32_t V, int32_t K, int32_t k, int32_t *ids, float *logprob, float *lse, float *logits,
+                   int64_t ldl, void *stream);
+
 /* The language front end (io_processors.py EmbeddingPreprocessor: embed(ids) + learned position embedding) as ONE launch.
  * ids [B, T] int32 (id_bytes 4) or int64 (id_bytes 8), t contiguous, sample stride ids_sb elements; table [V, C] fp32 (row
  * pitch ldt); pos [T, C] fp32 (row pitch ldp); y [B, T, C] fp32 (row pitch ldy, sample stride y_sb); tokens: optional

@@ -172,6 +172,7 @@ SIGNATURES = {
     "pio_assemble_tokens": (C.c_int, [P(TokenSegment), _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "pio_build_queries": (C.c_int, [P(QuerySegment), _i32, _vp, _i64, _i32, _i32, _vp]),
     "pio_project_heads": (C.c_int, [P(HeadSegment), _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "pio_vocab_topk": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "pio_embed_tokens": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i32,
                                    _i32, _i32, _vp]),
     "pio_flow_blend_tiles": (C.c_int, [P(FlowBlend), _vp, _i64, _i64, _i64, _vp]),

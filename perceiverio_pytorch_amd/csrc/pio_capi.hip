@@ -218,6 +218,12 @@ int pio_project_heads(const pio_head_segment_t *segs, int32_t nseg, const float 
     return project_heads_launch(segs, nseg, x, x_sb, ldx, B, Q, K, (hipStream_t)stream);
 }
 
+int pio_vocab_topk(const float *x, int64_t x_sb, int64_t ldx, const float *w, int64_t ldw, const float *bias, int32_t B,
+                   int32_t Q, int32_t V, int32_t K, int32_t k, int32_t *ids, float *logprob, float *lse, float *logits,
+                   int64_t ldl, void *stream) {
+    return vocab_topk_launch(x, x_sb, ldx, w, ldw, bias, B, Q, V, K, k, ids, logprob, lse, logits, ldl, (hipStream_t)stream);
+}
+
 int pio_embed_tokens(const void *ids, int32_t id_bytes, int64_t ids_sb, const float *table, int64_t ldt, int32_t V,
                      const float *pos, int64_t ldp, float *y, int64_t y_sb, int64_t ldy, float *tokens, int64_t tok_sb,
                      int64_t ldtok, int32_t *bad_ids, int32_t B, int32_t T, int32_t C, void *stream) {

@@ -153,6 +153,11 @@ int build_queries_launch(const pio_query_segment_t *segs, int nseg, float *y, in
 // output heads: up to 4 row segments of the decoder output, each through its own narrow fp32 linear head, written in place
 int project_heads_launch(const pio_head_segment_t *segs, int nseg, const float *x, int64_t x_sb, int64_t ldx, int B, int Q,
                          int K, hipStream_t s);
+// vocabulary head: fp32 logits of decoder rows against a [V <= 1024, K] embedding, their log-sum-exp and top-k (or the
+// selection alone on given logits: x == w == NULL)
+int vocab_topk_launch(const float *x, int64_t x_sb, int64_t ldx, const float *w, int64_t ldw, const float *bias, int B, int Q,
+                      int V, int K, int k, int32_t *ids, float *logprob, float *lse, float *logits, int64_t ldl,
+                      hipStream_t s);
 int pack_linear_launch(const float *w, const float *bias, int out, int in, int64_t ldw, int row_heads,
                        int col_heads, void *dst_hi, void *dst_lo, float *dst_bias, int dst_row0, int k_pad,
                        int dtype, hipStream_t s);

@@ -413,6 +413,65 @@ def project_heads(io, outputs, query_sizes, into=None):
     return result
 
 
+# Rows (B x P) up to which pio_vocab_topk multiplies itself; above it runtime.hip_linear makes the logits and the kernel's
+# second mode selects.  A measurement (profiles/language_predict.json, tools/prep_bench.py --language-predict): at 262 x 768
+# the kernel's own fp32 multiply lost to cast + GEMM + selection at EVERY row count from 1 to 204 800 (55 against 48 us at one
+# row, where eight waves stream the whole embedding; 5.2 against 1.6 ms at 204 800), so the shipped routing is the selection
+# alone: 0.  The computing mode stays in the library and in the tests (the C-ABI, and the model with this raised).
+VOCAB_FUSED_MAX_ROWS = 0
+
+
+def vocab_plan(post, x, k):
+    """What vocab_topk does with a decoder output x [B, P, K] and k: "fused" (the kernel multiplies), "select" (hip_linear, then
+    the kernel's selection alone) or None (decline: the chain).  Declines the switch off, the torch backend, CPU tensors,
+    anything but fp32 x / embedding / bias on one device, x that is not 3-D with unit channel stride and at least one row,
+    V > 1024, k outside [1, min(8, V)] and an active range probe (the chain keeps its "cast" record of x)."""
+    w, bias = post._embedding.weight, post.bias
+    if not gate(post.fused_predict, x) or LP.range_active() or w.dtype != torch.float32 or bias.dtype != torch.float32:
+        return None
+    if x.dim() != 3 or w.dim() != 2 or x.shape[2] != w.shape[1] or x.shape[0] < 1 or x.shape[1] < 1 or x.stride(2) != 1:
+        return None
+    v, kk = w.shape
+    if w.device != x.device or bias.device != x.device or tuple(bias.shape) != (v,):
+        return None
+    if not 1 <= v <= 1024 or not 1 <= k <= min(8, v) or x.shape[0] * x.shape[1] >= 2 ** 31:
+        return None
+    fused = 4 <= kk <= 1024 and kk % 4 == 0 and x.shape[0] * x.shape[1] <= VOCAB_FUSED_MAX_ROWS
+    return "fused" if fused else "select"
+
+
+def vocab_topk(post, x, k, return_logits=False):
+    """(ids int64 [B, P, k], logprobs fp32 [B, P, k], logits fp32 [B, P, V] or None) of a decoder output x [B, P, K] behind an
+    EmbeddingPostprocessor from pio_vocab_topk, or None when it declines (vocab_plan).  "fused": ONE launch multiplies the
+    unrounded fp32 rows against the fp32 embedding and selects; "select": the postprocessor's own hip_linear (the chain's
+    logits, bit for bit), then one launch for log-sum-exp and top-k.  Equal logits put the lower id first."""
+    mode = vocab_plan(post, x, k)
+    if mode is None:
+        return None
+    w, bias = post._embedding.weight, post.bias
+    (b, p, _), v, dev = x.shape, w.shape[0], x.device
+    ids = torch.empty((b, p, k), dtype=torch.int32, device=dev)
+    logprob = torch.empty((b, p, k), dtype=torch.float32, device=dev)
+    if mode == "fused":
+        xr = rows(x, min_stride=True, stride4=True, aligned=True)
+        if b > 1 and xr.stride(0) % 4:
+            xr = xr.detach().contiguous()
+        wr = rows(w, min_stride=True, stride4=True, aligned=True)
+        br = bias.detach().contiguous()
+        logits = torch.empty((b, p, v), dtype=torch.float32, device=dev) if return_logits else None
+        R.call(dev, "pio_vocab_topk", xr.data_ptr(), xr.stride(0) if b > 1 else 0, xr.stride(1) if p > 1 else xr.shape[2],
+               wr.data_ptr(), wr.stride(0) if v > 1 else wr.shape[1], br.data_ptr(), b, p, v, xr.shape[2], k, ids.data_ptr(),
+               logprob.data_ptr(), None, None if logits is None else logits.data_ptr(), v)
+    else:
+        logits = post(x).contiguous()
+        R.call(dev, "pio_vocab_topk", None, 0, 0, None, 0, None, b, p, v, 0, k, ids.data_ptr(), logprob.data_ptr(), None,
+               logits.data_ptr(), v)
+        if not return_logits:
+            logits = None
+    logprob = R.forward_only(logprob, x, w, bias)
+    return ids.long(), logprob, (None if logits is None else R.forward_only(logits, x, w, bias))
+
+
 def _covers(corners, length, size):
     """True when the intervals [c, c + length) of the corners cover [0, size)."""
     pos = 0

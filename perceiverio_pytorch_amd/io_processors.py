@@ -424,6 +424,28 @@ class EmbeddingPostprocessor(PackedOwner):
         return (inputs.reshape(-1, self._d_model) @ self._embedding.weight.T + self.bias).reshape(b, t,
                                                                                                  self._vocab_size)
 
+    # predict(): logits, log-sum-exp and top-k of the rows from pio_vocab_topk (fused_io.vocab_topk: fp32 products of the
+    # unrounded rows up to fused_io.VOCAB_FUSED_MAX_ROWS rows, hip_linear + the kernel's selection above) for CUDA fp32 rows
+    # under the hip backend, V <= 1024, k <= 8 and no active range probe.  False (and whatever vocab_topk declines): the chain
+    # -- forward, log_softmax, topk.
+    fused_predict = True
+
+    def _vocab_topk(self, rows, k, return_logits):
+        from . import fused_io as FIO
+        return FIO.vocab_topk(self, rows, k, return_logits)
+
+    def predict(self, rows: torch.Tensor, k: int = 5, return_logits: bool = False):
+        """(ids int64 [B, P, k], logprobs fp32 [B, P, k], logits [B, P, V] or None) of decoder rows [B, P, d_model]: the k
+        most probable tokens of every row, most probable first, and their log-probabilities."""
+        if not 1 <= k <= self._vocab_size:
+            raise ValueError(f"predict: k = {k} outside [1, vocab_size = {self._vocab_size}]")
+        fused = self._vocab_topk(rows, k, return_logits)
+        if fused is not None:
+            return fused
+        logits = self.forward(rows)
+        logprobs, ids = torch.log_softmax(logits, dim=-1).topk(k, dim=-1)
+        return ids, logprobs, (logits if return_logits else None)
+
 
 class ImagePostprocessor(nn.Module):
     """"pixels" (identity) and "patches" (reverse space-to-depth); the conv variants are unimplemented in the

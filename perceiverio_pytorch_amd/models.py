@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import itertools
 from enum import Enum
-from typing import Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -193,6 +193,13 @@ class ClassificationPerceiver(nn.Module):
             return self.perceiver(img)
 
 
+class Prediction(NamedTuple):
+    """LanguagePerceiver.predict: ids int64 [B, P, k], logprobs fp32 [B, P, k], logits fp32 [B, P, V] or None."""
+    ids: torch.Tensor
+    logprobs: torch.Tensor
+    logits: Optional[torch.Tensor]
+
+
 class LanguagePerceiver(nn.Module):
     """Byte-level masked language model: 256 x 1280 latents, 26 self-attends (reference language_perceiver.py:10-74)."""
 
@@ -228,6 +235,54 @@ class LanguagePerceiver(nn.Module):
     def forward(self, inputs: torch.Tensor, input_masks: torch.Tensor):
         with _policy_scope(self):
             return self.perceiver(inputs, input_mask=input_masks, query_mask=input_masks)
+
+    # predict(): only the positions asked for are decoded (decoder rows are independent), and the rows become logits,
+    # log-probabilities and top-k ids on the device (EmbeddingPostprocessor.fused_predict -> pio_vocab_topk); False restores
+    # the chain behind the decoder: the tied-embedding GEMM, log_softmax and topk in torch.
+    @property
+    def fused_predict(self) -> bool:
+        return self.perceiver._output_postprocessors["__default"].fused_predict
+
+    @fused_predict.setter
+    def fused_predict(self, on: bool) -> None:
+        self.perceiver._output_postprocessors["__default"].fused_predict = bool(on)
+
+    def _positions(self, positions, batch: int, device):
+        """`positions` of predict() as a validated int64 index tensor [P] or [B, P] on `device` (None: None)."""
+        t = self.perceiver._output_queries["__default"]._position_encoding.pos_embs.shape[0]
+        if positions is None:
+            return None
+        if not isinstance(positions, torch.Tensor):
+            positions = torch.as_tensor(list(positions), dtype=torch.int64)
+        if positions.dtype.is_floating_point or positions.dtype in (torch.bool, torch.complex64, torch.complex128):
+            raise ValueError(f"predict: positions must be integers, got {positions.dtype}")
+        if positions.dim() not in (1, 2) or (positions.dim() == 2 and positions.shape[0] != batch):
+            raise ValueError(f"predict: positions must be [P] or [{batch}, P], got {tuple(positions.shape)}")
+        if positions.shape[-1] < 1:
+            raise ValueError("predict: no positions")
+        host = positions.detach().cpu()          # (a CUDA tensor: the one read-back)
+        lo, hi = int(host.min()), int(host.max())
+        if lo < 0 or hi >= t:
+            raise ValueError(f"predict: position {lo if lo < 0 else hi} outside [0, {t})")
+        return positions.detach().to(device=device, dtype=torch.int64)
+
+    def predict(self, inputs: torch.Tensor, input_masks: torch.Tensor, positions=None, k: int = 5,
+                return_logits: bool = False) -> "Prediction":
+        """Masked-token prediction: Prediction(ids int64 [B, P, k], logprobs fp32 [B, P, k], logits fp32 [B, P, V] or None) --
+        the k most probable tokens of every chosen position, most probable first, with their log-probabilities.
+
+        positions: a sequence of ints or an integer tensor [P] (the same positions for every sample) or [B, P] (each sample
+        its own); None: every position.  A CPU tensor or a sequence is validated where it is; a CUDA tensor is read back to
+        the host ONCE for validation (a synchronisation).  An index outside [0, max_seq_len) or an empty selection raises
+        ValueError before anything reaches the device, and so does k outside [1, vocab_size]."""
+        post = self.perceiver._output_postprocessors["__default"]
+        if not 1 <= int(k) <= post._vocab_size:
+            raise ValueError(f"predict: k = {k} outside [1, vocab_size = {post._vocab_size}]")
+        index = self._positions(positions, inputs.shape[0], inputs.device)
+        with _policy_scope(self):
+            out = self.perceiver(inputs, input_mask=input_masks, query_mask=input_masks, query_index=index,
+                                 postprocess=lambda rows: post.predict(rows, int(k), bool(return_logits)))
+        return Prediction(*out)
 
 
 class FlowPerceiver(nn.Module):

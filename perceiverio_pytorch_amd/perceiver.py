@@ -549,17 +549,22 @@ class PerceiverIO(nn.Module):
         return torch.cat([queries[m] for m in sorted(queries.keys())], dim=1), sizes
 
     def forward(self, inputs, *, subsampled_output_points=None, pos=None, input_mask=None, query_mask=None,
-                query_shard=None):
+                query_shard=None, query_index=None, postprocess=None):
         """Reference signature (perceiver.py:287-288) plus `query_shard=(rank, world)`: decode only this rank's slice
         of the query rows and all-gather the result along the query axis (dist.decode_query_sharded) -- the
         multi-GPU form for batches smaller than the world (optical flow).  Needs an initialised process group.
+
+        `query_index` (None = every row): an int64 index tensor [P] (the same rows for every sample) or [B, P] (each
+        sample its own) of the query rows to decode, for a single output modality -- see _gather_query_rows; the caller
+        validates the indices.  `postprocess` (None = the output postprocessors): a callable that takes the decoder output
+        [B, rows, C] in their place, under the decoder's precision policy (LanguagePerceiver.predict).
 
         The fp16 range guard of the folded latent stack (runtime.range_check) is resolved HERE, once, after everything
         has been enqueued: the encoder's kernels report into a device word, nothing synchronises between encoder and
         decoder, and the word is read where the caller is about to consume the outputs.  A set word repeats the
         forward with the fold off (PIO_E_RANGE if that does not help)."""
         kw = dict(subsampled_output_points=subsampled_output_points, pos=pos, input_mask=input_mask,
-                  query_mask=query_mask, query_shard=query_shard)
+                  query_mask=query_mask, query_shard=query_shard, query_index=query_index, postprocess=postprocess)
         with R.defer_range_checks() as guard:
             outputs = self._forward(inputs, **kw)
         if guard.pending and any(int(f.item()) != 0 for f in guard.pending):
@@ -570,8 +575,30 @@ class PerceiverIO(nn.Module):
                 self._encoder._range_fallback = False
         return outputs
 
+    @staticmethod
+    def _gather_query_rows(query, query_mask, index):
+        """(query, query_mask) restricted to the rows `index` names: int64 [P] -- the same rows of every sample; a
+        batch-invariant (stride-0) query stays ONE [1, P, C] array behind a stride-0 batch axis, so the decoder still
+        normalises and projects it once -- or [B, P], each sample its own rows.  Decoder rows are independent and the mask
+        is gathered with them: a gathered row sees exactly what it sees in a full forward."""
+        b = query.shape[0]
+        if index.dim() == 1:
+            if b > 1 and query.stride(0) == 0:
+                query = torch.broadcast_to(query[:1].index_select(1, index), (b, index.shape[0], query.shape[2]))
+            else:
+                query = query.index_select(1, index)
+            if query_mask is not None:
+                query_mask = query_mask.index_select(1, index.to(query_mask.device))
+        else:
+            if tuple(index.shape[:1]) != (b,) or index.dim() != 2:
+                raise ValueError(f"query_index: expected [P] or [{b}, P], got {tuple(index.shape)}")
+            query = torch.gather(query, 1, index[:, :, None].expand(-1, -1, query.shape[2]))
+            if query_mask is not None:
+                query_mask = torch.gather(query_mask, 1, index.to(query_mask.device))
+        return query, query_mask
+
     def _forward(self, inputs, *, subsampled_output_points=None, pos=None, input_mask=None, query_mask=None,
-                 query_shard=None):
+                 query_shard=None, query_index=None, postprocess=None):
         if type(inputs) is torch.Tensor:
             inputs = {"__default": inputs}
         split = self._split_input(inputs, pos) if self.split_encoder_input else None
@@ -612,12 +639,20 @@ class PerceiverIO(nn.Module):
                 query_mask = query_mask[:, self.decoder_query_rows]
             assert len(query_sizes) == 1, "decoder_query_rows is defined for a single output modality"
             query_sizes = {m: query.shape[1] for m in query_sizes}
+        if query_index is not None:
+            assert len(query_sizes) == 1 and not isinstance(query, (tuple, list)), \
+                "query_index is defined for a single output modality with one query array"
+            query, query_mask = self._gather_query_rows(query, query_mask, query_index)
+            query_sizes = {m: query.shape[1] for m in query_sizes}
         with R.precision(self.decoder_policy):
             if query_shard is not None:
                 from .dist import decode_query_sharded
                 outputs = decode_query_sharded(self._decoder, query, latents, query_mask, *query_shard)
             else:
                 outputs = self._decoder(query, latents, query_mask=query_mask)
+        if postprocess is not None:
+            with R.precision(self.decoder_policy):
+                return postprocess(outputs)
         if self._output_postprocessors:
             with R.precision(self.decoder_policy):       # (the heads behind the decoder belong to its half)
                 heads = self._project_heads(outputs, query_sizes)

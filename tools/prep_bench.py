@@ -14,6 +14,10 @@
                                                 prints one JSON line
     python tools/prep_bench.py --language-front     the language front end (pio_embed_tokens) at full size ([B, 2048, 768],
                                                 V = 262, int64 ids), B = 1, 8 and 100; prints one JSON line
+    python tools/prep_bench.py --language-predict   masked-token prediction (LanguagePerceiver.predict, pio_vocab_topk) against
+                                                the full forward plus log_softmax / topk at (B, P) = (1, 9), (8, 307),
+                                                (100, 307), (100, 2048), and the vocabulary head alone in both modes over
+                                                1 .. 204 800 rows (the routing threshold); prints one JSON line
     python tools/prep_bench.py --flow-blend         the tile blend of tiled flow inference (pio_flow_blend_tiles) against the
                                                 torch chain at 436 x 1024 (6 tiles) and 1080 x 1920 (20 tiles), b = 1; prints
                                                 one JSON line
@@ -496,6 +500,102 @@ def language_front(repeats, launches):
     print(json.dumps(result))
 
 
+def language_predict(repeats, launches):
+    """Masked-token prediction of the default LanguagePerceiver (T = 2048, C = 768, V = 262, k = 5), timed like language_front
+    (device events around back-to-back calls after 3 warm-up calls, `repeats` times, the ways alternating inside every
+    repeat; `launches` calls per repeat, 3 at B = 100):
+      parent  -- what the parent commit offers: model(ids, mask) (all 2048 positions decoded, [B, 2048, 262] logits -- forward is
+                 untouched by predict, bit for bit), then log_softmax(out[b, pos]).topk(k) in torch
+      predict -- model.predict(ids, mask, pos, k) with the shipped routing
+      chain   -- model.predict with fused_predict = False: the chosen rows decoded, then hip_linear, log_softmax, topk
+    for (B, P) = (1, 9), (8, 307), (100, 307) with per-sample positions and (100, 2048) with positions=None.
+    Then the vocabulary head alone on seeded decoder rows [1, R, 768] under the decoder's policy, R from 1 to 204 800:
+      fused   -- ONE pio_vocab_topk launch that multiplies and selects
+      select  -- hip_linear (cast + GEMM), then pio_vocab_topk's selection alone
+      chain   -- hip_linear, log_softmax, topk
+    and from it the routing threshold: the largest R of the sweep up to which `fused` is the faster of the two kernel routes at
+    every R measured.  Prints one JSON line."""
+    from perceiverio_pytorch_amd import fused_io as FIO, runtime as R
+    from perceiverio_pytorch_amd.models import LanguagePerceiver, split_policy
+    T, V, K = 2048, 262, 5
+    torch.manual_seed(5)
+    model = LanguagePerceiver().to(dev).eval()
+    post = model.perceiver._output_postprocessors["__default"]
+    with torch.no_grad():
+        post.bias.copy_(torch.randn(V) * 0.1)
+    result = {"tool": "tools/prep_bench.py --language-predict", "policy": model.precision_policy, "T": T, "V": V, "k": K,
+              "repeats": repeats, "unit": "us", "shipped_VOCAB_FUSED_MAX_ROWS": FIO.VOCAB_FUSED_MAX_ROWS, "model": {},
+              "head_alone": {}}
+
+    def stats(v):
+        return {"median": statistics.median(v), "min": min(v), "max": max(v)}
+    for b, p in ((1, 9), (8, 307), (100, 307), (100, T)):
+        n = launches if b < 100 else 3
+        ids = torch.randint(0, V, (b, T), device=dev)
+        mask = torch.ones(b, T, device=dev)
+        gen = torch.Generator().manual_seed(b * 7 + p)
+        # (positions as a host tensor, as a tokenizer hands them over: a CUDA tensor costs predict a read-back per call)
+        pos = None if p == T else torch.stack([torch.randperm(T, generator=gen)[:p] for _ in range(b)])
+        index = torch.arange(T, device=dev).expand(b, T) if pos is None else pos.to(dev)
+
+        def parent():
+            out = model(ids, mask)
+            rows = torch.gather(out, 1, index[:, :, None].expand(-1, -1, V))
+            return torch.log_softmax(rows, dim=-1).topk(K, dim=-1)
+
+        def predict(on=True):
+            def f():
+                model.fused_predict = on
+                return model.predict(ids, mask, pos, k=K)
+            return f
+        ways = {"parent": parent, "predict": predict(True), "chain": predict(False)}
+        a, c = ways["parent"](), ways["predict"]()
+        agree = float((a[1][..., 0] == c.ids[..., 0]).float().mean())
+        del a, c
+        times = {w: [] for w in ways}
+        for _ in range(repeats):
+            for w, f in ways.items():
+                times[w].append(timed(f, n))
+        model.fused_predict = True
+        case = {w: stats(v) for w, v in times.items()}
+        case.update(rows=b * p, calls_per_repeat=n, top1_agreement_with_parent=agree,
+                    route=FIO.vocab_plan(post, torch.empty(b, p, 768, device=dev), K))
+        result["model"][f"B={b},P={p}"] = case
+        del ids, mask
+        torch.cuda.empty_cache()
+    sweep = (1, 9, 64, 512, 2456, 4096, 8192, 16384, 30700, 65536, 204800)
+    shipped = FIO.VOCAB_FUSED_MAX_ROWS
+    with R.precision(split_policy(model.precision_policy)[1]):
+        for r in sweep:
+            x = torch.randn(1, r, 768, device=dev, generator=torch.Generator(device=dev).manual_seed(r))
+
+            def head(limit):
+                def f():
+                    FIO.VOCAB_FUSED_MAX_ROWS = limit
+                    return FIO.vocab_topk(post, x, K)
+                return f
+
+            def chain():
+                return torch.log_softmax(post(x), dim=-1).topk(K, dim=-1)
+            ways = {"fused": head(2 ** 31), "select": head(0), "chain": chain}
+            times = {w: [] for w in ways}
+            for _ in range(repeats):
+                for w, f in ways.items():
+                    times[w].append(timed(f, launches if r < 65536 else 5))
+            result["head_alone"][f"R={r}"] = {w: stats(v) for w, v in times.items()}
+            del x
+            torch.cuda.empty_cache()
+    FIO.VOCAB_FUSED_MAX_ROWS = shipped
+    threshold = 0
+    for r in sweep:
+        t = result["head_alone"][f"R={r}"]
+        if t["fused"]["median"] > t["select"]["median"]:
+            break
+        threshold = r
+    result["measured_threshold_rows"] = threshold
+    print(json.dumps(result))
+
+
 def _kernel_launches(f):
     """Device kernels and memory copies of one call of f, counted by the profiler (None where it is not usable)."""
     try:
@@ -695,6 +795,7 @@ if __name__ == "__main__":
     ap.add_argument("--decoder-queries", action="store_true", help="time pio_build_queries against the torch chain")
     ap.add_argument("--multimodal-heads", action="store_true", help="time pio_project_heads against the hip_linear chain")
     ap.add_argument("--language-front", action="store_true", help="time pio_embed_tokens against the torch chain")
+    ap.add_argument("--language-predict", action="store_true", help="time LanguagePerceiver.predict and pio_vocab_topk")
     ap.add_argument("--flow-blend", action="store_true", help="time pio_flow_blend_tiles against the torch chain")
     ap.add_argument("--flow-blend-forward", action="store_true", help="time the whole tiled forward of the flow model")
     ap.add_argument("--flow-image", action="store_true", help="time flow_to_image on the device against the numpy path")
@@ -713,6 +814,8 @@ if __name__ == "__main__":
             multimodal_heads(args.repeats, args.launches)
         elif args.language_front:
             language_front(args.repeats, args.launches)
+        elif args.language_predict:
+            language_predict(args.repeats, args.launches)
         elif args.flow_blend:
             flow_blend(args.repeats, args.launches)
         elif args.flow_blend_forward:
