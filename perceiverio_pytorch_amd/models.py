@@ -21,7 +21,7 @@ from .io_processors import (AudioPostprocessor, AudioPreprocessor, Classificatio
                             OneHotPreprocessor, ProjectionPostprocessor)
 from .output_queries import FlowQuery, FourierQuery, TrainableQuery
 from .perceiver import PerceiverIO
-from .runtime import get_backend, precision
+from .runtime import get_backend, precision, split_policy, split_policy3  # noqa: F401  (both re-exported)
 from .position_encoding import PosEncodingType
 
 
@@ -83,24 +83,6 @@ from .position_encoding import PosEncodingType
 #    model needs three-sweep GEMMs AND pair cores, i.e. about twice the default's time.
 DEFAULT_POLICY = {"ClassificationPerceiver": "fp16x2w/fp16sd/fp16x2af", "LanguagePerceiver": "fp16x2w/fp16x2o/fp16x3f",
                   "FlowPerceiver": "fp16/fp16x2af", "MultiModalPerceiver": "fp16x2w/fp16x2afo"}
-
-
-def split_policy3(policy):
-    """"X/A/B" -> (X, A, B): X for the encoder's cross-attend alone, A for the latent self-attend stack, B for the decoder;
-    "A/B" -> (None, A, B) (the cross-attend runs under A); a plain name (or None) applies everywhere."""
-    if policy is not None and "/" in policy:
-        parts = policy.split("/")
-        if len(parts) == 3:
-            return parts[0], parts[1], parts[2]
-        if len(parts) == 2:
-            return None, parts[0], parts[1]
-        raise ValueError(f"precision policy {policy!r}: expected 'name', 'encoder/decoder' or 'cross/stack/decoder'")
-    return None, policy, policy
-
-
-def split_policy(policy):
-    """(encoder policy, decoder policy) of a task model's policy string (split_policy3 without the cross-attend's)."""
-    return split_policy3(policy)[1:]
 
 
 class _policy_scope:

@@ -87,7 +87,7 @@ class PerceiverEncoder(R.PackedOwner):
         Lyr = len(self.self_attends)
         # policy "fp16sd": one set of packed images per block (error-feedback rounding of the shared weights over the
         # block index, SelfAttention._desc_blocks) -- layers[b * Lyr + i]; otherwise the Lyr shared descriptors
-        per_block = R.policy_block_feedback() and self._num_blocks > 1 and Lyr > 0
+        per_block = R.policy().feedback and self._num_blocks > 1 and Lyr > 0
         nset = self._num_blocks if per_block else 1
         descs = []
         for sa in self.self_attends:
@@ -220,12 +220,9 @@ class PerceiverDecoder(R.PackedOwner):
             nn.init.constant_(self.final_layer.bias, 0)
 
     def _final_desc(self):
-        return self._packed.get(R.param_key(self.final_layer.weight, self.final_layer.bias), self._build_final)
-
-    def _build_final(self):
-        dtype, wlevel, _split = R.policy_dtype()
-        two = wlevel >= 2 or "final_layer" in R.policy_fine_split()
-        return R.PackedLinear(self.final_layer.weight, self.final_layer.bias, 1, 1, dtype, two), None
+        fl = self.final_layer
+        return self._packed.get(R.param_key(fl.weight, fl.bias), lambda: (
+            R.PackedLinear(fl.weight, fl.bias, 1, 1, R.policy().dtype, R.splits("final_layer")), None))
 
     def forward(self, query, latents, *, query_mask=None, q_cache=None):
         """Reference signature (perceiver.py:166) plus `q_cache`: a dict the CALLER keeps per query array whose content

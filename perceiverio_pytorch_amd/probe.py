@@ -146,17 +146,16 @@ def recommend_precision_policy(model, *inputs, threshold: Optional[float] = None
     """Run ONE forward of `model(*inputs, **kw)` under the probe and return (policy string, report).
 
     The string starts from the model's current policy (`model.precision_policy`, else the ambient one) split into its
-    three parts cross / stack / decoder (models.split_policy3); every part whose largest logit exceeds `threshold`
+    three parts cross / stack / decoder (runtime.split_policy3); every part whose largest logit exceeds `threshold`
     becomes "fp16x3fq" (Q and K as fp16 pairs inside the fused cores), the others are left alone -- when none does, the
     model's own string comes back unchanged.  Nothing is set: assign `model.precision_policy` yourself.
     report = {"absmax": {part: figure}, "threshold": t, "calls": n, "policy": the model's current string}."""
-    from .models import split_policy3
     if threshold is None:
         threshold = DEFAULT_THRESHOLD
     if threshold is None:
         raise ValueError("recommend_precision_policy: no default threshold is set; pass threshold=")
     current = getattr(model, "precision_policy", None) or R.get_precision_policy()
-    cross, stack, dec = split_policy3(current)
+    cross, stack, dec = R.split_policy3(current)
     parts = {"cross": cross if cross is not None else stack, "stack": stack, "decoder": dec}
     with torch.no_grad(), logit_probe() as probe:
         model(*inputs, **kw)
@@ -273,7 +272,7 @@ def recommend_operand_dtype(model, *inputs, limit: float = FP16_MAX, **kw):
     """Run ONE forward of `model(*inputs, **kw)` under the range probe and return (policy string, report).
 
     The string starts from the model's current policy (`model.precision_policy`, else the ambient one) split into its
-    three parts cross / stack / decoder (models.split_policy3); every part whose largest 16-bit operand is inf or exceeds
+    three parts cross / stack / decoder (runtime.split_policy3); every part whose largest 16-bit operand is inf or exceeds
     `limit` becomes "bf16x3" -- the only bf16 policy that meets 1e-3 (runtime.py) -- the others are left alone, and when
     none does the model's own string comes back unchanged.  Nothing is set: assign `model.precision_policy` yourself.
     `limit` defaults to the fp16 maximum, 65 504 (not a tuned number): pass a lower one for headroom.
@@ -281,9 +280,8 @@ def recommend_operand_dtype(model, *inputs, limit: float = FP16_MAX, **kw):
 
     A forward that ends in the library's own PIO_E_RANGE error (the guard of the LayerNorm-folded stack) still yields its
     figures: that is the case the recommendation exists for."""
-    from .models import split_policy3
     current = getattr(model, "precision_policy", None) or R.get_precision_policy()
-    cross, stack, dec = split_policy3(current)
+    cross, stack, dec = R.split_policy3(current)
     parts = {"cross": cross if cross is not None else stack, "stack": stack, "decoder": dec}
     probe = range_probe()
     try:

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -20,59 +20,71 @@ from . import _lib as L
 #   bf16*    the same with bf16 operands (wider range, 8x coarser mantissa; only bf16x3 meets 1e-3).
 # (numbers: tools/numerics_model.py and tests/test_parity_gpu.py; discussion in DESIGN.md)
 # ------------------------------------------------------------------------------------------------
-# (operand dtype, weight split level, activations split)
-#   weight split level: 0 none | 1 proj_v + final ("x2s": the two projections whose weight rounding matters most,
-#   4.5e-4 on the ImageNet model at 1.2x the fp16 cost) | 2 + fc1, fc2, decoder final_layer ("x2w": 3.1e-4) |
-#   3 every weight incl. proj_q / proj_k ("x3").  proj_q / proj_k stay single below level 3: their rounding is
-#   not measurable in the output (3.13e-4 with or without it, tools/numerics_model.py attribution).
-_POLICIES = {"fp16": (L.PIO_DT_F16, 0, False), "fp16x2s": (L.PIO_DT_F16, 1, False),
-             "fp16x2w": (L.PIO_DT_F16, 2, False), "fp16x3": (L.PIO_DT_F16, 3, True),
-             "bf16": (L.PIO_DT_BF16, 0, False), "bf16x2w": (L.PIO_DT_BF16, 2, False),
-             "bf16x3": (L.PIO_DT_BF16, 3, True),
-             # x3f: every GEMM with split operands as x3, but the attention core (Q K^T, softmax, P V) single-sweep on
-             # the fused kernels (q / k / v / p rounded once; the core's output leaves as a pair): no score matrix
-             "fp16x3f": (L.PIO_DT_F16, 3, True), "bf16x3f": (L.PIO_DT_BF16, 3, True),
-             # x3fq: "x3f" with Q and K entering the fused core as (hi, lo) pairs -- S = Q_hi K_hi + Q_lo K_hi + Q_hi K_lo
-             # inside the kernel (pio_attention_t.act_split = 3): the one rounding "x3f" leaves in front of the exponent is
-             # gone, still no score matrix.  For models whose logits are large (trained LayerNorm gains: |s| ~ 10-15).
-             # Pair cores exist for fp16 heads of dk <= 32; any other shape runs the materialised path of "x3" (fp16 only:
-             # there is no bf16 pair core, hence no "bf16x3fq")
-             "fp16x3fq": (L.PIO_DT_F16, 3, True),
-             # x2af: split ACTIVATIONS against single weights (A_hi B^T + A_lo B^T: two sweeps) around a single-sweep
-             # fused attention core -- for decoders whose error is dominated by the rounding of wide-range inputs
-             # (Fourier / position features of dense outputs), at 2/3 of the x3f cost
-             "fp16x2af": (L.PIO_DT_F16, 0, True),
-             # fp16sd: "fp16" with ERROR-FEEDBACK rounding of the weights an encoder shares over its blocks: block b
-             # multiplies with fp16(W + E_{b-1}), E_b = (W + E_{b-1}) - that image (first-order sigma-delta over the
-             # block index).  Every image is a rounding of W within one ulp; the error the 8 applications of a shared
-             # weight accumulate stays below half an ulp instead of growing 8-fold.  Same kernels, same time, 8 x the
-             # packed images (604 MB for the ImageNet stack); -18..-21 % error on the ImageNet goldens.  Everything
-             # that is not a weight-shared block stack runs as under "fp16".
-             "fp16sd": (L.PIO_DT_F16, 0, False),
-             # finer weight splits of a self-attend stack (round 4): only the out projection ("final"), or only proj_v, of
-             # the two that "x2s" splits -- a second K sweep costs its GEMM's time again
-             "fp16x2o": (L.PIO_DT_F16, 0, False), "fp16x2v": (L.PIO_DT_F16, 0, False),
-             # x2afo: "x2af" (split activations around the single-sweep fused core) + split WEIGHTS on the output side of a
-             # decoder only -- the attention's out projection, the decoder's final_layer, the heads behind it -- where a
-             # dense-output model has nothing left to average a weight's rounding away (multimodal, second seed: x2af
-             # 1.01e-3 / 1.14e-3, x2afo 4.0e-4 / 5.3e-4 at +4 % time; x3f 0.6e-4 / 2.7e-4 at +17 %)
-             "fp16x2afo": (L.PIO_DT_F16, 0, True)}
-# weights split under the fine policies (beside the level of _POLICIES): Attention: proj_v, final; MLP: fc1, fc2; decoder:
-# final_layer; heads behind the decoder (hip_linear): post
-_FINE_SPLIT = {"fp16x2o": {"final"}, "fp16x2v": {"proj_v"}, "fp16x2afo": {"final", "final_layer", "post"}}
-_FUSED_CORE = {"fp16x3f", "bf16x3f", "fp16x2af", "fp16x2afo", "fp16x3fq"}
-_PAIR_CORE = {"fp16x3fq"}      # ... of which: Q / K as pairs inside the core's Q K^T
-_BLOCK_FEEDBACK = {"fp16sd"}
-_policy = os.environ.get("PIO_PRECISION", "fp16x3")
-if _policy not in _POLICIES:
-    raise ValueError(f"PIO_PRECISION={_policy!r} not in {sorted(_POLICIES)}")
+# One record per policy.  `split`: the linears whose WEIGHTS are (hi, lo) pairs -- Attention: proj_q, proj_k, proj_v, final;
+# MLP: fc1, fc2; decoder: final_layer; heads behind the decoder (hip_linear): post.  `act_split`: activations are pairs,
+# around the attention `core` named (attention_act_split).  `feedback`: one image set per block of a weight-shared stack.
+class Policy(NamedTuple):
+    dtype: int
+    split: frozenset
+    act_split: bool = False
+    core: str = "materialised"
+    feedback: bool = False
+
+
+# nested weight sets: "x2s" the two projections whose weight rounding matters most (4.5e-4 on the ImageNet model at 1.2x the
+# fp16 cost) | "x2w" + fc1, fc2, final_layer, post (3.1e-4) | "x3" every weight.  proj_q / proj_k stay single below "x3": their
+# rounding is not measurable in the output (3.13e-4 with or without it, tools/numerics_model.py attribution).
+_NONE = frozenset()
+_X2S = frozenset({"proj_v", "final"})
+_X2W = _X2S | {"fc1", "fc2", "final_layer", "post"}
+_X3 = _X2W | {"proj_q", "proj_k"}
+_F16, _BF16 = L.PIO_DT_F16, L.PIO_DT_BF16
+_POLICIES = {
+    "fp16": Policy(_F16, _NONE), "fp16x2s": Policy(_F16, _X2S), "fp16x2w": Policy(_F16, _X2W),
+    "fp16x3": Policy(_F16, _X3, True),
+    "bf16": Policy(_BF16, _NONE), "bf16x2w": Policy(_BF16, _X2W), "bf16x3": Policy(_BF16, _X3, True),
+    # x3f: every GEMM with split operands as x3, but the attention core (Q K^T, softmax, P V) single-sweep on the fused
+    # kernels (q / k / v / p rounded once; the core's output leaves as a pair): no score matrix
+    "fp16x3f": Policy(_F16, _X3, True, "fused"), "bf16x3f": Policy(_BF16, _X3, True, "fused"),
+    # x3fq: "x3f" with Q and K entering the fused core as (hi, lo) pairs -- S = Q_hi K_hi + Q_lo K_hi + Q_hi K_lo
+    # inside the kernel (pio_attention_t.act_split = 3): the one rounding "x3f" leaves in front of the exponent is
+    # gone, still no score matrix.  For models whose logits are large (trained LayerNorm gains: |s| ~ 10-15).
+    # Pair cores exist for fp16 heads of dk <= 32; any other shape runs the materialised path of "x3" (fp16 only:
+    # there is no bf16 pair core, hence no "bf16x3fq")
+    "fp16x3fq": Policy(_F16, _X3, True, "fused_pair"),
+    # x2af: split ACTIVATIONS against single weights (A_hi B^T + A_lo B^T: two sweeps) around a single-sweep
+    # fused attention core -- for decoders whose error is dominated by the rounding of wide-range inputs
+    # (Fourier / position features of dense outputs), at 2/3 of the x3f cost
+    "fp16x2af": Policy(_F16, _NONE, True, "fused"),
+    # fp16sd: "fp16" with ERROR-FEEDBACK rounding of the weights an encoder shares over its blocks: block b
+    # multiplies with fp16(W + E_{b-1}), E_b = (W + E_{b-1}) - that image (first-order sigma-delta over the
+    # block index).  Every image is a rounding of W within one ulp; the error the 8 applications of a shared
+    # weight accumulate stays below half an ulp instead of growing 8-fold.  Same kernels, same time, 8 x the
+    # packed images (604 MB for the ImageNet stack); -18..-21 % error on the ImageNet goldens.  Everything
+    # that is not a weight-shared block stack runs as under "fp16".
+    "fp16sd": Policy(_F16, _NONE, feedback=True),
+    # finer weight splits of a self-attend stack (round 4): only the out projection ("final"), or only proj_v, of
+    # the two that "x2s" splits -- a second K sweep costs its GEMM's time again
+    "fp16x2o": Policy(_F16, frozenset({"final"})), "fp16x2v": Policy(_F16, frozenset({"proj_v"})),
+    # x2afo: "x2af" (split activations around the single-sweep fused core) + split WEIGHTS on the output side of a
+    # decoder only -- the attention's out projection, the decoder's final_layer, the heads behind it -- where a
+    # dense-output model has nothing left to average a weight's rounding away (multimodal, second seed: x2af
+    # 1.01e-3 / 1.14e-3, x2afo 4.0e-4 / 5.3e-4 at +4 % time; x3f 0.6e-4 / 2.7e-4 at +17 %)
+    "fp16x2afo": Policy(_F16, frozenset({"final", "final_layer", "post"}), True, "fused")}
+
+
+def _known(name: str, message: str = "unknown precision policy {name!r}; choose from {names}") -> str:
+    if name not in _POLICIES:
+        raise ValueError(message.format(name=name, names=sorted(_POLICIES)))
+    return name
+
+
+_policy = _known(os.environ.get("PIO_PRECISION", "fp16x3"), "PIO_PRECISION={name!r} not in {names}")
 
 
 def set_precision_policy(name: str) -> None:
     global _policy
-    if name not in _POLICIES:
-        raise ValueError(f"unknown precision policy {name!r}; choose from {sorted(_POLICIES)}")
-    _policy = name
+    _policy = _known(name)
 
 
 def get_precision_policy() -> str:
@@ -83,9 +95,7 @@ class precision:
     """Context manager: run a block under another precision policy (None = leave the current one)."""
 
     def __init__(self, name: Optional[str]):
-        if name is not None and name not in _POLICIES:
-            raise ValueError(f"unknown precision policy {name!r}; choose from {sorted(_POLICIES)}")
-        self._name = name
+        self._name = None if name is None else _known(name)
         self._saved = None
 
     def __enter__(self):
@@ -101,9 +111,61 @@ class precision:
         return False
 
 
-def policy_dtype(name: Optional[str] = None) -> Tuple[int, bool, bool]:
-    """(operand dtype, weights split, activations split)"""
+def split_policy3(policy):
+    """"X/A/B" -> (X, A, B): X for the encoder's cross-attend alone, A for the latent self-attend stack, B for the decoder;
+    "A/B" -> (None, A, B) (the cross-attend runs under A); a plain name (or None) applies everywhere."""
+    parts = policy.split("/") if policy is not None else [None]
+    if len(parts) > 3:
+        raise ValueError(f"precision policy {policy!r}: expected 'name', 'encoder/decoder' or 'cross/stack/decoder'")
+    return tuple(parts) if len(parts) == 3 else (None, parts[0], parts[-1])
+
+
+def split_policy(policy):
+    """(encoder policy, decoder policy) of a task model's policy string (split_policy3 without the cross-attend's)."""
+    return split_policy3(policy)[1:]
+
+
+# ---- what the packing sites ask (name: a policy, None = the ambient one) ----
+def policy(name: Optional[str] = None) -> Policy:
     return _POLICIES[name or _policy]
+
+
+def policy_dtype(name: Optional[str] = None) -> Tuple[int, bool]:
+    """(operand dtype, activations split)"""
+    return policy(name).dtype, policy(name).act_split
+
+
+def torch_dtype(dtype: int) -> torch.dtype:
+    return torch.float16 if dtype == L.PIO_DT_F16 else torch.bfloat16
+
+
+def splits(linear: str, name: Optional[str] = None) -> bool:
+    """Are the weights of `linear` (a name of Policy.split) packed as (hi, lo) pairs?  PIO_EXTRA_SPLIT=a,b adds names on
+    top of every policy (A/B experiments: tools/); it is read per call."""
+    return linear in policy(name).split or linear in os.environ.get("PIO_EXTRA_SPLIT", "").split(",")
+
+
+def attention_act_split(name: Optional[str] = None) -> int:
+    """pio_attention_t.act_split of a policy: 0 single activations, 1 split everywhere (materialised core), 2 split
+    projections around the single-operand fused core, 3 the same with pair-operand Q K^T in the core."""
+    p = policy(name)
+    return {"materialised": 1, "fused": 2, "fused_pair": 3}[p.core] if p.act_split else 0
+
+
+def kv_fold_offered(name: Optional[str] = None) -> bool:
+    """K / V projection fold of a single-head cross-attend (Attention._build_desc, which says why): every policy whose
+    weight set lies below "x2s" -- the finer ones ("x2o", "x2v", "x2afo") keep the offer.  PIO_EXTRA_SPLIT does not count."""
+    return not _X2S <= policy(name).split
+
+
+def ln_fold_offered(name: Optional[str] = None) -> bool:
+    """LayerNorm fold of a self-attend block (SelfAttention._build_ln_fold): single proj_q / proj_k, single activations."""
+    return not ("proj_q" in policy(name).split or policy(name).act_split)
+
+
+def qkv_stack_allowed(name: Optional[str] = None) -> bool:
+    """q | k | v in one packed image: only a suffix of a stack may carry a lo image, so proj_q / proj_k must be single."""
+    return not (splits("proj_q", name) or splits("proj_k", name))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -184,46 +246,15 @@ def capturing(device: torch.device) -> bool:
         return False
 
 
-def policy_fine_split(name: Optional[str] = None) -> set:
-    """Names of the linears whose weights are (hi, lo) pairs beyond what the policy's level says (Attention: proj_v, final;
-    MLP: fc1, fc2; decoder: final_layer; heads behind the decoder: post)."""
-    extra = set(os.environ.get("PIO_EXTRA_SPLIT", "").split(",")) - {""}      # (A/B experiments: tools/)
-    return _FINE_SPLIT.get(name or _policy, set()) | extra
-
-
-def policy_core_single(name: Optional[str] = None) -> bool:
-    """True for the "x3f" policies: split operands in the projections, single-sweep fused attention core."""
-    return (name or _policy) in _FUSED_CORE
-
-
-def policy_core_pair(name: Optional[str] = None) -> bool:
-    """True for "fp16x3fq": a fused-core policy whose core takes Q and K as (hi, lo) pairs (act_split = 3)."""
-    return (name or _policy) in _PAIR_CORE
-
-
-def attention_act_split(name: Optional[str] = None) -> int:
-    """pio_attention_t.act_split of a policy: 0 single activations, 1 split everywhere (materialised core), 2 split
-    projections around the single-operand fused core, 3 the same with pair-operand Q K^T in the core."""
-    if not _POLICIES[name or _policy][2]:
-        return 0
-    return 3 if policy_core_pair(name) else 2 if policy_core_single(name) else 1
-
-
-def policy_block_feedback(name: Optional[str] = None) -> bool:
-    """True for the policies that pack one image set per block of a weight-shared stack ("fp16sd")."""
-    return (name or _policy) in _BLOCK_FEEDBACK
-
-
 def feedback_images(w: torch.Tensor, nblk: int, dtype: int):
     """The nblk error-feedback roundings of the fp32 weight `w` to the operand dtype, as fp32 tensors that are exactly
     representable in it (packing them is exact): image_b = round(w + E_{b-1}), E_b = (w + E_{b-1}) - image_b, E_{-1} = 0.
     |w - image_b| < 1 ulp for every b and |sum_{b<=k} (w - image_b)| = |E_k| <= ulp / 2 for every k."""
-    tdt = torch.float16 if dtype == L.PIO_DT_F16 else torch.bfloat16
     w = w.detach().float()
     out, e = [], torch.zeros_like(w)
     for _ in range(nblk):
         t = w + e
-        hi = t.to(tdt).float()
+        hi = t.to(torch_dtype(dtype)).float()
         e = t - hi
         out.append(hi)
     return out
@@ -393,7 +424,6 @@ def cu_share(n: int) -> int:
 def _masked_streams(device: torch.device, n: int) -> list:
     """`n` streams with complementary CU masks: slice i owns CUs [i*32/n, (i+1)*32/n) of EVERY XCD (mask bit j is CU
     j // 8 of XCD j % 8), so each slice keeps the round-robin dispatch over all eight L2s."""
-    import ctypes as C
     lib = L.lib()
     per = 32 // n
     out = []
@@ -444,7 +474,7 @@ class PackedLinear:
         w = weight.detach()
         if w.dtype != torch.float32 or not w.is_contiguous():
             w = w.float().contiguous()
-        tdt = torch.float16 if dtype == L.PIO_DT_F16 else torch.bfloat16
+        tdt = torch_dtype(dtype)
         alloc = torch.zeros if self.n > rows_packed else torch.empty     # (rows behind the packed ones stay zero)
         self.hi = alloc((self.n, self.k), dtype=tdt, device=dev)
         self.lo = alloc((self.n, self.k), dtype=tdt, device=dev) if two_pass else None
@@ -481,7 +511,7 @@ class PackedStack:
         self.k = padc(inn)
         rows = [row_heads * pad8(w.shape[0] // row_heads) for w, _ in pairs]
         self.n = sum(rows)
-        tdt = torch.float16 if dtype == L.PIO_DT_F16 else torch.bfloat16
+        tdt = torch_dtype(dtype)
         self.hi = torch.empty((self.n, self.k), dtype=tdt, device=dev)
         self.lo = torch.empty((self.n, self.k), dtype=tdt, device=dev) if two_pass else None
         self.bias = torch.empty((self.n,), dtype=torch.float32, device=dev)
@@ -646,17 +676,16 @@ def layernorm_desc(ln: torch.nn.LayerNorm, keep: list) -> L.LayerNorm:
 # I/O plumbing right behind the decoder (tied-embedding vocabulary projection of the language model)
 # ------------------------------------------------------------------------------------------------
 def hip_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], cache: PackedCache) -> torch.Tensor:
-    """y[..., out] = x[..., in] W^T + b on the MI355X under the current precision policy (weights split from level
-    "x2w" on, activations under "x3").  `cache` (the owner's) keeps the packed weight image between calls."""
+    """y[..., out] = x[..., in] W^T + b on the MI355X under the current precision policy (the weight is the policy's
+    "post").  `cache` (the owner's) keeps the packed weight image between calls."""
     require_device(x, "hip_linear")
     dev = x.device
-    dtype, wlevel, split = policy_dtype()
-    lin = cache.get(param_key(weight, bias), lambda: (
-        PackedLinear(weight, bias, 1, 1, dtype, wlevel >= 2 or "post" in policy_fine_split()), None))
+    dtype, split = policy_dtype()
+    lin = cache.get(param_key(weight, bias), lambda: (PackedLinear(weight, bias, 1, 1, dtype, splits("post")), None))
     lead = x.shape[:-1]
     x3 = as_f32_3d(x.reshape(1, -1, x.shape[-1]))
     rows, n_out = x3.shape[1], weight.shape[0]
-    tdt = torch.float16 if dtype == L.PIO_DT_F16 else torch.bfloat16
+    tdt = torch_dtype(dtype)
     x16 = torch.empty((rows, lin.k), dtype=tdt, device=dev)
     x16lo = torch.empty((rows, lin.k), dtype=tdt, device=dev) if split else None
     out = torch.empty((rows, n_out), dtype=torch.float32, device=dev)

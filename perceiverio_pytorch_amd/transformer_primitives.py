@@ -147,16 +147,14 @@ class Attention(_HipModule):
     # ---- packed descriptor -------------------------------------------------------------------
     def _build_desc(self, ov=None):
         """`ov` (policy "fp16sd"): {linear: fp32 weight image to pack instead of its parameter} for one block."""
-        dtype, wlevel, split = R.policy_dtype()
+        dtype, split = R.policy_dtype()
         H = self._num_heads
-        two = wlevel >= 3          # proj_q / proj_k: split only under the all-split (x3) policies
+        q_two, k_two, v_two = R.splits("proj_q"), R.splits("proj_k"), R.splits("proj_v")
         wt = (lambda lin: ov[lin]) if ov else (lambda lin: lin.weight)
-        q = R.PackedLinear(wt(self.proj_q), self.proj_q.bias, H, 1, dtype, two)
-        k = R.PackedLinear(wt(self.proj_k), self.proj_k.bias, H, 1, dtype, two)
-        fine = R.policy_fine_split()
-        v_two, o_two = wlevel >= 1 or "proj_v" in fine, wlevel >= 1 or "final" in fine
+        q = R.PackedLinear(wt(self.proj_q), self.proj_q.bias, H, 1, dtype, q_two)
+        k = R.PackedLinear(wt(self.proj_k), self.proj_k.bias, H, 1, dtype, k_two)
         v = R.PackedLinear(wt(self.proj_v), self.proj_v.bias, H, 1, dtype, v_two)
-        o = R.PackedLinear(wt(self.final), self.final.bias, 1, H, dtype, o_two, k_channels=False)
+        o = R.PackedLinear(wt(self.final), self.final.bias, 1, H, dtype, R.splits("final"), k_channels=False)
         dk, dv = self._qk_channels_per_head, self._v_channels_per_head
         d = L.Attention(q.desc, k.desc, v.desc, o.desc, H, dk, dv, R.pad8(dk), R.pad8(dv),
                         self.proj_q.in_features, self.proj_k.in_features, self.proj_v.in_features,
@@ -166,7 +164,7 @@ class Attention(_HipModule):
         # restructurings", reference :93-95,138,163): q (x Wk^T + bk)^T = (q Wk) x^T + const and
         # P (x Wv^T + bv) Wo^T + bo = (P x)(Wo Wv)^T + (Wo bv + bo).  The folded weights are formed in float64 and packed
         # like any other; the library takes them when keys outnumber query rows 4 : 1 (the encoders' cross-attends).
-        # Offered under the single-weight policies only ("fp16", "fp16sd", "fp16x2af"): there it replaces single-sweep K / V
+        # Offered where the weights are single (runtime.kv_fold_offered: below "x2s"): there it replaces single-sweep K / V
         # projections with exact (float64-folded, pair-packed) weights -- on the eight classifier goldens "fp16sd" moves from
         # 8.3e-4 / 1.72e-3 (fails the trained-like one) to 7.7e-4 / 9.0e-4, the multimodal model under "fp16/fp16x3f" from
         # 9.7e-4 / 1.06e-3 to 5.4e-4 / 5.6e-4, the flow forward from 5.66 to 5.42 ms.  Under the split-weight policies the
@@ -178,7 +176,7 @@ class Attention(_HipModule):
         # the split-operand ("x3f") decoder.
         kin = self.proj_k.in_features
         if H == 1 and kin == self.proj_v.in_features and dk == kin and dv == kin and (
-                wlevel == 0 or os.environ.get("PIO_KV_FOLD_ANY") == "1"):   # (env: A/B experiments, tools/)
+                R.kv_fold_offered() or os.environ.get("PIO_KV_FOLD_ANY") == "1"):   # (env: A/B experiments, tools/)
             with torch.no_grad():
                 Wk, Wv, Wo = wt(self.proj_k).double(), wt(self.proj_v).double(), wt(self.final).double()
                 bv = self.proj_v.bias.double() if self.proj_v.bias is not None else torch.zeros(kin, device=Wv.device)
@@ -190,18 +188,17 @@ class Attention(_HipModule):
             d.kq, d.vo = kq.desc, vo.desc
             keep += [kq, vo]
         if self.proj_q.in_features == self.proj_k.in_features and not split:
-            qk = R.PackedStack([(wt(self.proj_q), self.proj_q.bias), (wt(self.proj_k), self.proj_k.bias)],
-                               H, dtype, two)
+            pq, pk, pv = ((wt(lin), lin.bias) for lin in (self.proj_q, self.proj_k, self.proj_v))
+            qk = R.PackedStack([pq, pk], H, dtype, [q_two, k_two])
             d.qk = qk.desc
             keep.append(qk)
             # q | k | v in one image when the fused attention kernel can read V row-major (the head widths it covers).
             # Under "x2s" / "x2w" the V rows alone carry a lo image (pio_linear_t.lo_row0): the wide GEMM kernel runs
             # its second K sweep for those columns only -- the library takes such an image inside the LayerNorm fold.
-            if (wlevel <= 2 and not two and self.proj_v.in_features == self.proj_q.in_features
+            if (R.qkv_stack_allowed() and self.proj_v.in_features == self.proj_q.in_features
                     and (R.pad8(dk), R.pad8(dv)) in FUSED_SELF_HEADS
                     and (not v_two or (2 * H * R.pad8(dk)) % 256 == 0)):
-                qkv = R.PackedStack([(wt(self.proj_q), self.proj_q.bias), (wt(self.proj_k), self.proj_k.bias),
-                                     (wt(self.proj_v), self.proj_v.bias)], H, dtype, [False, False, v_two])
+                qkv = R.PackedStack([pq, pk, pv], H, dtype, [False, False, v_two])
                 d.qkv = qkv.desc
                 keep.append(qkv)
         return d, keep
@@ -246,12 +243,10 @@ class MLP(_HipModule):
         self.dropout = nn.Dropout(dropout_prob)
 
     def _build_desc(self, ov=None):
-        dtype, wlevel, split = R.policy_dtype()
-        two = wlevel >= 2
-        fine = R.policy_fine_split()
+        dtype, split = R.policy_dtype()
         wt = (lambda lin: ov[lin]) if ov else (lambda lin: lin.weight)
-        f1 = R.PackedLinear(wt(self.fc1), self.fc1.bias, 1, 1, dtype, two or "fc1" in fine, n_channels=True)
-        f2 = R.PackedLinear(wt(self.fc2), self.fc2.bias, 1, 1, dtype, two or "fc2" in fine)
+        f1 = R.PackedLinear(wt(self.fc1), self.fc1.bias, 1, 1, dtype, R.splits("fc1"), n_channels=True)
+        f2 = R.PackedLinear(wt(self.fc2), self.fc2.bias, 1, 1, dtype, R.splits("fc2"))
         d = L.Mlp(f1.desc, f2.desc, self.fc1.in_features, self.fc1.out_features, self.fc2.out_features, dtype,
                   int(split))
         return d, [f1, f2]
@@ -319,7 +314,7 @@ class SelfAttention(_HipModule):
         return self._packed.get(R.param_key(*self._params()) + (nblk,), lambda: self._build_blocks(nblk), slot="blocks")
 
     def _build_blocks(self, nblk: int):
-        dtype, _wlevel, _split = R.policy_dtype()
+        dtype = R.policy().dtype
         att, mlp = self.attention, self.mlp
         lins = (att.proj_q, att.proj_k, att.proj_v, att.final, mlp.fc1, mlp.fc2)
         descs, keep = [], []
@@ -342,10 +337,10 @@ class SelfAttention(_HipModule):
         W' = W * gamma, c = rowsum(W' as packed), b' = W beta + b (reference :281-292 computes LN then Linear).
         Offered for blocks of 512 / 768 / 1024 / 1280 / 1536 channels (widening factor 1) under the single-sweep policies;
         the library decides per call."""
-        dtype, wlevel, split = R.policy_dtype()
+        dtype = R.policy().dtype
         att, mlp = self.attention, self.mlp
         C_ = self._in_channels
-        if (wlevel > 2 or split or C_ % 256 or not 512 <= C_ <= 1536 or not a.qkv.w_hi
+        if (not R.ln_fold_offered() or C_ % 256 or not 512 <= C_ <= 1536 or not a.qkv.w_hi
                 or mlp.fc1.in_features != C_ or mlp.fc1.out_features != C_ or att.proj_q.in_features != C_):
             return
         with torch.no_grad():
@@ -360,10 +355,9 @@ class SelfAttention(_HipModule):
                 return wg.contiguous(), (w @ b + bias).contiguous()
 
             H = att._num_heads
-            # (the split levels of the un-folded descriptors: proj_v from "x2s" on, fc1 from "x2w" on)
             qkv = R.PackedStack([folded(att.proj_q, g1, b1), folded(att.proj_k, g1, b1), folded(att.proj_v, g1, b1)],
-                                H, dtype, [False, False, wlevel >= 1 or "proj_v" in R.policy_fine_split()])
-            fc1 = R.PackedLinear(*folded(mlp.fc1, g2, b2), 1, 1, dtype, wlevel >= 2, n_channels=True)
+                                H, dtype, [False, False, R.splits("proj_v")])
+            fc1 = R.PackedLinear(*folded(mlp.fc1, g2, b2), 1, 1, dtype, R.splits("fc1"), n_channels=True)
             # c[n] = sum_k of the packed weights the GEMM actually multiplies with: hi (+ lo where there is one)
             qkv_c = (qkv.hi.float() + (qkv.lo.float() if qkv.lo is not None else 0)).sum(1).contiguous()
             fc1_c = (fc1.hi.float() + (fc1.lo.float() if fc1.lo is not None else 0)).sum(1).contiguous()

@@ -21,12 +21,9 @@ static const void *W = (const void *)(uintptr_t)0x10000000;   // a fake, aligned
 static char *const BASE = (char *)(uintptr_t)0x40000000;      // the fake workspace
 
 // ---- descriptors as the Python front end packs them (runtime.py PackedLinear / PackedStack, _POLICIES) ---------------
-struct Policy { int wlevel; bool split; int act_split; bool fine_v, fine_o, fine_final; };
-static const Policy FP16 = {0, false, 0, false, false, false}, X2O = {0, false, 0, false, true, false},
-                    X2S = {1, false, 0, false, false, false}, X2W = {2, false, 0, false, false, false},
-                    X2AF = {0, true, 2, false, false, false}, X2AFO = {0, true, 2, false, true, true},
-                    X3 = {3, true, 1, false, false, false}, X3F = {3, true, 2, false, false, false},
-                    X3FQ = {3, true, 3, false, false, false};
+// (one constant per policy the cases use, written by _policies_cpp() from the answers of runtime.py itself)
+struct Policy { bool q, k, v, o, fc1, fc2, final_layer, split; int act_split; bool kv_fold, ln_fold, qkv_stack; };
+@POLICIES@
 static pio_linear_t lin(int n, int k, bool two, int lo_row0 = 0) {
     pio_linear_t l = {};
     l.w_hi = W; l.w_lo = two ? W : nullptr; l.n = n; l.k = k; l.lo_row0 = two ? lo_row0 : 0;
@@ -36,20 +33,19 @@ static pio_linear_t lin(int n, int k, bool two, int lo_row0 = 0) {
 static pio_attention_t attn(const Policy &p, int H, int q_in, int kv_in, int qk, int v, int out) {
     pio_attention_t a = {};
     const int dk = qk / H, dv = v / H, dkp = pad8(dk), dvp = pad8(dv);
-    const bool two = p.wlevel >= 3, v_two = p.wlevel >= 1 || p.fine_v, o_two = p.wlevel >= 1 || p.fine_o;
     a.heads = H; a.dk = dk; a.dv = dv; a.dkp = dkp; a.dvp = dvp; a.q_in = q_in; a.k_in = a.v_in = kv_in; a.out = out;
     a.dtype = PIO_DT_F16; a.act_split = p.act_split;
-    a.q = lin(H * dkp, padc(q_in), two); a.k = lin(H * dkp, padc(kv_in), two); a.v = lin(H * dvp, padc(kv_in), v_two);
-    a.o = lin(pad8(out), H * dvp, o_two);
-    if (H == 1 && dk == kv_in && dv == kv_in && p.wlevel == 0) {   // K / V projection fold offered
+    a.q = lin(H * dkp, padc(q_in), p.q); a.k = lin(H * dkp, padc(kv_in), p.k); a.v = lin(H * dvp, padc(kv_in), p.v);
+    a.o = lin(pad8(out), H * dvp, p.o);
+    if (H == 1 && dk == kv_in && dv == kv_in && p.kv_fold) {   // K / V projection fold offered
         a.kq = lin(pad8(kv_in), pad8(qk), true); a.vo = lin(pad8(out), pad8(kv_in), true);
     }
     if (q_in == kv_in && !p.split) {
-        a.qk = lin(2 * H * dkp, padc(q_in), two);
+        a.qk = lin(2 * H * dkp, padc(q_in), p.q && p.k);
         const bool fused_head = (dkp == 128 && dvp == 128) || (dkp == 64 && dvp == 64) || (dkp == 32 && dvp == 32) ||
                                 (dkp == 32 && dvp == 160);       // FUSED_SELF_HEADS
-        if (p.wlevel <= 2 && !two && fused_head && (!v_two || (2 * H * dkp) % 256 == 0))
-            a.qkv = lin(2 * H * dkp + H * dvp, padc(q_in), v_two, 2 * H * dkp);
+        if (p.qkv_stack && fused_head && (!p.v || (2 * H * dkp) % 256 == 0))
+            a.qkv = lin(2 * H * dkp + H * dvp, padc(q_in), p.v, 2 * H * dkp);
     }
     return a;
 }
@@ -57,7 +53,7 @@ static pio_attention_t attn(const Policy &p, int H, int q_in, int kv_in, int qk,
 static pio_mlp_t mlp(const Policy &p, int in, int widening, int out) {
     pio_mlp_t m = {};
     m.in = in; m.hidden = widening * in; m.out = out; m.dtype = PIO_DT_F16; m.act_split = p.split;
-    m.fc1 = lin(padc(m.hidden), padc(in), p.wlevel >= 2); m.fc2 = lin(pad8(out), padc(m.hidden), p.wlevel >= 2);
+    m.fc1 = lin(padc(m.hidden), padc(in), p.fc1); m.fc2 = lin(pad8(out), padc(m.hidden), p.fc2);
     return m;
 }
 // SelfAttention._build_desc + _build_ln_fold
@@ -66,9 +62,9 @@ static pio_self_attention_t self_block(const Policy &p, int C, int H, int qk = 0
     qk = qk ? qk : C; v = v ? v : qk;
     sa.attn = attn(p, H, C, C, qk, v, v);
     sa.mlp = mlp(p, v, widening, v);
-    if (!(p.wlevel > 2 || p.split || C % 256 || C < 512 || C > 1536 || !sa.attn.qkv.w_hi || widening != 1 || v != C)) {
-        sa.fold.qkv = lin(sa.attn.qkv.n, padc(C), p.wlevel >= 1 || p.fine_v, 2 * H * sa.attn.dkp);
-        sa.fold.fc1 = lin(padc(C), padc(C), p.wlevel >= 2);
+    if (!(!p.ln_fold || C % 256 || C < 512 || C > 1536 || !sa.attn.qkv.w_hi || widening != 1 || v != C)) {
+        sa.fold.qkv = lin(sa.attn.qkv.n, padc(C), p.v, 2 * H * sa.attn.dkp);
+        sa.fold.fc1 = lin(padc(C), padc(C), p.fc1);
         sa.fold.qkv_c = sa.fold.fc1_c = (const float *)W;
     }
     return sa;
@@ -84,7 +80,7 @@ static pio_cross_attention_t cross_block(const Policy &p, int q_in, int kv_in, i
     return ca;
 }
 // PerceiverDecoder._final_desc: nn.Linear(query channels, outputs)
-static pio_linear_t final_layer(const Policy &p, int q_c, int out) { return lin(pad8(out), padc(q_c), p.wlevel >= 2 || p.fine_final); }
+static pio_linear_t final_layer(const Policy &p, int q_c, int out) { return lin(pad8(out), padc(q_c), p.final_layer); }
 
 // ---- printing ------------------------------------------------------------------------------------------------------
 static long long off(const void *p) { return p ? (long long)((const char *)p - BASE) : -1; }
@@ -691,12 +687,28 @@ ENCODER = {
 Y16 = {"no_final_layer": 0, "k_is_padc": 1, "k_is_pad8_only": 0, "switched_off": 0}
 
 
+POLICY_CONSTANTS = {"FP16": "fp16", "X2O": "fp16x2o", "X2S": "fp16x2s", "X2W": "fp16x2w", "X2AF": "fp16x2af",
+                    "X2AFO": "fp16x2afo", "X3": "fp16x3", "X3F": "fp16x3f", "X3FQ": "fp16x3fq"}
+
+
+def _policies_cpp():
+    """The driver's `Policy` constants, in the order of the struct's members."""
+    from perceiverio_pytorch_amd import runtime as R
+
+    def row(n):
+        vals = [R.splits(lin, n) for lin in ("proj_q", "proj_k", "proj_v", "final", "fc1", "fc2", "final_layer")]
+        vals += [R.policy(n).act_split, R.attention_act_split(n), R.kv_fold_offered(n), R.ln_fold_offered(n),
+                 R.qkv_stack_allowed(n)]
+        return "{" + ", ".join(str(int(v)) for v in vals) + "}"
+    return "static const Policy " + ", ".join(f"{c} = {row(n)}" for c, n in POLICY_CONSTANTS.items()) + ";"
+
+
 def _run_driver():
     inc = os.path.join(ROOT, "include")
     csrc = os.path.join(ROOT, "perceiverio_pytorch_amd", "csrc")
     with tempfile.TemporaryDirectory() as d:
         src = os.path.join(d, "route.cpp")
-        open(src, "w").write(DRIVER)
+        open(src, "w").write(DRIVER.replace("@POLICIES@", _policies_cpp()))
         exe = os.path.join(d, "route")
         subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", inc, "-I", csrc, src, "-o", exe])
         out = subprocess.check_output([exe]).decode().split("\n")

@@ -18,6 +18,7 @@ import numerics_model as NM  # noqa: E402
 import qk_pair_cases as QC  # noqa: E402
 
 TOL = 1e-3          # the project's bar (tests/test_parity_gpu.py, tests/test_models.py)
+NAMES = ("proj_q", "proj_k", "proj_v", "final", "fc1", "fc2", "final_layer", "post")    # the linears a policy can split
 
 
 def test_policy_is_known_through_every_selection_route():
@@ -30,8 +31,11 @@ def test_policy_is_known_through_every_selection_route():
         P.set_precision_policy(prev)
         with R.precision("fp16x3fq"):                                        # 2: the context manager
             assert R.get_precision_policy() == "fp16x3fq"
-            assert R.policy_dtype() == (L.PIO_DT_F16, 3, True) == R.policy_dtype("fp16x3f")   # GEMMs as under "fp16x3f"
-            assert R.policy_core_single() and R.policy_core_pair() and R.attention_act_split() == 3
+            assert R.policy_dtype() == (L.PIO_DT_F16, True) == R.policy_dtype("fp16x3f")      # GEMMs as under "fp16x3f":
+            assert R.policy().split == R.policy("fp16x3f").split == frozenset(NAMES)           # every weight a pair
+            assert all(R.splits(n) and R.splits(n, "fp16x3f") for n in NAMES)
+            assert R.policy()._replace(core="fused") == R.policy("fp16x3f")                    # the core alone differs
+            assert R.policy().core == "fused_pair" and R.attention_act_split() == 3
         assert R.get_precision_policy() == prev
     finally:
         P.set_precision_policy(prev)
@@ -43,7 +47,8 @@ def test_policy_is_known_through_every_selection_route():
     assert out.stdout.split() == ["fp16x3fq", "3"]
     # 4: any part of a model's "cross/stack/decoder" string
     assert M.split_policy3("fp16x3fq/fp16x2o/fp16x3fq") == ("fp16x3fq", "fp16x2o", "fp16x3fq")
-    assert "fp16x3fq" in R._FUSED_CORE and "bf16x3fq" not in R._POLICIES     # no bf16 pair core, no bf16 policy name
+    assert [n for n, p in R._POLICIES.items() if p.core == "fused_pair"] == ["fp16x3fq"]
+    assert "bf16x3fq" not in R._POLICIES                                     # no bf16 pair core, no bf16 policy name
     # the other policies map as before
     assert [R.attention_act_split(n) for n in ("fp16", "fp16x2w", "fp16x3", "fp16x3f", "fp16x2af", "bf16x3f")] == \
         [0, 0, 1, 2, 2, 2]

@@ -129,31 +129,26 @@ int main() {
 '''
 
 
-def _policy_facts(policy):
-    from perceiverio_pytorch_amd import runtime as R
-    dtype, wlevel, split = R.policy_dtype(policy)
-    return dtype, wlevel, split, R.attention_act_split(policy)
-
-
 def _attn_expr(policy, H, qk, v, q_in, kv_in, out):
     """The C++ expression of the descriptor Attention._build_desc packs (transformer_primitives.py)."""
+    from perceiverio_pytorch_amd import runtime as R
     from perceiverio_pytorch_amd.transformer_primitives import FUSED_SELF_HEADS
-    dtype, wlevel, split, act_split = _policy_facts(policy)
+    dtype, split = R.policy_dtype(policy)
     dk, dv = qk // H, v // H
     pad8 = lambda c: (c + 7) & ~7  # noqa: E731
-    two, v_two = wlevel >= 3, wlevel >= 1
-    kvf = H == 1 and dk == kv_in and dv == kv_in and wlevel == 0
+    v_two = R.splits("proj_v", policy)
+    kvf = H == 1 and dk == kv_in and dv == kv_in and R.kv_fold_offered(policy)
     has_qk = q_in == kv_in and not split
-    has_qkv = (has_qk and wlevel <= 2 and not two and (pad8(dk), pad8(dv)) in FUSED_SELF_HEADS
+    has_qkv = (has_qk and R.qkv_stack_allowed(policy) and (pad8(dk), pad8(dv)) in FUSED_SELF_HEADS
                and (not v_two or (2 * H * pad8(dk)) % 256 == 0))
-    return (f"attn({H}, {dk}, {dv}, {act_split}, {dtype}, {q_in}, {kv_in}, {out}, {int(has_qk)}, {int(has_qkv)}, "
-            f"{int(has_qkv and v_two)}, {int(kvf)})"), has_qkv
+    return (f"attn({H}, {dk}, {dv}, {R.attention_act_split(policy)}, {dtype}, {q_in}, {kv_in}, {out}, {int(has_qk)}, "
+            f"{int(has_qkv)}, {int(has_qkv and v_two)}, {int(kvf)})"), has_qkv
 
 
 def _fold_offered(policy, C, has_qkv):
     """SelfAttention._build_ln_fold (widening factor 1 throughout the table)."""
-    _dtype, wlevel, split, _ = _policy_facts(policy)
-    return not (wlevel > 2 or split or C % 256 or not 512 <= C <= 1536 or not has_qkv)
+    from perceiverio_pytorch_amd import runtime as R
+    return not (not R.ln_fold_offered(policy) or C % 256 or not 512 <= C <= 1536 or not has_qkv)
 
 
 def _lines(c):
