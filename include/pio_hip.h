@@ -272,16 +272,9 @@ int pio_ln_fold_enable(int on);
 int pio_gemm_kernel_override(int which);
 
 /* --- running on a part of the chip ----------------------------------------------------------------- */
-/* A stream whose kernels run only on the CUs whose bit is set in `mask` (`words` 32-bit words; bit i = CU i / 8 of
- * XCD i % 8 on MI355X, the layout of hipExtStreamCreateWithCUMask).  Two such streams with complementary masks run
- * two independent kernel chains side by side: one chain's HBM-bound epilogues overlap the other's MFMA main loops
- * (PerceiverEncoder.forward with PIO_CU_SPLIT=1 runs the two halves of a batch that way).  Destroy with
- * pio_stream_destroy. */
-int pio_stream_create_cu_mask(void **stream, const uint32_t *mask, uint32_t words);
-int pio_stream_destroy(void *stream);
 /* Process-wide (not thread-safe): the number of CUs the persistent GEMM kernels size their grids for; 0 (default) =
- * every CU of the device.  Set it to the population of a stream's CU mask around the calls that launch on that
- * stream.  Returns the previous value. */
+ * every CU of the device.  Set it to the population of a stream's CU mask (hipExtStreamCreateWithCUMask, the
+ * caller's own) around the calls that launch on that stream.  Returns the previous value. */
 int pio_set_cu_budget(int32_t n_cu);
 
 /* --- weight packing (one-off, after load_state_dict) ------------------------------------------ */

@@ -146,10 +146,9 @@ struct SelfPlan {
     // copy of x lives in x16
     void *x16b = nullptr, *lo_a = nullptr, *lo_b = nullptr;  // lo_*: x - x16 / x1 - x16b (the stream as a 16-bit pair)
     float *part_a = nullptr, *part_b = nullptr;
-    // inplace: the in-place residual stream of a folded stack, below (FoldKnobs.inplace).
     // lean: the caller never passes a full mask / bias / probability output (the encoder stack): no score buffers
     // when a fused kernel covers the block
-    size_t carve(void *base, const pio_self_attention_t &sa, int B, int N, bool inplace, bool lean = false) {
+    size_t carve(void *base, const pio_self_attention_t &sa, int B, int N, bool lean = false) {
         Carver c(base);
         const int64_t rows = (int64_t)B * N;
         const int cmax = padc(sa.attn.q_in) > padc(sa.mlp.in) ? padc(sa.attn.q_in) : padc(sa.mlp.in);
@@ -160,15 +159,14 @@ struct SelfPlan {
         if (sa.fold.qkv.w_hi && sa.fold.fc1.w_hi) {
             // The residual GEMMs (out, fc2) read the residual pair and write the result pair element for element from
             // the same lane (load, add, store), and their A operand is another array (attention output / hidden
-            // activations): the stream is updated IN PLACE -- one 16-bit pair instead of two ping-pong pairs, and the
+            // activations): the stream is updated IN PLACE -- one 16-bit pair (x16b = x16.hi, lo_b = lo_a), and the
             // hidden activations take the attention output's buffer (dead once the out projection has run).  Per layer
-            // at B = 32 the arrays in flight shrink from 288 MB (beyond the 256 MB Infinity Cache) to 192 MB.
-            x16b = inplace ? x16.hi : c.take((size_t)rows * cmax * 2);
-            lo_a = c.take((size_t)rows * cmax * 2);
-            lo_b = inplace ? lo_a : c.take((size_t)rows * cmax * 2);
+            // at B = 32 the arrays in flight are 192 MB (two ping-pong pairs: 288 MB, beyond the 256 MB Infinity Cache).
+            x16b = x16.hi;
+            lo_a = lo_b = c.take((size_t)rows * cmax * 2);
             part_a = (float *)c.take((size_t)rows * (cmax / 64 + 1) * 2 * 4);  // (up to one slot per 64 columns)
             part_b = (float *)c.take((size_t)rows * (cmax / 64 + 1) * 2 * 4);
-            if (inplace && !sa.mlp.act_split && !sa.attn.act_split &&
+            if (!sa.mlp.act_split && !sa.attn.act_split &&
                 (size_t)rows * padc(sa.mlp.hidden) <= (size_t)rows * sa.attn.heads * sa.attn.dvp)
                 h16.hi = core.o16.hi;
         }
@@ -222,7 +220,6 @@ struct DecoderPlan {
 struct FoldKnobs {  // every switch the fold consults, read by the caller (pio_blocks.hip: env, pio_ln_fold_enable, call opts)
     int choice;  // 0 off, 1 where it pays, 2 wherever offered
     int64_t wide_min_rows, small_min_rows, small_max_rows;  // row bounds of the two kernel families
-    bool inplace;  // SelfPlan::carve: one stream pair updated in place
 };
 
 struct SelfCall {  // what self_attention_run knows about one call, as plain facts
@@ -266,9 +263,9 @@ inline SelfFold self_fold_route(const pio_self_attention_t &sa, const SelfCall &
 }
 
 // A decoder with a final Linear: the cross-attend's result is only ever that Linear's operand, so fc2 writes it as 16-bit
-// rows directly (switch_on: PIO_DEC_Y16, read by the caller) when the packed image's K is the channel pitch of those rows.
-inline bool decoder_y16_direct(const pio_linear_t *final_layer, int q_c, bool switch_on) {
-    return final_layer && switch_on && final_layer->k == padc(q_c);
+// rows directly when the packed image's K is the channel pitch of those rows.
+inline bool decoder_y16_direct(const pio_linear_t *final_layer, int q_c) {
+    return final_layer && final_layer->k == padc(q_c);
 }
 
 }  // namespace pio

@@ -425,13 +425,6 @@ static Pair pair_if(Pair p, bool split) {
     return p;
 }
 
-// In-place residual stream of a folded self-attend stack (see SelfPlan::carve); PIO_FOLD_INPLACE=0 restores the two
-// ping-pong pairs (read at every carve: an A/B switch for tools/, not an API).
-static bool fold_inplace() {
-    const char *e = getenv("PIO_FOLD_INPLACE");
-    return !e || atoi(e) != 0;
-}
-
 // LayerNorm fold switch (pio_ln_fold_enable; initial value from env PIO_LN_FOLD, default 1).
 // 0: never, 1: where it pays, 2: wherever a block offers it.  "Where it pays": the fold's GEMMs are the 256 x 256-tile
 // kernel, which needs >= 96 tiles of a 1024-wide output to beat the 128 / 64-tile kernels of the un-folded block --
@@ -498,8 +491,7 @@ static int64_t ln_fold_small_max_rows() {
 }
 // Every switch of the fold as the plain values pio_block_route.h takes; filled once per C-ABI call (inside its CallOpts).
 static FoldKnobs fold_knobs() {
-    return FoldKnobs{ln_fold_choice(), ln_fold_min_rows(), ln_fold_small_min_rows(), ln_fold_small_max_rows(),
-                     fold_inplace()};
+    return FoldKnobs{ln_fold_choice(), ln_fold_min_rows(), ln_fold_small_min_rows(), ln_fold_small_max_rows()};
 }
 
 // Carried from one SelfAttention block to the next inside a stack: the 16-bit copy and the partial sums of the block's
@@ -699,7 +691,7 @@ int pio_ln_fold_enable(int on) { return ln_fold_enable(on); }
 size_t pio_self_attention_workspace_bytes(const pio_self_attention_t *sa, int32_t B, int32_t N) {
     if (!sa) return 0;
     SelfPlan p;
-    return p.carve(nullptr, *sa, B, N, fold_inplace());
+    return p.carve(nullptr, *sa, B, N);
 }
 
 int pio_self_attention_fwd(const pio_self_attention_t *sa, const pio_tensor3_t *x, const uint8_t *kv_mask,
@@ -717,7 +709,7 @@ int pio_self_attention_fwd_opts(const pio_self_attention_t *sa, const pio_tensor
     CallOpts scope(opts);
     const FoldKnobs knobs = fold_knobs();
     SelfPlan p;
-    if (p.carve(workspace, *sa, x->B, x->T, knobs.inplace) > workspace_bytes) return PIO_E_WORKSPACE;
+    if (p.carve(workspace, *sa, x->B, x->T) > workspace_bytes) return PIO_E_WORKSPACE;
     return self_attention_run(*sa, *x, kv_mask, q_mask, full_mask, attention_bias, out, probs_out, p, knobs,
                               (hipStream_t)stream);
 }
@@ -748,10 +740,9 @@ size_t pio_encoder_workspace_bytes(const pio_cross_attention_t *cross, const pio
     if (!cross) return 0;
     CrossPlan cp;
     size_t need = cp.carve(nullptr, *cross, B, N, M, false, true);
-    const bool inplace = fold_inplace();
     for (int l = 0; l < L; ++l) {
         SelfPlan sp;
-        const size_t n = sp.carve(nullptr, layers[l], B, N, inplace, true);
+        const size_t n = sp.carve(nullptr, layers[l], B, N, true);
         if (n > need) need = n;
     }
     return need;
@@ -810,7 +801,7 @@ int pio_encoder_fwd_opts(const pio_cross_attention_t *cross, const pio_self_atte
             // (per_block: block blk has its own IMAGES of the shared parameters -- same shapes -- at layers[blk * L + l])
             const pio_self_attention_t &lay = layers[(per_block ? (size_t)blk * L : 0) + l];
             SelfPlan sp;
-            sp.carve(workspace, lay, B, N, knobs.inplace, true);
+            sp.carve(workspace, lay, B, N, true);
             const bool last = blk == num_blocks - 1 && l == L - 1;
             PIO_TRY(self_attention_run(lay, z, nullptr, nullptr, nullptr, nullptr, out, nullptr, sp, knobs, s, &carry,
                                        last));
@@ -841,14 +832,6 @@ size_t pio_decoder_qcache_bytes(const pio_cross_attention_t *cross, int32_t Bq, 
     return (size_t)round_up((int64_t)Bq * Q * cross->attn.heads * cross->attn.dkp * 2, 256);
 }
 
-static bool dec_y16_enabled() {  // (env PIO_DEC_Y16, read once per process; see decoder_run)
-    static const bool on = [] {
-        const char *e = getenv("PIO_DEC_Y16");
-        return !e || atoi(e) != 0;
-    }();
-    return on;
-}
-
 static int decoder_run(const pio_cross_attention_t *cross, const pio_linear_t *final_layer, int32_t final_out,
                        const pio_tensor3_t *query, const pio_tensor3_t *query_tail, const pio_tensor3_t *latents,
                        const uint8_t *query_mask, float *out, void *workspace, size_t workspace_bytes, void *stream,
@@ -867,9 +850,8 @@ static int decoder_run(const pio_cross_attention_t *cross, const pio_linear_t *f
     // perceiver.py:172-177: mask[b,i,j] = query_mask[b,i]
     float *y = final_layer ? p.y : out;
     const int64_t y_ld = final_layer ? pitch4(q_c) : q_c;  // (y is internal when a final layer follows)
-    // (with a final Linear the cross-attend's result is only ever its operand: fc2 writes it as 16-bit rows directly --
-    //  env PIO_DEC_Y16=0: the fp32 rows + cast pass of rounds 1-3, for A/B)
-    const bool direct = decoder_y16_direct(final_layer, q_c, dec_y16_enabled());
+    // (with a final Linear the cross-attend's result is only ever its operand: fc2 writes it as 16-bit rows directly)
+    const bool direct = decoder_y16_direct(final_layer, q_c);
     PIO_TRY(cross_attention_run(*cross, *query, *latents, nullptr, query_mask, nullptr, nullptr, y, nullptr, p.cp,
                                 s, nullptr, y_ld, qc, direct ? &p.y16 : nullptr, query_tail));
     if (!final_layer) return PIO_OK;

@@ -63,19 +63,6 @@ int pio_set_cu_budget(int32_t n_cu) {
     return prev;
 }
 
-int pio_stream_create_cu_mask(void **stream, const uint32_t *mask, uint32_t words) {
-    if (!stream || !mask || words == 0) return PIO_E_ARG;
-    hipStream_t s = nullptr;
-    if (hipExtStreamCreateWithCUMask(&s, words, mask) != hipSuccess) return PIO_E_LAUNCH;
-    *stream = (void *)s;
-    return PIO_OK;
-}
-
-int pio_stream_destroy(void *stream) {
-    if (!stream) return PIO_E_ARG;
-    return hipStreamDestroy((hipStream_t)stream) == hipSuccess ? PIO_OK : PIO_E_LAUNCH;
-}
-
 int pio_prof_begin(int32_t max_records) {
     if (max_records <= 0) return PIO_E_ARG;
     while (g_prof.ev.size() < (size_t)2 * max_records) {

@@ -8,7 +8,6 @@ The fused paths around them (_assemble, _fused_decoder_query, _project_heads) ar
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import torch
 import torch.nn as nn
@@ -117,45 +116,20 @@ class PerceiverEncoder(R.PackedOwner):
 
         layers = self._packed.get((tuple(id(d) for ds in descs for d in ds), flag.data_ptr() if guard else 0), build_layers)
 
-        def launch(xs, tail, zs, mask_ptr, out_ptr, blockwise, opts, stream=None):
-            """One pio_encoder_fwd_opts call on the current stream's workspace (the whole batch, or one batch slice)."""
+        def launch(xs, tail, zs, mask_ptr, out_ptr, blockwise, opts):
+            """One pio_encoder_fwd_opts call on the current stream's workspace."""
             LP.expect("cross", *["stack"] * (Lyr * self._num_blocks))    # (one attention call per block, this order)
             LP.mark_range("cross")           # (range probe: the library marks "stack" behind the cross-attend itself)
             try:
                 ws = R.workspace(dev, lib.pio_encoder_workspace_bytes(cross, layers, Lyr, xs.shape[0], M, N))
                 R.call(dev, "pio_encoder_fwd_opts", cross, layers, Lyr, self._num_blocks, blockwise, R.tensor3(xs), tail,
-                       R.tensor3(zs), mask_ptr, out_ptr, ws.data_ptr(), ws.numel(), stream=stream, tail=(opts,),
+                       R.tensor3(zs), mask_ptr, out_ptr, ws.data_ptr(), ws.numel(), tail=(opts,),
                        what="pio_encoder_fwd")
             finally:
                 LP.mark_range("attention")
 
-        nsplit = R.batch_streams()
-        if nsplit <= 1 or B < 2 * nsplit or B % nsplit or inputs_tail is not None or per_block:
-            # (the un-folded repeat of the range guard is a PER-CALL option: no process state changes around the call)
-            launch(x, tail3, z0, im_ptr, out.data_ptr(), int(per_block), L.CallOpts(1 if self._range_fallback else 0, 0))
-            return self._finish(out, flag, inputs, inputs_tail, latents, input_mask)
-        # Samples are independent: run `nsplit` batch slices as independent kernel chains on side streams so that
-        # one chain's fill / drain / HBM-bound kernels overlap the other's MFMA-bound ones (each slice still fills
-        # >= half of the CUs).  Every slice has its own workspace; the current stream waits for all of them.
-        cur = torch.cuda.current_stream(dev)
-        bs = B // nsplit
-        # (PIO_CU_BUDGET_ONLY=1, experiment: plain streams, but persistent grids sized for a 1/nsplit share of the chip)
-        masked = (R.cu_split() or os.environ.get("PIO_CU_BUDGET_ONLY") == "1") and 32 % nsplit == 0
-        # (the CU share of a masked stream travels with the call: pio_call_opts_t.cu_budget, not the process-wide setting)
-        opts = L.CallOpts(1 if self._range_fallback else 0, R.cu_share(nsplit) if masked else 0)
-        sides = R.side_streams(dev, nsplit)
-        for side in sides:                   # every slice starts behind the work already queued on `cur` ...
-            side.wait_stream(cur)
-        for i, side in enumerate(sides):
-            with torch.cuda.stream(side):
-                launch(x[i * bs:(i + 1) * bs], None, z0[i * bs:(i + 1) * bs],
-                       im_ptr + i * bs * M if im_ptr is not None else None, out[i * bs:(i + 1) * bs].data_ptr(), 0, opts,
-                       stream=side.cuda_stream)
-        for side in sides:                   # ... and `cur` continues behind ALL of them (a wait queued between
-            cur.wait_stream(side)            # two slices would chain them one after the other)
-        for t in (x, z0, out):
-            for side in R.side_streams(dev, nsplit):
-                t.record_stream(side)
+        # (the un-folded repeat of the range guard is a PER-CALL option: no process state changes around the call)
+        launch(x, tail3, z0, im_ptr, out.data_ptr(), int(per_block), L.CallOpts(1 if self._range_fallback else 0, 0))
         return self._finish(out, flag, inputs, inputs_tail, latents, input_mask)
 
     _range_fallback = False   # True while the call is being repeated un-folded (the guard's fallback)

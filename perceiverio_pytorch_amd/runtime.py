@@ -371,88 +371,6 @@ def release_workspaces() -> None:
 
 
 # ------------------------------------------------------------------------------------------------
-# optional batch-slice streams for the encoder stack (PIO_STREAMS=k, default 1 = off)
-# ------------------------------------------------------------------------------------------------
-_nstreams = max(1, int(os.environ.get("PIO_STREAMS", "1")))
-_side_streams: Dict[Tuple[int, int], list] = {}
-
-
-def batch_streams() -> int:
-    return _nstreams
-
-
-def set_batch_streams(n: int) -> None:
-    global _nstreams
-    _nstreams = max(1, int(n))
-
-
-_cu_split = os.environ.get("PIO_CU_SPLIT", "0") == "1"
-
-
-def cu_split() -> bool:
-    return _cu_split
-
-
-def set_cu_split(on: bool) -> None:
-    """Batch-slice streams that each own a disjoint share of every XCD's CUs (pio_stream_create_cu_mask) instead of
-    plain streams: the slices' kernel chains then truly run side by side."""
-    global _cu_split
-    _cu_split = bool(on)
-    release_side_streams()
-
-
-_masked_cache: Dict[Tuple[int, int], list] = {}    # (device index, n) -> CU-masked streams, created ONCE and reused
-
-
-def release_side_streams() -> None:
-    """Forget the cached side streams.  CU-masked streams (raw HIP streams from pio_stream_create_cu_mask) are NOT
-    destroyed here: tensors that were record_stream()-ed on them keep the handle alive inside PyTorch's caching
-    allocator, and destroying it under the allocator crashes the process.  They are created once per (device, split) and
-    reused by every later toggle instead -- a bounded set, no leak."""
-    _side_streams.clear()
-
-
-def cu_share(n: int) -> int:
-    """CUs per slice when the chip is split `n` ways, from the device's own CU count (MI355X: 256 = 8 XCDs x 32)."""
-    try:
-        total = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
-    except Exception:  # noqa: BLE001
-        total = 256
-    return total // n
-
-
-def _masked_streams(device: torch.device, n: int) -> list:
-    """`n` streams with complementary CU masks: slice i owns CUs [i*32/n, (i+1)*32/n) of EVERY XCD (mask bit j is CU
-    j // 8 of XCD j % 8), so each slice keeps the round-robin dispatch over all eight L2s."""
-    lib = L.lib()
-    per = 32 // n
-    out = []
-    for i in range(n):
-        words = (C.c_uint32 * 8)()
-        for j in range(256):
-            if i * per <= j // 8 < (i + 1) * per:
-                words[j // 32] |= 1 << (j % 32)
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            L.check(lib.pio_stream_create_cu_mask(C.byref(h), words, 8), "pio_stream_create_cu_mask")
-        out.append(torch.cuda.ExternalStream(h.value, device=device))
-    return out
-
-
-def side_streams(device: torch.device, n: int) -> list:
-    key = (device.index if device.index is not None else torch.cuda.current_device(), n, _cu_split)
-    if key not in _side_streams:
-        if _cu_split and 32 % n == 0:
-            mk = (key[0], n)
-            if mk not in _masked_cache:
-                _masked_cache[mk] = _masked_streams(device, n)
-            _side_streams[key] = _masked_cache[mk]
-        else:
-            _side_streams[key] = [torch.cuda.Stream(device=device) for _ in range(n)]
-    return _side_streams[key]
-
-
-# ------------------------------------------------------------------------------------------------
 # packed weights
 # ------------------------------------------------------------------------------------------------
 class PackedLinear:

@@ -108,10 +108,10 @@ static void show_mlp(const char *id, const pio_mlp_t &m, int64_t rows) {
     pair("x16", p.x16); pair("h16", p.h16);
     printf("\n");
 }
-static void show_self(const char *id, const pio_self_attention_t &sa, int B, int N, bool inplace, bool lean) {
+static void show_self(const char *id, const pio_self_attention_t &sa, int B, int N, bool lean) {
     SelfPlan p, n;
-    const size_t total = p.carve(BASE, sa, B, N, inplace, lean);
-    printf("plan %s total=%zu null_base_total=%zu", id, total, n.carve(nullptr, sa, B, N, inplace, lean));
+    const size_t total = p.carve(BASE, sa, B, N, lean);
+    printf("plan %s total=%zu null_base_total=%zu", id, total, n.carve(nullptr, sa, B, N, lean));
     pair("x16", p.x16); pair("h16", p.h16);
     printf(" x1=%lld", off(p.x1));
     core(p.core, sa.attn, B, B, N, N);
@@ -138,17 +138,17 @@ static void show_decoder(const char *id, const pio_cross_attention_t &ca, const 
     printf("plan %s total=%zu null_base_total=%zu y=%lld", id, total, n.carve(nullptr, ca, fin, B, Q, N, qb), off(p.y));
     pair("y16", p.y16);
     cross_members(p.cp, ca, B, Q, N, qb);
-    printf(" pitch4=%d pad8=%d padc=%d y16_direct=%d y16_switched_off=%d\n", pitch4(ca.attn.q_in), pad8(ca.attn.q_in),
-           padc(ca.attn.q_in), decoder_y16_direct(fin, ca.attn.q_in, true), decoder_y16_direct(fin, ca.attn.q_in, false));
+    printf(" pitch4=%d pad8=%d padc=%d y16_direct=%d\n", pitch4(ca.attn.q_in), pad8(ca.attn.q_in), padc(ca.attn.q_in),
+           decoder_y16_direct(fin, ca.attn.q_in));
 }
 // pio_encoder_workspace_bytes' rule against what pio_encoder_fwd carves (latents broadcast over the batch or not)
 static void show_encoder(const char *id, const pio_cross_attention_t &ca, const pio_self_attention_t &sa, int B, int M,
-                         int N, bool inplace) {
+                         int N) {
     CrossPlan cp; SelfPlan sp;
     size_t rule = cp.carve(nullptr, ca, B, N, M, false, true);
-    const size_t n = sp.carve(nullptr, sa, B, N, inplace, true);
+    const size_t n = sp.carve(nullptr, sa, B, N, true);
     if (n > rule) rule = n;
-    const size_t run_self = sp.carve(BASE, sa, B, N, inplace, true);
+    const size_t run_self = sp.carve(BASE, sa, B, N, true);
     const size_t c0 = cp.carve(BASE, ca, B, N, M, false, true), c1 = cp.carve(BASE, ca, B, N, M, true, true);
     printf("encoder %s %zu %zu %zu\n", id, rule, c0 > run_self ? c0 : run_self, c1 > run_self ? c1 : run_self);
 }
@@ -161,41 +161,41 @@ static void plan_cases() {
     const pio_self_attention_t im_s = self_block(FP16, 1024, 8);
     const pio_linear_t im_f = final_layer(X2AF, 1024, 1000);
     show_cross("imagenet_cross", im_x, 32, 512, 3136, true, true);
-    show_self("imagenet_stack", im_s, 32, 512, true, true);
+    show_self("imagenet_stack", im_s, 32, 512, true);
     show_decoder("imagenet_decoder", im_d, &im_f, 32, 1000, 512, true);
-    show_encoder("imagenet", im_x, im_s, 32, 3136, 512, true);
+    show_encoder("imagenet", im_x, im_s, 32, 3136, 512);
     // language "fp16x2w/fp16x2o/fp16x3f": 2048 x 768 tokens, 256 x 1280 latents, 8 heads of (32, 160); decoder heads (32, 96)
     const pio_cross_attention_t la_x = cross_block(X2W, 1280, 768, 8, 256, 1280), la_d = cross_block(X3F, 768, 1280, 8, 256, 768, false);
     const pio_self_attention_t la_s = self_block(X2O, 1280, 8, 256, 1280);
     show_cross("language_cross", la_x, 100, 256, 2048, true, true);
-    show_self("language_stack", la_s, 100, 256, true, true);
+    show_self("language_stack", la_s, 100, 256, true);
     show_decoder("language_decoder", la_d, nullptr, 100, 2048, 256, false);
-    show_encoder("language", la_x, la_s, 100, 2048, 256, true);
+    show_encoder("language", la_x, la_s, 100, 2048, 256);
     // flow "fp16/fp16x2af": 182 528 x 322 pixels, 2048 x 512 latents, 16 heads of 32; the queries are the inputs
     const pio_cross_attention_t fl_x = cross_block(FP16, 512, 322, 1), fl_d = cross_block(X2AF, 322, 512, 1, 0, 0, false);
     const pio_self_attention_t fl_s = self_block(FP16, 512, 16);
     const pio_linear_t fl_f = final_layer(X2AF, 322, 2);
     show_cross("flow_cross", fl_x, 1, 2048, 182528, true, true);
-    show_self("flow_stack", fl_s, 1, 2048, true, true);
+    show_self("flow_stack", fl_s, 1, 2048, true);
     show_decoder("flow_decoder_322", fl_d, &fl_f, 1, 182528, 2048, false);
     show_decoder("flow_decoder_322_no_final", fl_d, nullptr, 1, 182528, 2048, false);
-    show_encoder("flow", fl_x, fl_s, 1, 182528, 2048, true);
+    show_encoder("flow", fl_x, fl_s, 1, 182528, 2048);
     // multimodal "fp16x2w/fp16x2afo": 52 097 x 704 inputs, 784 x 512 latents, 8 heads of 64, chunks of 6288 x 1026 queries
     const pio_cross_attention_t mm_x = cross_block(X2W, 512, 704, 1), mm_d = cross_block(X2AFO, 1026, 512, 1, 0, 0, false);
     const pio_self_attention_t mm_s = self_block(X2W, 512, 8);
     const pio_linear_t mm_f = final_layer(X2AFO, 1026, 512);
     show_cross("multimodal_cross", mm_x, 1, 784, 52097, true, true);
-    show_self("multimodal_stack", mm_s, 1, 784, true, true);
+    show_self("multimodal_stack", mm_s, 1, 784, true);
     show_decoder("multimodal_decoder_1026", mm_d, &mm_f, 1, 6288, 784, false);
     show_decoder("multimodal_decoder_1026_no_final", mm_d, nullptr, 1, 6288, 784, false);
-    show_encoder("multimodal", mm_x, mm_s, 1, 52097, 784, true);
+    show_encoder("multimodal", mm_x, mm_s, 1, 52097, 784);
 
     // act_split 0 / 1 / 2 / 3 on one small block of each kind
     const Policy *pol[4] = {&FP16, &X3, &X3F, &X3FQ};
     for (int s = 0; s < 4; ++s) {
         char id[64];
         snprintf(id, sizeof id, "self_512_act_split_%d", s);
-        show_self(id, self_block(*pol[s], 512, 16), 2, 256, true, false);
+        show_self(id, self_block(*pol[s], 512, 16), 2, 256, false);
         snprintf(id, sizeof id, "cross_act_split_%d", s);
         show_cross(id, cross_block(*pol[s], 256, 96, 8, 256, 256), 2, 128, 200, false, false);
         snprintf(id, sizeof id, "attention_act_split_%d", s);
@@ -205,25 +205,23 @@ static void plan_cases() {
     }
     show_attention("attention_v_apart_q_bcast", attn(FP16, 8, 256, 96, 256, 256, 256), 2, 128, 200, true, false);
     // lean on / off, q_bcast on / off
-    show_self("imagenet_stack_b1_not_lean", im_s, 1, 512, true, false);
-    show_self("imagenet_stack_b1_lean", im_s, 1, 512, true, true);
+    show_self("imagenet_stack_b1_not_lean", im_s, 1, 512, false);
+    show_self("imagenet_stack_b1_lean", im_s, 1, 512, true);
     show_cross("flow_cross_b2_small_not_lean", fl_x, 2, 256, 1000, false, false);
     show_cross("flow_cross_b2_small_lean", fl_x, 2, 256, 1000, false, true);
     show_cross("flow_cross_b2_small_lean_q_bcast", fl_x, 2, 256, 1000, true, true);
     show_decoder("imagenet_decoder_b2", im_d, &im_f, 2, 1000, 512, false);
     show_decoder("imagenet_decoder_b2_q_bcast", im_d, &im_f, 2, 1000, 512, true);
-    // inplace on / off (policy with split weights: the fold's buffers are carved all the same)
-    show_self("imagenet_stack_b4_inplace", im_s, 4, 512, true, true);
-    show_self("imagenet_stack_b4_ping_pong", im_s, 4, 512, false, true);
-    show_self("stack_x2w_1024_inplace", self_block(X2W, 1024, 8), 4, 512, true, true);
-    show_self("stack_x2w_1024_ping_pong", self_block(X2W, 1024, 8), 4, 512, false, true);
+    // the in-place stream (policy with split weights: the fold's buffers are carved all the same)
+    show_self("imagenet_stack_b4_inplace", im_s, 4, 512, true);
+    show_self("stack_x2w_1024_inplace", self_block(X2W, 1024, 8), 4, 512, true);
     // h16.hi == core.o16.hi at its edge: padc(hidden) == heads * dvp (1280 = 8 x 160) / greater (widening 4: no fold offered;
     // and a fold descriptor handed to a block whose hidden width is larger than its attention output)
-    show_self("alias_edge_hidden_equal", self_block(FP16, 1280, 8, 256, 1280), 2, 256, true, true);
+    show_self("alias_edge_hidden_equal", self_block(FP16, 1280, 8, 256, 1280), 2, 256, true);
     pio_self_attention_t wide_hidden = self_block(FP16, 1280, 8, 256, 1280);
     wide_hidden.mlp = mlp(FP16, 1280, 2, 1280);
-    show_self("alias_edge_hidden_greater", wide_hidden, 2, 256, true, true);
-    show_self("no_fold_offered_widening_4", self_block(FP16, 1024, 8, 0, 0, 4), 2, 256, true, true);
+    show_self("alias_edge_hidden_greater", wide_hidden, 2, 256, true);
+    show_self("no_fold_offered_widening_4", self_block(FP16, 1024, 8, 0, 0, 4), 2, 256, true);
 }
 
 static void chunk_cases() {   // score_chunks: all at once / whole samples per pass / row chunks of one sample
@@ -240,8 +238,8 @@ static void chunk_cases() {   // score_chunks: all at once / whole samples per p
 }
 
 // ---- the fold ------------------------------------------------------------------------------------------------------
-static const FoldKnobs MODE0 = {0, 6144, 512, 4096, true}, MODE1 = {1, 6144, 512, 4096, true},
-                       MODE2 = {2, 2048, 128, 4096, true};    // (mode 2: the caller lowers the bounds to 2048 / 128)
+static const FoldKnobs MODE0 = {0, 6144, 512, 4096}, MODE1 = {1, 6144, 512, 4096},
+                       MODE2 = {2, 2048, 128, 4096};    // (mode 2: the caller lowers the bounds to 2048 / 128)
 static SelfCall call_of(int B, int N, int C) {
     SelfCall c = {};
     c.B = B; c.N = N; c.C = C; c.stride_t = C; c.stride_b = (int64_t)N * C; c.x_aligned16 = c.has_fold_buffers = true;
@@ -333,10 +331,9 @@ static void fold_cases() {
 
 static void y16_cases() {
     const pio_linear_t k384 = lin(8, 384, false), k328 = lin(8, 328, false);
-    printf("y16 no_final_layer %d\n", decoder_y16_direct(nullptr, 322, true));
-    printf("y16 k_is_padc %d\n", decoder_y16_direct(&k384, 322, true));
-    printf("y16 k_is_pad8_only %d\n", decoder_y16_direct(&k328, 322, true));
-    printf("y16 switched_off %d\n", decoder_y16_direct(&k384, 322, false));
+    printf("y16 no_final_layer %d\n", decoder_y16_direct(nullptr, 322));
+    printf("y16 k_is_padc %d\n", decoder_y16_direct(&k384, 322));
+    printf("y16 k_is_pad8_only %d\n", decoder_y16_direct(&k328, 322));
 }
 
 int main() {
@@ -368,7 +365,7 @@ PLANS = {
         "core.q16.hi=722468864 core.q16.lo=724516864 core.k16.hi=726564864 core.k16.lo=760119296 "
         "core.vt16.hi=793673728 core.vt16.lo=827228160 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 "
         "core.o16.hi=860782592 core.o16.lo=926318592 core.xpart=991854592 split=1 qbytes=2048000 "
-        "kbytes=33554432 pitch4=1024 pad8=1024 padc=1024 y16_direct=1 y16_switched_off=0",
+        "kbytes=33554432 pitch4=1024 pad8=1024 padc=1024 y16_direct=1",
     "language_cross":
         "total=1271555072 null_base_total=1271555072 q16.hi=0 q16.lo=-1 kv16.hi=65536000 kv16.lo=-1 "
         "h16.hi=380108800 h16.lo=-1 x1=445644800 core.q16.hi=576716800 core.q16.lo=-1 core.k16.hi=576847872 "
@@ -386,7 +383,7 @@ PLANS = {
         "core.q16.hi=2018508800 core.q16.lo=2123366400 core.k16.hi=2228224000 core.k16.lo=2241331200 "
         "core.vt16.hi=2254438400 core.vt16.lo=2293760000 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 "
         "core.o16.hi=2333081600 core.o16.lo=2647654400 core.xpart=2962227200 split=1 qbytes=104857600 "
-        "kbytes=13107200 pitch4=768 pad8=768 padc=768 y16_direct=0 y16_switched_off=0",
+        "kbytes=13107200 pitch4=768 pad8=768 padc=768 y16_direct=0",
     "flow_cross":
         "total=434011136 null_base_total=434011136 q16.hi=0 q16.lo=-1 kv16.hi=2097152 kv16.lo=-1 "
         "h16.hi=142278656 h16.lo=-1 x1=144375808 core.q16.hi=148570112 core.q16.lo=-1 core.k16.hi=149913600 "
@@ -404,14 +401,14 @@ PLANS = {
         "core.q16.hi=1321316352 core.q16.lo=1508225024 core.k16.hi=1695133696 core.k16.lo=1697230848 "
         "core.vt16.hi=1699328000 core.vt16.lo=1701425152 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 "
         "core.o16.hi=1703522304 core.o16.lo=1890430976 core.xpart=2077339648 split=1 qbytes=186908672 "
-        "kbytes=2097152 pitch4=324 pad8=328 padc=384 y16_direct=1 y16_switched_off=0",
+        "kbytes=2097152 pitch4=324 pad8=328 padc=384 y16_direct=1",
     "flow_decoder_322_no_final":
         "total=1560420608 null_base_total=1560420608 y=-1 y16.hi=-1 y16.lo=-1 q16.hi=0 q16.lo=140181504 "
         "kv16.hi=280363008 kv16.lo=282460160 h16.hi=284557312 h16.lo=424738816 x1=564920320 "
         "core.q16.hi=804397056 core.q16.lo=991305728 core.k16.hi=1178214400 core.k16.lo=1180311552 "
         "core.vt16.hi=1182408704 core.vt16.lo=1184505856 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 "
         "core.o16.hi=1186603008 core.o16.lo=1373511680 core.xpart=1560420352 split=1 qbytes=186908672 "
-        "kbytes=2097152 pitch4=324 pad8=328 padc=384 y16_direct=0 y16_switched_off=0",
+        "kbytes=2097152 pitch4=324 pad8=328 padc=384 y16_direct=0",
     "multimodal_cross":
         "total=254310144 null_base_total=254310144 q16.hi=0 q16.lo=-1 kv16.hi=802816 kv16.lo=-1 "
         "h16.hi=74155520 h16.lo=-1 x1=74958336 core.q16.hi=76563968 core.q16.lo=-1 core.k16.hi=77667840 "
@@ -429,14 +426,14 @@ PLANS = {
         "core.q16.hi=135514880 core.q16.lo=141953792 core.k16.hi=148392704 core.k16.lo=149195520 "
         "core.vt16.hi=149998336 core.vt16.lo=150817536 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 "
         "core.o16.hi=151636736 core.o16.lo=158075648 core.xpart=164514560 split=1 qbytes=6438912 "
-        "kbytes=802816 pitch4=1028 pad8=1032 padc=1088 y16_direct=1 y16_switched_off=0",
+        "kbytes=802816 pitch4=1028 pad8=1032 padc=1088 y16_direct=1",
     "multimodal_decoder_1026_no_final":
         "total=150078208 null_base_total=150078208 y=-1 y16.hi=-1 y16.lo=-1 q16.hi=0 q16.lo=13682688 "
         "kv16.hi=27365376 kv16.lo=28168192 h16.hi=28971008 h16.lo=42653696 x1=56336384 core.q16.hi=82293248 "
         "core.q16.lo=88732160 core.k16.hi=95171072 core.k16.lo=95973888 core.vt16.hi=96776704 "
         "core.vt16.lo=97595904 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 core.o16.hi=98415104 "
         "core.o16.lo=104854016 core.xpart=111292928 split=1 qbytes=6438912 kbytes=802816 pitch4=1028 "
-        "pad8=1032 padc=1088 y16_direct=0 y16_switched_off=0",
+        "pad8=1032 padc=1088 y16_direct=0",
     "self_512_act_split_0":
         "total=17375488 null_base_total=17375488 x16.hi=0 x16.lo=-1 h16.hi=16252928 h16.lo=-1 x1=1048576 "
         "core.q16.hi=2097152 core.q16.lo=-1 core.k16.hi=2621440 core.k16.lo=-1 core.vt16.hi=3145728 "
@@ -553,38 +550,26 @@ PLANS = {
         "core.q16.hi=45154304 core.q16.lo=49250304 core.k16.hi=53346304 core.k16.lo=55443456 "
         "core.vt16.hi=57540608 core.vt16.lo=59637760 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 "
         "core.o16.hi=61734912 core.o16.lo=65830912 core.xpart=69926912 split=1 qbytes=4096000 kbytes=2097152 "
-        "pitch4=1024 pad8=1024 padc=1024 y16_direct=1 y16_switched_off=0",
+        "pitch4=1024 pad8=1024 padc=1024 y16_direct=1",
     "imagenet_decoder_b2_q_bcast":
         "total=65831168 null_base_total=65831168 y=0 y16.hi=8192000 y16.lo=12288000 q16.hi=16384000 "
         "q16.lo=20480000 kv16.hi=24576000 kv16.lo=26673152 h16.hi=28770304 h16.lo=32866304 x1=36962304 "
         "core.q16.hi=45154304 core.q16.lo=47202304 core.k16.hi=49250304 core.k16.lo=51347456 "
         "core.vt16.hi=53444608 core.vt16.lo=55541760 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 "
         "core.o16.hi=57638912 core.o16.lo=61734912 core.xpart=65830912 split=1 qbytes=2048000 kbytes=2097152 "
-        "pitch4=1024 pad8=1024 padc=1024 y16_direct=1 y16_switched_off=0",
+        "pitch4=1024 pad8=1024 padc=1024 y16_direct=1",
     "imagenet_stack_b4_inplace":
         "total=55345920 null_base_total=55345920 x16.hi=0 x16.lo=-1 h16.hi=29360128 h16.lo=-1 x1=8388608 "
         "core.q16.hi=16777216 core.q16.lo=-1 core.k16.hi=20971520 core.k16.lo=-1 core.vt16.hi=25165824 "
         "core.vt16.lo=-1 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 core.o16.hi=29360128 core.o16.lo=-1 "
         "core.xpart=33554432 split=0 qbytes=4194304 kbytes=4194304 x16b=0 lo_a=50594560 lo_b=50594560 "
         "part_a=54788864 part_b=55067392",
-    "imagenet_stack_b4_ping_pong":
-        "total=63734528 null_base_total=63734528 x16.hi=0 x16.lo=-1 h16.hi=4194304 h16.lo=-1 x1=8388608 "
-        "core.q16.hi=16777216 core.q16.lo=-1 core.k16.hi=20971520 core.k16.lo=-1 core.vt16.hi=25165824 "
-        "core.vt16.lo=-1 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 core.o16.hi=29360128 core.o16.lo=-1 "
-        "core.xpart=33554432 split=0 qbytes=4194304 kbytes=4194304 x16b=50594560 lo_a=54788864 lo_b=58983168 "
-        "part_a=63177472 part_b=63456000",
     "stack_x2w_1024_inplace":
         "total=55345920 null_base_total=55345920 x16.hi=0 x16.lo=-1 h16.hi=29360128 h16.lo=-1 x1=8388608 "
         "core.q16.hi=16777216 core.q16.lo=-1 core.k16.hi=20971520 core.k16.lo=-1 core.vt16.hi=25165824 "
         "core.vt16.lo=-1 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 core.o16.hi=29360128 core.o16.lo=-1 "
         "core.xpart=33554432 split=0 qbytes=4194304 kbytes=4194304 x16b=0 lo_a=50594560 lo_b=50594560 "
         "part_a=54788864 part_b=55067392",
-    "stack_x2w_1024_ping_pong":
-        "total=63734528 null_base_total=63734528 x16.hi=0 x16.lo=-1 h16.hi=4194304 h16.lo=-1 x1=8388608 "
-        "core.q16.hi=16777216 core.q16.lo=-1 core.k16.hi=20971520 core.k16.lo=-1 core.vt16.hi=25165824 "
-        "core.vt16.lo=-1 core.scores=-1 core.p16.hi=-1 core.p16.lo=-1 core.o16.hi=29360128 core.o16.lo=-1 "
-        "core.xpart=33554432 split=0 qbytes=4194304 kbytes=4194304 x16b=50594560 lo_a=54788864 lo_b=58983168 "
-        "part_a=63177472 part_b=63456000",
     "alias_edge_hidden_equal":
         "total=9871616 null_base_total=9871616 x16.hi=0 x16.lo=-1 h16.hi=7077888 h16.lo=-1 x1=2621440 "
         "core.q16.hi=5242880 core.q16.lo=-1 core.k16.hi=5505024 core.k16.lo=-1 core.vt16.hi=5767168 "
@@ -684,7 +669,7 @@ ENCODER = {
     "multimodal": (254310144, 254310144, 254310144),
 }
 
-Y16 = {"no_final_layer": 0, "k_is_padc": 1, "k_is_pad8_only": 0, "switched_off": 0}
+Y16 = {"no_final_layer": 0, "k_is_padc": 1, "k_is_pad8_only": 0}
 
 
 POLICY_CONSTANTS = {"FP16": "fp16", "X2O": "fp16x2o", "X2S": "fp16x2s", "X2W": "fp16x2w", "X2AF": "fp16x2af",
@@ -791,16 +776,13 @@ def test_q16_k16_vt16_are_adjacent():
 
 def test_in_place_aliases():
     """The in-place residual stream: x16b is x16.hi, lo_b is lo_a, and the hidden activations take the attention output's
-    buffer when they fit (padc(hidden) <= heads * dvp); the ping-pong layout keeps them apart."""
+    buffer when they fit (padc(hidden) <= heads * dvp)."""
     p = {k: _members(v) for k, v in _got()["plan"].items()}
     for name in ("imagenet_stack_b4_inplace", "stack_x2w_1024_inplace", "alias_edge_hidden_equal"):
         m = p[name]
         assert m["x16b"] == m["x16.hi"] and m["lo_b"] == m["lo_a"] and m["h16.hi"] == m["core.o16.hi"], name
     m = p["alias_edge_hidden_greater"]
     assert m["x16b"] == m["x16.hi"] and m["lo_b"] == m["lo_a"] and m["h16.hi"] != m["core.o16.hi"]
-    for name in ("imagenet_stack_b4_ping_pong", "stack_x2w_1024_ping_pong"):
-        m = p[name]
-        assert len({m["x16b"], m["x16.hi"], m["lo_a"], m["lo_b"], m["h16.hi"], m["core.o16.hi"]}) == 6, name
     assert p["no_fold_offered_widening_4"]["x16b"] == -1
 
 

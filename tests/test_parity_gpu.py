@@ -1125,32 +1125,6 @@ def test_backward_through_hip_modules_raises(dev):
     assert all(p.grad is None for p in m.parameters())
 
 
-@pytest.mark.parametrize("masked", [False, True])
-def test_encoder_batch_slice_streams_match_single_stream(dev, masked):
-    """PerceiverEncoder.forward with the batch cut into two slices on side streams (runtime.set_batch_streams(2); plain
-    streams or CU-masked ones) gives the single-stream result."""
-    from perceiverio_pytorch_amd import runtime as R
-    from perceiverio_pytorch_amd.perceiver import PerceiverEncoder
-    cfg = ENCDEC_CASES["encdec_mid"]
-    p_enc, _, _, x, _, _ = gen_encdec_inputs("encdec_mid", cfg, 21)
-    enc = PerceiverEncoder(cfg["C"], cfg["L"], cfg["blocks"], cfg["N"], cfg["D"], num_cross_attend_heads=cfg["xh"],
-                           num_self_attend_heads=cfg["sh"])
-    enc.load_state_dict(_sd(p_enc, "cpu"))
-    enc = enc.to(dev).eval()
-    xt = _t(np.concatenate([x, x[::-1]], axis=0), dev)          # B = 4: two slices of two samples
-    _policy("fp16x3")
-    try:
-        z1 = enc(xt, enc.latents(xt))
-        R.set_batch_streams(2)
-        R.set_cu_split(masked)
-        z2 = enc(xt, enc.latents(xt))
-        torch.cuda.synchronize()
-    finally:
-        R.set_batch_streams(1)
-        R.set_cu_split(False)
-    _assert_close(z2, z1.cpu().numpy(), 1e-5, what=f"2 batch-slice streams (cu masks: {masked})")
-
-
 # ----------------------------------------------------------------------------------------------------
 # fused cross-attention kernel (pio_xattn.hip): mask VECTORS, wide single heads, dv != dk, key splits
 # ----------------------------------------------------------------------------------------------------

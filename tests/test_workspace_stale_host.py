@@ -93,7 +93,7 @@ static void cross_entry(const char *id, const pio_attention_t &a, AttnCall c, in
         fin.w_hi = W; fin.k = final_k;
         DecoderPlan p;
         p.carve(BASE, ca, final_k ? &fin : nullptr, c.B, c.Tq, c.Tk, c.q_bcast);
-        printf("y16 %s %d\n", id, (int)decoder_y16_direct(final_k ? &fin : nullptr, a.q_in, true));
+        printf("y16 %s %d\n", id, (int)decoder_y16_direct(final_k ? &fin : nullptr, a.q_in));
         route(id, a, p.cp.core, c);
         return;
     }
@@ -112,9 +112,9 @@ static void self_entry(const char *id, const pio_attention_t &a, int B, int N, i
         sa.fold.qkv.n = a.qkv.n; sa.fold.qkv.k = C; sa.fold.fc1.n = sa.mlp.fc1.n; sa.fold.fc1.k = C;
     }
     const int choice = ln_fold > 0 ? ln_fold - 1 : 1;
-    const FoldKnobs knobs{choice, choice == 2 ? 2048 : 6144, choice == 2 ? 128 : 512, 4096, true};
+    const FoldKnobs knobs{choice, choice == 2 ? 2048 : 6144, choice == 2 ? 128 : 512, 4096};
     SelfPlan p;
-    p.carve(BASE, sa, B, N, knobs.inplace, lean);
+    p.carve(BASE, sa, B, N, lean);
     SelfCall sc = {};
     sc.B = B; sc.N = N; sc.C = C; sc.stride_t = C; sc.stride_b = (int64_t)N * C; sc.x_aligned16 = true;
     sc.has_fold_buffers = p.x16b != nullptr;

@@ -1,7 +1,7 @@
 """Dev tool (GPU): in-process A/B of library switches that are read from the environment at every call
 (cdna_hip_programming.md rule 24: interleaved rounds in ONE process, median and min per arm).
 
-    python tools/ab_env.py PIO_FOLD_INPLACE=0 PIO_FOLD_INPLACE=1 [--config imagenet] [--policy fp16sd] [--rounds 7]
+    python tools/ab_env.py PIO_KV_FOLD=0 PIO_KV_FOLD=1 [--config imagenet] [--policy fp16sd] [--rounds 7]
 
 Each arm is a comma-separated list of NAME=VALUE settings applied with os.environ before the arm's forwards.  Prints ms per
 forward (eager launches, HIP events on the launch stream) and whether the arms' outputs are bit-identical.
