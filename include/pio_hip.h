@@ -570,6 +570,47 @@ int pio_flow_blend_tiles(const pio_flow_blend_t *p, float *out, int64_t on, int6
 int pio_flow_to_image(const float *flow, int64_t sn, int64_t sy, int64_t sx, int64_t sc, int32_t b, int32_t h, int32_t w,
                       float clip_flow, int32_t has_clip, int32_t bgr, uint8_t *out, uint32_t *rad_max, void *stream);
 
+/* Input images: crop, bilinear resize (with or without antialiasing), channel reversal and (v - mean) / std of a list of
+ * images as ONE launch.  nsrc (1 .. PIO_MAX_IMAGE_SOURCES) descriptors, each n images of C channels and H x W pixels of uint8
+ * or fp32 read in place: element (i, c, y, x) at data[i*sb + c*sc + y*sy + x*sx] (element strides, all >= 0; the stride of
+ * an axis of length 1 is not read), of which the crop box rows [y0, y0 + ch), columns [x0, x0 + cw) is resampled to oh x ow.
+ * out: fp32, image g (descriptors in order, images of a descriptor in order) at out + g*out_sb, [C, oh, ow] contiguous.
+ * Per axis, `in` the crop length, `out` the output length, output index i has weights over crop indices j, every index
+ * and numerator an integer and every weight ONE fp32 division (never scale * (i + 0.5) in floating point):
+ *   antialias == 0:  q = max(0, (2i+1) in - out),  j0 = min(q / (2 out), in - 1),  l = (q - 2 out j0) / (2 out)
+ *                    w[j0] = 1 - l,  w[j0 + 1] = l  (j0 == in - 1, where both taps fall on one pixel:  w[j0] = (1 - l) + l)
+ *   antialias != 0:  d = 2 max(in, out),  lo = max(0, ((2i+1) in - d + out) / (2 out)),  hi = min(in, ((2i+1) in + d + out) / (2 out))
+ *                    r[j] = max(0, 1 - |(2j+1) out - (2i+1) in| / d),  w[j] = r[j] / (r[lo] + .. + r[hi-1], ascending)
+ * (integer divisions truncate), which are max(0, 1 - |j + 1/2 - centre| / support) of centre = (in/out)(i + 1/2), support =
+ * max(in/out, 1) over trunc(centre -+ support + 1/2).  Then, with fmaf chains that start at +0 and run ascending:
+ *   h[c, y, ox]  = sum_x wx[ox, x] * src[c, y0 + y, x0 + x]           (the horizontal pass, fp32 in LDS)
+ *   v[c, oy, ox] = sum_y wy[oy, y] * h[c, y, ox]
+ *   out[c, oy, ox] = fdiv_rn(fsub_rn(v[cs, oy, ox], mean[c]), std[c]),  cs = reverse_channels ? C - 1 - c : c
+ * mean / std: HOST pointers to C floats, copied into the kernel arguments; NULL means 0 / 1.  The bits of an output value
+ * depend on its own image, box and sizes only: not on n, the descriptor, its position or the other descriptors.  Non-finite
+ * fp32 source values propagate as the arithmetic above has it (a zero weight times inf is NaN).  Exactly C*oh*ow values per
+ * image are written and nothing else.  The table is copied into the kernel arguments; no workspace, no device allocation,
+ * no synchronisation; the call can be captured into a graph.
+ * PIO_E_ARG: NULL srcs / out / data, nsrc outside [1, PIO_MAX_IMAGE_SOURCES], dtype not PIO_IMAGE_U8 / PIO_IMAGE_F32;
+ * PIO_E_SHAPE: C outside [1, 4] or a descriptor's C different, n < 1, H or W outside [1, 16384], oh or ow outside [1, 1024],
+ * an empty box or one not inside the image, a negative stride, ch > PIO_IMAGE_MAX_REDUCTION * oh or cw > .. * ow, out_sb <
+ * C*oh*ow with more than one image, more than 2^31 - 1 workgroups; PIO_E_ALIGN: fp32 data or out not 4-byte aligned.  A
+ * refused call launches nothing. */
+#define PIO_MAX_IMAGE_SOURCES 32
+#define PIO_IMAGE_MAX_REDUCTION 40
+#define PIO_IMAGE_U8 0
+#define PIO_IMAGE_F32 1
+typedef struct pio_image_src_t {
+    const void *data;
+    int64_t sb, sc, sy, sx; /* element strides: image, channel, row, column */
+    int32_t dtype;          /* PIO_IMAGE_U8 / PIO_IMAGE_F32 */
+    int32_t n, C, H, W;
+    int32_t y0, x0, ch, cw; /* the crop box */
+} pio_image_src_t;
+int pio_prepare_images(const pio_image_src_t *srcs, int32_t nsrc, int32_t C, int32_t oh, int32_t ow, int32_t antialias,
+                       int32_t reverse_channels, const float *mean, const float *std, float *out, int64_t out_sb,
+                       void *stream);
+
 /* C = epilogue(alpha * A B^T): A [M,K], B [N,K] operand dtype, K contiguous (multiple of 8).
  * Batched over z = zb*nh + zh with element strides; bias_mode 0 none / 1 per column / 2 per row;
  * act 0 none / 1 exact-erf GELU (F.gelu, transformer_primitives.py:214); optional fp32 residual R

@@ -11,4 +11,10 @@ from .flow_image import flow_to_image  # noqa: F401
 # False sends it down the torch restatement of the same formula (flow_image.restatement), which every other input takes
 fused_flow_image = True
 
+from .image_prep import prepare_images  # noqa: E402,F401
+
+# prepare_images of CUDA uint8 / fp32 images under the hip backend: pio_prepare_images (one launch per 32 sources) when True;
+# False sends them down the torch chain (image_prep.chain), which CPU tensors and whatever the plan declines take
+fused_image_prep = True
+
 __version__ = "0.1.0"

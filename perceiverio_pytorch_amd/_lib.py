@@ -119,6 +119,21 @@ class FlowBlend(C.Structure):
                 ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
 
 
+# descriptors per pio_prepare_images launch: 32 x 64 bytes of the kernel's own table + ~100 bytes of sizes, mean and std keep
+# the argument block well inside HIP's 4 KB; longer lists are launched in groups (fused_io.prepare_images)
+PIO_MAX_IMAGE_SOURCES = 32
+PIO_IMAGE_MAX_REDUCTION = 40
+PIO_IMAGE_U8 = 0
+PIO_IMAGE_F32 = 1
+
+
+class ImageSource(C.Structure):
+    """pio_image_src_t: n images of one size, layout and dtype of pio_prepare_images, read in place, with their crop box."""
+    _fields_ = [("data", C.c_void_p), ("sb", C.c_int64), ("sc", C.c_int64), ("sy", C.c_int64), ("sx", C.c_int64),
+                ("dtype", C.c_int32), ("n", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("y0", C.c_int32), ("x0", C.c_int32), ("ch", C.c_int32), ("cw", C.c_int32)]
+
+
 class Gemm(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("A_lo", C.c_void_p), ("B_lo", C.c_void_p), ("C", C.c_void_p),
                 ("C_lo", C.c_void_p),
@@ -175,6 +190,7 @@ SIGNATURES = {
                                    _i32, _i32, _vp]),
     "pio_flow_blend_tiles": (C.c_int, [P(FlowBlend), _vp, _i64, _i64, _i64, _vp]),
     "pio_flow_to_image": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _f, _i32, _i32, _vp, _vp, _vp]),
+    "pio_prepare_images": (C.c_int, [P(ImageSource), _i32, _i32, _i32, _i32, _i32, _i32, P(_f), P(_f), _vp, _i64, _vp]),
     "pio_gemm_nt": (C.c_int, [P(Gemm), _vp]),
     "pio_softmax_rows": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f, _vp, _vp, _vp, _vp, _i32, _vp]),
     "pio_flash_attention": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64,

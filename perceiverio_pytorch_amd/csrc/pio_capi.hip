@@ -227,6 +227,13 @@ int pio_flow_to_image(const float *flow, int64_t sn, int64_t sy, int64_t sx, int
     return flow_to_image_launch(flow, sn, sy, sx, sc, b, h, w, clip_flow, has_clip, bgr, out, rad_max, (hipStream_t)stream);
 }
 
+int pio_prepare_images(const pio_image_src_t *srcs, int32_t nsrc, int32_t C, int32_t oh, int32_t ow, int32_t antialias,
+                       int32_t reverse_channels, const float *mean, const float *std, float *out, int64_t out_sb,
+                       void *stream) {
+    return prepare_images_launch(srcs, nsrc, C, oh, ow, antialias, reverse_channels, mean, std, out, out_sb,
+                                 (hipStream_t)stream);
+}
+
 int pio_gemm_nt(const pio_gemm_t *g, void *stream) {
     if (!g) return PIO_E_ARG;
     return gemm_nt_launch(*g, (hipStream_t)stream);

@@ -148,6 +148,9 @@ int flow_blend_tiles_launch(const pio_flow_blend_t *p, float *out, int64_t on, i
 // flow visualisation: the Middlebury colour wheel of a batch of flow fields, one maximum radius per image (two launches)
 int flow_to_image_launch(const float *flow, int64_t sn, int64_t sy, int64_t sx, int64_t sc, int b, int h, int w,
                          float clip_flow, int has_clip, int bgr, uint8_t *out, uint32_t *rad_max, hipStream_t s);
+// input images: crop, bilinear resize (antialiased or not), channel reversal and (v - mean) / std of up to 32 sources
+int prepare_images_launch(const pio_image_src_t *srcs, int nsrc, int C, int oh, int ow, int antialias, int reverse,
+                          const float *mean, const float *std, float *out, int64_t out_sb, hipStream_t s);
 // decoder queries: Fourier features of index points | learned table, each with its padding embedding, up to 4 row segments
 int build_queries_launch(const pio_query_segment_t *segs, int nseg, float *y, int64_t ldy, int Qtot, int Cq, hipStream_t s);
 // output heads: up to 4 row segments of the decoder output, each through its own narrow fp32 linear head, written in place

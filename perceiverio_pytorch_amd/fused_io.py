@@ -529,3 +529,53 @@ def blend_tiles(model, pair, h, w, min_overlap):
     if not R.call(dev, "pio_flow_blend_tiles", p, out.data_ptr(), 2 * h * w, h * w, w, declines=(-1, -2)):
         return None
     return R.forward_only(out, *keep)
+
+
+def image_prep_decline(on, items, oh, ow):
+    """Why prepare_images does not take `items` ([(view [n, C, H, W], (top, left, height, width)), ..]) to oh x ow, as a
+    sentence, or None when it takes them: the switch, the backend, a tensor that is not a CUDA uint8 / fp32 tensor, sizes
+    beyond the entry point's caps (source sides 16 384, output sides 1024, a reduction above PIO_IMAGE_MAX_REDUCTION per
+    axis), more images than an int32 counts."""
+    if not on:
+        return "fused_image_prep is off"
+    if R.get_backend() != "hip":
+        return "the backend is not hip"
+    if not 1 <= oh <= 1024 or not 1 <= ow <= 1024:
+        return "an output side beyond 1024"
+    total = 0
+    for x, (_, _, ch, cw) in items:
+        if not x.is_cuda:
+            return "a tensor that is not on a GPU"
+        if x.dtype not in (torch.uint8, torch.float32):
+            return "a dtype other than uint8 and float32"
+        if x.shape[2] > 16384 or x.shape[3] > 16384:
+            return "a source side beyond 16384"
+        if ch > L.PIO_IMAGE_MAX_REDUCTION * oh or cw > L.PIO_IMAGE_MAX_REDUCTION * ow:
+            return f"a reduction above {L.PIO_IMAGE_MAX_REDUCTION}"
+        total += x.shape[0]
+    return "2^31 images or more" if total >= 2 ** 31 else None
+
+
+def prepare_images(on, items, c, oh, ow, antialias, reverse, mean, std, out):
+    """`out` [N, C, oh, ow] (fp32, contiguous within an image) filled by pio_prepare_images from `items` (see
+    image_prep_decline; every view is read in place through its strides), in launches of at most PIO_MAX_IMAGE_SOURCES
+    descriptors, or None when image_prep_decline gives a reason.  mean / std: C Python floats each."""
+    if image_prep_decline(on, items, oh, ow) is not None:
+        return None
+    dev = out.device
+    fl = (L.C.c_float * c)
+    mean_c, std_c = fl(*mean), fl(*std)
+    sb = out.stride(0) if out.shape[0] > 1 else c * oh * ow
+    done = 0
+    for i in range(0, len(items), L.PIO_MAX_IMAGE_SOURCES):
+        group = items[i:i + L.PIO_MAX_IMAGE_SOURCES]
+        arr = (L.ImageSource * len(group))()
+        for d, (x, (y0, x0, ch, cw)) in zip(arr, group):
+            d.data, d.dtype = x.data_ptr(), L.PIO_IMAGE_U8 if x.dtype == torch.uint8 else L.PIO_IMAGE_F32
+            d.sb, d.sc, d.sy, d.sx = x.stride()
+            d.n, d.C, d.H, d.W = x.shape
+            d.y0, d.x0, d.ch, d.cw = y0, x0, ch, cw
+        R.call(dev, "pio_prepare_images", arr, len(group), c, oh, ow, int(bool(antialias)), int(bool(reverse)), mean_c,
+               std_c, out.data_ptr() + 4 * done * sb, sb)
+        done += sum(x.shape[0] for x, _ in group)
+    return out

@@ -14,6 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import fused_io as FIO
+from . import image_prep
 from . import io_processors
 from . import runtime as R
 from .io_processors import (AudioPostprocessor, AudioPreprocessor, ClassificationPostprocessor,
@@ -160,6 +161,17 @@ class ClassificationPerceiver(nn.Module):
                                                               project=False))
         # opt-in: the postprocessor keeps query row 0 only (postprocessors.py:187), and decoder rows are independent
         self.decode_row0_only = decode_row0_only
+        self.img_size = (img_size, img_size) if isinstance(img_size, int) else tuple(img_size)
+
+    # example_img_classify.py: the pixel statistics its Normalize is given
+    MEAN_RGB = (0.485 * 255, 0.456 * 255, 0.406 * 255)
+    STDDEV_RGB = (0.229 * 255, 0.224 * 255, 0.225 * 255)
+
+    def prepare(self, images) -> torch.Tensor:
+        """Photographs (a tensor or a list of differently sized ones, values 0 .. 255) as the example prepares them: centre
+        square, antialiased bilinear resize to img_size, Normalize(MEAN_RGB, STDDEV_RGB): [N, 3, H, W] for forward()."""
+        return image_prep.prepare_images(images, self.img_size, crop="center", antialias=True, mean=self.MEAN_RGB,
+                                         std=self.STDDEV_RGB)
 
     @property
     def decode_row0_only(self) -> bool:
@@ -308,6 +320,12 @@ class FlowPerceiver(nn.Module):
             input_preprocessors=prep,
             output_postprocessors=FlowPostprocessor(img_size=img_size, flow_scale_factor=flow_scale_factor))
         self.H, self.W = (img_size, img_size) if isinstance(img_size, int) else tuple(img_size)
+
+    @staticmethod
+    def prepare(img) -> torch.Tensor:
+        """A frame (or a batch of frames) with values 0 .. 255 scaled to [-1, 1], at its own size: (x - 127.5) / 127.5, which
+        is example_opt_flow.py's 2 (x / 255) - 1 up to rounding (2 ulp of 1.0 at most over the 256 byte values)."""
+        return image_prep.prepare_images(img, None, mean=127.5, std=127.5)
 
     def compute_grid_indices(self, image_shape: tuple, min_overlap: int):
         """Top-left corners of training-size tiles covering the image with at least ``min_overlap`` overlap."""
@@ -476,6 +494,16 @@ class MultiModalPerceiver(R.PackedOwner):
     def forward(self, images: torch.Tensor, audio: torch.Tensor, n_chunks: int = 128):
         with _policy_scope(self):
             return self._forward(images, audio, n_chunks)
+
+    def prepare_video(self, frames, bgr: bool = True) -> torch.Tensor:
+        """Decoded frames (a [T, H, W, 3] tensor or a list of [H, W, 3] ones, values 0 .. 255; bgr: in OpenCV's channel
+        order) as example_multimodal.py's load_video prepares them: crop_center_square (its own corner, x // 2 - m // 2),
+        bilinear resize without antialiasing to the model's frame size, RGB order, / 255: [1, T, 3, H, W] for forward()."""
+        shapes = [frames.shape[1:3]] * frames.shape[0] if isinstance(frames, torch.Tensor) else [f.shape[:2] for f in frames]
+        boxes = [(h // 2 - min(h, w) // 2, w // 2 - min(h, w) // 2, min(h, w), min(h, w)) for h, w in shapes]
+        x = image_prep.prepare_images(frames, (self.H, self.W), crop=boxes, antialias=False, reverse_channels=bgr, std=255.0,
+                                      channels_last=True)
+        return x.unsqueeze(0)
 
     # The decoder query array of an output chunk -- Fourier features of the chunk's index points, the learned label
     # query, the padding embeddings -- depends on no input, only on parameters and constants (every output query of

@@ -27,6 +27,9 @@
     python tools/prep_bench.py --flow-image         flow_to_image on the device (pio_flow_to_image) against .cpu().numpy() plus
                                                 the numpy function at 368 x 496, 436 x 1024 and 1080 x 1920, b = 1; prints
                                                 one JSON line
+    python tools/prep_bench.py --image-prep         prepare_images (pio_prepare_images) against the torch chain on four
+                                                workloads, and ClassificationPerceiver.prepare + forward at B = 32; prints
+                                                one JSON line
 """
 import argparse
 import json
@@ -788,8 +791,84 @@ def flow_image(repeats, launches):
     print(json.dumps(result))
 
 
+def image_prep(repeats, launches, forward=True):
+    """prepare_images (pio_prepare_images) against the torch chain (fused_image_prep = False) on the same device, sources
+    resident, `repeats` alternating runs of `launches` back-to-back calls each (device events, 3 warm-up calls):
+      batch32   -- 32 uint8 channels-last photographs of 500 x 375 as ONE tensor -> 224 x 224, centre square, antialiased
+      list32    -- 32 such photographs of mixed sizes between 256 and 640 as a list
+      video16   -- a 16-frame 240 x 320 BGR clip through MultiModalPerceiver.prepare_video
+      frame1080 -- one 1080 x 1920 frame -> 224 x 224, antialiased
+    Per workload: median and (min, max) in microseconds of both paths, device kernels and copies of one call, peak memory
+    above the inputs, and the kernel path's bytes per second over the bytes it must move (crop in, output out).  Then the
+    whole step: ClassificationPerceiver.prepare + forward at B = 32 against chain + forward, three alternating runs."""
+    import perceiverio_pytorch_amd as P
+    from perceiverio_pytorch_amd.models import ClassificationPerceiver, MultiModalPerceiver
+    from perceiverio_pytorch_amd.image_prep import center_box
+    g = torch.Generator().manual_seed(0)
+
+    def photo(h, w):
+        return torch.randint(0, 256, (h, w, 3), dtype=torch.uint8, generator=g).to(dev)
+    sizes = [(256 + (37 * i) % 385, 256 + (101 * i) % 385) for i in range(32)]
+    mm = MultiModalPerceiver.__new__(MultiModalPerceiver)
+    mm.H, mm.W = 224, 224
+    batch, many = torch.stack([photo(500, 375) for _ in range(32)]), [photo(h, w) for h, w in sizes]
+    clip, frame = torch.stack([photo(240, 320) for _ in range(16)]), photo(1080, 1920)
+    cls = dict(size=(224, 224), crop="center", mean=ClassificationPerceiver.MEAN_RGB, std=ClassificationPerceiver.STDDEV_RGB)
+    work = {"batch32": (lambda: P.prepare_images(batch, **cls), [(500, 375)] * 32),
+            "list32": (lambda: P.prepare_images(many, **cls), sizes),
+            "video16": (lambda: mm.prepare_video(clip), [(240, 320)] * 16),
+            "frame1080": (lambda: P.prepare_images(frame, (224, 224)), None)}
+    result = {"tool": "tools/prep_bench.py --image-prep", "repeats": repeats, "launches_per_repeat": launches, "unit": "us",
+              "cases": {}}
+
+    def switched(on, f):
+        def run():
+            P.fused_image_prep = on
+            try:
+                return f()
+            finally:
+                P.fused_image_prep = True
+        return run
+
+    def peak(f):
+        f()
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        f()
+        torch.cuda.synchronize()
+        return torch.cuda.max_memory_allocated() - base
+    for name, (f, shapes) in work.items():
+        ways = {"kernel": switched(True, f), "chain": switched(False, f)}
+        a, b = ways["kernel"](), ways["chain"]()
+        times = {k: [] for k in ways}
+        for _ in range(repeats):
+            for k, w in ways.items():
+                times[k].append(timed(w, launches))
+        case = {k: {"median": statistics.median(v), "min": min(v), "max": max(v), "one_call": _kernel_launches(ways[k]),
+                    "peak_bytes_above_inputs": peak(ways[k])} for k, v in times.items()}
+        crops = [(1080, 1920)] if shapes is None else [center_box(h, w)[2:] for h, w in shapes]
+        need = sum(3 * ch * cw for ch, cw in crops) + 4.0 * a.numel()
+        case["kernel"]["algorithm_bytes"] = need
+        case["kernel"]["GB_per_s_at_median"] = need / (case["kernel"]["median"] * 1e-6) / 1e9
+        case["max_abs_difference_kernel_chain"] = float((a - b).abs().max())
+        result["cases"][name] = case
+    if forward:
+        model = ClassificationPerceiver().to(dev).eval()
+        steps = {"kernel": switched(True, lambda: model(model.prepare(batch))),
+                 "chain": switched(False, lambda: model(model.prepare(batch)))}
+        times = {k: [] for k in steps}
+        for _ in range(3):
+            for k, w in steps.items():
+                times[k].append(timed(w, max(2, launches // 4)))
+        result["classifier_step_B32"] = {k: {"median": statistics.median(v), "min": min(v), "max": max(v)}
+                                         for k, v in times.items()}
+    print(json.dumps(result))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--image-prep", action="store_true", help="time pio_prepare_images against the torch chain")
     ap.add_argument("--flow-front", action="store_true", help="time pio_flow_patch_tokens against the torch chain")
     ap.add_argument("--multimodal-front", action="store_true", help="time pio_assemble_tokens against the torch chain")
     ap.add_argument("--decoder-queries", action="store_true", help="time pio_build_queries against the torch chain")
@@ -804,7 +883,9 @@ if __name__ == "__main__":
     ap.add_argument("--launches", type=int, default=20)
     args = ap.parse_args()
     with torch.no_grad():
-        if args.flow_front:
+        if args.image_prep:
+            image_prep(args.repeats, args.launches)
+        elif args.flow_front:
             flow_front(args.repeats, args.launches)
         elif args.multimodal_front:
             multimodal_front(args.repeats, args.launches)
