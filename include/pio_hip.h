@@ -337,6 +337,30 @@ int pio_flow_patch_tokens(const float *frame0, const float *frame1, int64_t sn0,
                           int64_t sc1, int64_t sy1, const float *w, const float *bias, float *y, int64_t ldy, int32_t N,
                           int32_t C, int32_t H, int32_t W, int32_t out, void *stream);
 
+/* Front end of the 1x1-conv image classifier in one pass: nn.Conv2d(C, N, kernel_size=1, stride=s) of an image batch and the
+ * channels-last copy behind it (preprocessors.py:57-258 ImagePreprocessor "conv1x1") as the token rows the encoder reads.
+ * With OH = H / s, OW = W / s, m = i*OW + j:
+ *   acc = bias ? bias[n] : 0.0f
+ *   for c = 0 .. C-1 (ascending): acc = fmaf(w[n*ldw + c], x[b*sb + c*sc + (i*s)*sy + (j*s)*sx], acc)
+ *   y[b*sYb + m*ldy + n] = acc
+ * x: fp32 [B, C, H, W] through its own four element strides -- any of them: a channels-last view, a batch slice, a stride-0
+ * batch, a pointer that is only 4-byte aligned; it is read in place (only pixels (i*s, j*s)), never copied.  w [N, C] fp32 with
+ * row pitch ldw, bias [N] fp32 or NULL; y [B, OH*OW, N] fp32 with row pitch ldy and sample stride sYb.  sb and sYb are not read
+ * when B == 1.  Only the N channels of each of the B*OH*OW rows are written: [N, ldy) and everything else stays untouched.
+ * ONE fp32 FMA chain per output in the order above: the bits of a value depend on its own pixel, weights and bias only -- not
+ * on the batch, the grid or the tile it fell into -- and are the same from run to run.  N <= PIO_CONV1X1_MAX_N: a lane keeps
+ * the 4*C weights and 4 biases of its four outputs per 256 channels in registers for a whole strip of rows -- 80 of them at
+ * C = 4, N = 1024, which with accumulators and addresses stays under the 128 registers per lane of four waves per SIMD.
+ * No workspace, no device allocation, no synchronisation.
+ * PIO_E_ARG: NULL x / w / y; PIO_E_SHAPE: B, H or W < 1, C outside [1, 4], s outside [1, 8], H % s or W % s != 0, N outside
+ * [4, PIO_CONV1X1_MAX_N] or not a multiple of 4, ldw < C, ldy < N, B*OH*OW > 2^31 - 1, for B > 1 sYb < OH*OW*ldy;
+ * PIO_E_ALIGN: ldy % 4 != 0, for B > 1 sYb % 4 != 0, y not 16-byte aligned, x / w / bias not 4-byte aligned.  A refused call
+ * launches nothing. */
+#define PIO_CONV1X1_MAX_N 1024
+int pio_conv1x1_tokens(const float *x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float *w, int64_t ldw,
+                       const float *bias, float *y, int64_t ldy, int64_t sYb, int32_t B, int32_t C, int32_t H, int32_t W,
+                       int32_t s, int32_t N, void *stream);
+
 /* One segment of the multimodal front end: rows [row0, row0 + M) of every sample of the token array.  With
  * Cp = Cc - C1 - C2 >= 0 and x the row
  *   x[0       : C1     ] = feature(b, m, :)

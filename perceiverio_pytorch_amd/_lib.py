@@ -125,6 +125,8 @@ PIO_MAX_IMAGE_SOURCES = 32
 PIO_IMAGE_MAX_REDUCTION = 40
 PIO_IMAGE_U8 = 0
 PIO_IMAGE_F32 = 1
+# output channels of pio_conv1x1_tokens: a lane keeps 4 C weights + 4 biases per 256 of them in registers
+PIO_CONV1X1_MAX_N = 1024
 
 
 class ImageSource(C.Structure):
@@ -182,6 +184,8 @@ SIGNATURES = {
     "pio_bn_relu_maxpool_tokens": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "pio_flow_patch_tokens": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32,
                                         _i32, _i32, _vp]),
+    "pio_conv1x1_tokens": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32,
+                                     _i32, _i32, _vp]),
     "pio_assemble_tokens": (C.c_int, [P(TokenSegment), _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "pio_build_queries": (C.c_int, [P(QuerySegment), _i32, _vp, _i64, _i32, _i32, _vp]),
     "pio_project_heads": (C.c_int, [P(HeadSegment), _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),

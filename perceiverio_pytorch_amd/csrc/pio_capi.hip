@@ -190,6 +190,12 @@ int pio_flow_patch_tokens(const float *frame0, const float *frame1, int64_t sn0,
                                     (hipStream_t)stream);
 }
 
+int pio_conv1x1_tokens(const float *x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float *w, int64_t ldw,
+                       const float *bias, float *y, int64_t ldy, int64_t sYb, int32_t B, int32_t C, int32_t H, int32_t W,
+                       int32_t s, int32_t N, void *stream) {
+    return conv1x1_tokens_launch(x, sb, sc, sy, sx, w, ldw, bias, y, ldy, sYb, B, C, H, W, s, N, (hipStream_t)stream);
+}
+
 int pio_assemble_tokens(const pio_token_segment_t *segs, int32_t nseg, float *y, int64_t ldy, int64_t sYb, int32_t B,
                         int32_t Mtot, int32_t Cc, void *stream) {
     return assemble_tokens_launch(segs, nseg, y, ldy, sYb, B, Mtot, Cc, (hipStream_t)stream);

@@ -136,6 +136,10 @@ int bn_relu_pool_nhwc_launch(const float *x, const float *scale, const float *sh
 int flow_patch_tokens_launch(const float *f0, const float *f1, int64_t sn0, int64_t sc0, int64_t sy0, int64_t sn1,
                              int64_t sc1, int64_t sy1, const float *w, const float *bias, float *y, int64_t ldy, int N,
                              int C, int H, int W, int out, hipStream_t s);
+// 1x1-conv classifier front end: a stride-s 1x1 convolution of an image batch written as channels-last token rows
+int conv1x1_tokens_launch(const float *x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float *w, int64_t ldw,
+                          const float *bias, float *y, int64_t ldy, int64_t sYb, int B, int C, int H, int W, int s, int N,
+                          hipStream_t st);
 // multimodal front end: features | position table | padding embedding (| mask token) of up to 8 row segments in one launch
 int assemble_tokens_launch(const pio_token_segment_t *segs, int nseg, float *y, int64_t ldy, int64_t sYb, int B, int Mtot,
                            int Cc, hipStream_t s);

@@ -115,6 +115,101 @@ def flow_patch_tokens(prep, pair):
     return R.forward_only(y if ldy == out else y[:, :, :out], *deps)
 
 
+# No size of the two classifier front ends below is routed back to the chain: a measurement (profiles/classify_front_ends.json,
+# tools/prep_bench.py --classify-front, B = 1 / 8 / 32 at 224 x 224) found no crossover -- the 1x1 hand-off 27 / 86 / 300 us
+# against 100 / 3370 / 14350 us, the pixel hand-off 30 / 162 / 606 us against 30 / 221 / 940 us (equal at one sample, inside the
+# repeats' range), the whole forward never slower.  Smaller images and s > 1 were not timed.
+def conv1x1_tokens(prep, x):
+    """The "conv1x1" image front end on an image batch [B, C, H, W] by ONE HIP kernel (pio_conv1x1_tokens): the strided 1x1
+    convolution and the channels-last copy behind it, without the [B, N, OH, OW] array between them.  Returns the features
+    [B, OH*OW, N] (one fresh allocation) or None: the switch off, the torch backend, anything but a 4-D CUDA fp32 tensor, a
+    preprocessor that is not "conv1x1", a conv with groups, dilation, padding, a non-square stride, a kernel other than 1x1
+    or a padding mode other than "zeros", a weight or bias that is not fp32 on the input's device, C outside [1, 4], a
+    stride outside [1, 8] or one that does not divide H and W, N outside [4, PIO_CONV1X1_MAX_N] or no multiple of 4, an
+    empty axis, 2^31 rows or more, OH*OW != prod(index_dims).  The image is read in place through its own strides."""
+    if getattr(prep, "_prep_type", None) != "conv1x1" or not gate(prep.fused_conv1x1, x) or x.dim() != 4:
+        return None
+    conv = prep.convnet_1x1
+    wt, bias = conv.weight, conv.bias
+    if (conv.groups != 1 or tuple(conv.kernel_size) != (1, 1) or tuple(conv.dilation) != (1, 1)
+            or isinstance(conv.padding, str) or tuple(conv.padding) != (0, 0) or conv.padding_mode != "zeros"
+            or conv.stride[0] != conv.stride[1]):
+        return None
+    dev, (b, c, h, w), s = x.device, x.shape, int(conv.stride[0])
+    if (wt.dtype != torch.float32 or wt.device != dev or tuple(wt.shape[1:]) != (c, 1, 1)
+            or (bias is not None and (bias.dtype != torch.float32 or bias.device != dev))):
+        return None
+    n = wt.shape[0]
+    if (not 1 <= c <= 4 or not 1 <= s <= 8 or min(b, h, w) < 1 or h % s or w % s or n % 4
+            or not 4 <= n <= L.PIO_CONV1X1_MAX_N or x.data_ptr() % 4):
+        return None
+    m = (h // s) * (w // s)
+    if m != int(math.prod(prep.index_dims)) or b * m >= 2 ** 31:
+        return None
+    w2 = rows(wt.reshape(n, c), min_stride=True)
+    bias_c = None if bias is None else bias.detach().contiguous()
+    y = torch.empty((b, m, n), dtype=torch.float32, device=dev)
+    R.call(dev, "pio_conv1x1_tokens", x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), x.stride(3), w2.data_ptr(),
+           w2.stride(0), None if bias_c is None else bias_c.data_ptr(), y.data_ptr(), n, m * n, b, c, h, w, s, n)
+    return R.forward_only(y, x, wt, bias)
+
+
+def projected_pos_table(prep, feats):
+    """The position half [M, C2] of a preprocessor whose position encoding is a PositionEncodingProjector over a learned
+    table or a Fourier grid table, for features `feats` [B, M, C1] -- ONE fp32 F.linear of the [M, .] base table instead of
+    the chain's BLAS call over B identical copies on every forward -- or None.  It depends on parameters only: built once
+    (outside inference mode, without autograd) and kept in the preprocessor's PackedCache under the parameters' key and the
+    device; .to(), load_state_dict and invalidate_packed_weights drop it.  Taken under the hip backend for CUDA fp32
+    features with the preprocessor's switch (fused_conv1x1) on, concatenated positions, no extra position MLPs and fp32
+    base table, weight and bias on the features' device."""
+    enc = prep._positional_encoding
+    if (not isinstance(prep, R.PackedOwner) or not gate(getattr(prep, "fused_conv1x1", False), feats) or feats.dim() != 3
+            or type(enc) is not PE.PositionEncodingProjector or prep._concat_or_add_pos != "concat"
+            or prep._n_extra_pos_mlp > 0):
+        return None
+    base, lin, dev = enc._base_position_encoding, enc._projector, feats.device
+    if type(base) is PE.TrainablePositionEncoding:
+        src = base.pos_embs
+    elif type(base) is PE.FourierPositionEncoding:
+        src = base(None, None, device=dev)          # (the grid table, built once per device by the encoding itself)
+    else:
+        return None
+    wt, bias = lin.weight, lin.bias
+    if (src.dim() != 2 or src.shape[0] != feats.shape[1] or src.shape[1] != wt.shape[1]
+            or any(t is not None and (t.dtype != torch.float32 or t.device != dev) for t in (src, wt, bias))):
+        return None
+
+    def build():
+        with torch.inference_mode(False), torch.no_grad():
+            table = torch.nn.functional.linear(src.detach(), wt.detach(), None if bias is None else bias.detach())
+            return table.contiguous(), None
+    table = prep._packed.get((R.param_key(src, wt, bias), str(dev)), build, slot="pos_table")
+    return R.forward_only(table, src, wt, bias)
+
+
+class _OneImage:
+    """What assemble_tokens reads of a MultimodalPreprocessor, for ONE ImagePreprocessor: no padding, no masking, the
+    common width the preprocessor's own."""
+    padding_embeddings = mask_tokens = _mask_probs = None
+
+    def __init__(self, prep):
+        self.fused_assembly = prep.fused_pixels
+        self._preprocessors = {"__default": prep}
+        self._common_channels = prep.n_output_channels()
+
+
+def pixel_tokens(prep, x):
+    """(inputs_with_pos [B, M, C + C2], inputs_without_pos) of a "pixels" ImagePreprocessor without subsampling on an image
+    batch [B, C, H, W], from ONE pio_assemble_tokens call (assemble_tokens' own plan: one space-to-depth segment with s = 1,
+    the position table as C2, no padding), or None.  For the hand-off that cannot be split: C or C2 odd.  Bit-identical to
+    the chain (every operation is a move); inputs_without_pos is the [:, :, :C] view of the result."""
+    if (prep._prep_type != "pixels" or prep._spatial_downsample != 1 or not isinstance(x, torch.Tensor) or x.dim() != 4
+            or not (x.shape[1] | prep._positional_encoding.n_output_channels()) & 1):
+        return None
+    got = assemble_tokens(_OneImage(prep), {"__default": x}, None)
+    return None if got is None else (got[0], got[2]["__default"])
+
+
 def bn_relu_pool_tokens(convnet, x):
     """The tail of Conv2DDownsample.forward_tokens: the last layer's BatchNorm (inference statistics) -> ReLU -> 3x3 stride-2
     max-pool (SAME) -> channels-last tokens [B, OH*OW, C] of its conv output `x` by ONE pio_bn_relu_maxpool_tokens call."""

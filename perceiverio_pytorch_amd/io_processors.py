@@ -191,12 +191,18 @@ class _PosMixin:
         replicated [B,M,C1+C2] array; None otherwise."""
         if self._concat_or_add_pos != "concat" or self._n_extra_pos_mlp > 0:
             return None
-        enc = self._positional_encoding(batch_size=feats.shape[0], pos=None, device=feats.device).to(feats.device)
-        if enc.dim() != 3 or (enc.shape[0] > 1 and enc.stride(0) != 0) or enc.shape[1] != feats.shape[1]:
+        table = self._projected_table(feats)    # a projected encoding: its [M, C2] table, once per parameter set
+        if table is None:
+            enc = self._positional_encoding(batch_size=feats.shape[0], pos=None, device=feats.device).to(feats.device)
+            if enc.dim() != 3 or (enc.shape[0] > 1 and enc.stride(0) != 0) or enc.shape[1] != feats.shape[1]:
+                return None
+            table = enc[0]
+        if (feats.shape[2] | table.shape[1]) & 1:
             return None
-        if (feats.shape[2] | enc.shape[2]) & 1:
-            return None
-        return feats, enc[0]
+        return feats, table
+
+    def _projected_table(self, feats: torch.Tensor):
+        return FIO.projected_pos_table(self, feats)
 
 
 class EmbeddingPreprocessor(nn.Module):
@@ -242,7 +248,7 @@ class EmbeddingPreprocessor(nn.Module):
         return tokens + self.input_pos_encoding(inputs.shape[0]), tokens
 
 
-class ImagePreprocessor(nn.Module, _PosMixin):
+class ImagePreprocessor(PackedOwner, _PosMixin):
     """Images / videos -> [B, M, C]: "conv" (Conv2DDownsample), "conv1x1", "patches" (space-to-depth) or "pixels",
     then the position encoding is concatenated or added (preprocessors.py:57-258)."""
 
@@ -301,9 +307,28 @@ class ImagePreprocessor(nn.Module, _PosMixin):
     def _flow_front(self, pair: torch.Tensor):
         return FIO.flow_patch_tokens(self, pair)
 
+    # "conv1x1": the strided 1x1 convolution and its channels-last copy as ONE HIP launch (pio_conv1x1_tokens), and -- with
+    # a projected position encoding -- the [M, C2] position table projected once per parameter set and handed to the encoder
+    # next to the features (forward_split: "split") instead of B projected copies concatenated to them: see _conv1x1_front
+    # and _PosMixin._projected_table.  False, and every input they decline, runs the chain exactly as before, the
+    # concatenated hand-off included.
+    fused_conv1x1 = True
+    # "pixels" without subsampling whose hand-off cannot be split (an odd channel count): [pixels | position table] from ONE
+    # pio_assemble_tokens launch instead of a channels-last copy and torch.cat: see _pixel_front.  Same bits either way.
+    fused_pixels = True
+
+    def _conv1x1_front(self, x: torch.Tensor):
+        return FIO.conv1x1_tokens(self, x)
+
+    def _pixel_front(self, x: torch.Tensor):
+        return FIO.pixel_tokens(self, x)
+
     def _features(self, inputs: torch.Tensor) -> torch.Tensor:
         x = inputs
         tokens = self._flow_front(x)                     # raw frame pair: 3x3 patches + projection in one HIP pass
+        if tokens is not None:
+            return tokens
+        tokens = self._conv1x1_front(x)                  # conv1x1: the convolution, channels-last, in one HIP pass
         if tokens is not None:
             return tokens
         if self._prep_type == "conv" and x.dim() == 4:
@@ -348,6 +373,9 @@ class ImagePreprocessor(nn.Module, _PosMixin):
         configuration does not concatenate a batch-invariant position table (see _PosMixin._split_pos) the ordinary
         hand-off ("full", inputs_with_pos, inputs_without_pos) built from the SAME features -- the preprocessing network
         runs once either way (in train mode a second pass would also update the BatchNorm statistics twice)."""
+        full = self._pixel_front(inputs)        # pixels that cannot be split: both arrays of "full" in one HIP pass
+        if full is not None:
+            return ("full",) + tuple(full)
         feats = self._features(inputs)
         sp = self._split_pos(feats)
         if sp is not None:

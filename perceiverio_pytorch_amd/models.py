@@ -181,6 +181,20 @@ class ClassificationPerceiver(nn.Module):
     def decode_row0_only(self, on: bool) -> None:
         self.perceiver.decoder_query_rows = slice(0, 1) if on else None
 
+    # The encoder input of the LEARNED_POS_1X1CONV and FOURIER_POS_PIXEL variants from ONE HIP launch each for CUDA fp32
+    # images under the hip backend (ImagePreprocessor.fused_conv1x1 -> pio_conv1x1_tokens, with the projected position table
+    # built once and handed over next to the features; ImagePreprocessor.fused_pixels -> pio_assemble_tokens); False restores
+    # the chain of torch ops and the concatenated hand-off.  The pixel variant gives the same bits either way.
+    @property
+    def fused_front_end(self) -> bool:
+        prep = self.perceiver._multi_preprocessor._preprocessors["__default"]
+        return prep.fused_conv1x1 and prep.fused_pixels
+
+    @fused_front_end.setter
+    def fused_front_end(self, on: bool) -> None:
+        prep = self.perceiver._multi_preprocessor._preprocessors["__default"]
+        prep.fused_conv1x1 = prep.fused_pixels = bool(on)
+
     def forward(self, img: torch.Tensor):
         """img: (batch, channels, H, W) -> logits (batch, num_classes)."""
         with _policy_scope(self):

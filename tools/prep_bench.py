@@ -30,6 +30,9 @@
     python tools/prep_bench.py --image-prep         prepare_images (pio_prepare_images) against the torch chain on four
                                                 workloads, and ClassificationPerceiver.prepare + forward at B = 32; prints
                                                 one JSON line
+    python tools/prep_bench.py --classify-front     the encoder hand-off of the 1x1-conv and pixel classifiers
+                                                (pio_conv1x1_tokens, pio_assemble_tokens) against the torch chain at B = 1, 8
+                                                and 32, and the whole forward with the switch on and off; prints one JSON line
 """
 import argparse
 import json
@@ -866,8 +869,102 @@ def image_prep(repeats, launches, forward=True):
     print(json.dumps(result))
 
 
+def classify_front(repeats, launches):
+    """The encoder hand-off of the LEARNED_POS_1X1CONV and FOURIER_POS_PIXEL classifiers ([B, 3, 224, 224] images, 50 176
+    tokens) for B = 1, 8 and 32, timed like language_front (device events around back-to-back calls after 3 warm-up calls,
+    `repeats` times, the ways alternating inside every repeat; `launches` calls per repeat at B = 1, a quarter of them above):
+      chain -- ImagePreprocessor.forward_split with the switch off: the torch ops and the concatenated array
+      fused -- the same call with the switch on: ONE launch (1x1: the features, next to the cached table; pixels: the array)
+      entry -- 1x1 only: pio_conv1x1_tokens alone into a resident output
+    Reported per way: median and (min, max) in microseconds, device kernels and copies per call, and (chain, fused)
+    torch.cuda.max_memory_allocated above what was allocated before the call; for the entry the rate of its one write.
+    Then the whole forward of both classifiers at B = 1 and B = 8 with fused_front_end on and off (off runs the code the
+    switch was added to), three alternating runs of `launches` / 4 forwards each."""
+    from perceiverio_pytorch_amd import _lib as L
+    from perceiverio_pytorch_amd.models import ClassificationPerceiver, PrepType
+    torch.manual_seed(7)
+    lib, stream = L.lib(), torch.cuda.current_stream().cuda_stream
+    result = {"tool": "tools/prep_bench.py --classify-front", "library": os.path.basename(
+        os.environ.get("PIO_LIB_PATH", "libpio_hip.so")), "image": [3, 224, 224], "tokens": 50176, "repeats": repeats,
+        "launches_per_repeat": {"B=1": launches, "B>1": max(2, launches // 4)}, "unit": "us", "handoff": {}, "forward": {}}
+    models = {"conv1x1": ClassificationPerceiver(prep_type=PrepType.LEARNED_POS_1X1CONV).to(dev).eval(),
+              "pixels": ClassificationPerceiver(prep_type=PrepType.FOURIER_POS_PIXEL).to(dev).eval()}
+    for variant, model in models.items():
+        prep = model.perceiver._multi_preprocessor._preprocessors["__default"]
+        for b in (1, 8, 32):
+            n = launches if b == 1 else max(2, launches // 4)
+            x = torch.randn(b, 3, 224, 224, device=dev)
+
+            def way(on, model=model, prep=prep, x=x):
+                def f():
+                    model.fused_front_end = on
+                    return prep.forward_split(x)
+                return f
+            ways = {"chain": way(False), "fused": way(True)}
+            if variant == "conv1x1":
+                conv = prep.convnet_1x1
+                resident = torch.empty(b, 50176, 256, device=dev)
+
+                def entry(conv=conv, resident=resident, x=x, b=b):
+                    L.check(lib.pio_conv1x1_tokens(x.data_ptr(), *x.stride(), conv.weight.data_ptr(), 3, conv.bias.data_ptr(),
+                                                   resident.data_ptr(), 256, 50176 * 256, b, 3, 224, 224, 1, 256, stream),
+                            "pio_conv1x1_tokens")
+                ways["entry"] = entry
+            got = {k: ways[k]() for k in ("chain", "fused")}
+            # (1x1 at B = 1: the chain's projected positions are one table as they stand, so it hands over a pair as well)
+            assert got["fused"][0] == ("split" if variant == "conv1x1" else "full"), "the fused path declined"
+            kinds = {k: got[k][0] for k in got}
+            if variant == "pixels":
+                assert torch.equal(got["chain"][1], got["fused"][1]), "chain and fused arrays differ"
+            else:
+                err = (got["chain"][1][:, :, :256] - got["fused"][1]).abs().max().item()
+                assert err <= 1e-5, f"chain and fused features differ by {err}"
+            del got
+            ops = {k: _device_ops(ways[k]) for k in ways}
+            peak = {}
+            for k in ("chain", "fused"):
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                base = torch.cuda.memory_allocated()
+                torch.cuda.reset_peak_memory_stats()
+                ways[k]()
+                torch.cuda.synchronize()
+                peak[k] = torch.cuda.max_memory_allocated() - base
+            times = {k: [] for k in ways}
+            for _ in range(repeats):
+                for k, f in ways.items():
+                    times[k].append(timed(f, n))
+            case = {k: {"median": statistics.median(v), "min": min(v), "max": max(v), "device_ops": ops[k]}
+                    for k, v in times.items()}
+            for k, v in peak.items():
+                case[k]["peak_bytes_above_inputs"] = v
+                case[k]["handoff"] = kinds[k]
+            if "entry" in case:
+                out_bytes = 4.0 * b * 50176 * 256
+                case["entry"].update(output_bytes=out_bytes,
+                                     write_TB_per_s_at_median=out_bytes / (case["entry"]["median"] * 1e-6) / 1e12)
+            result["handoff"].setdefault(variant, {})[f"B={b}"] = case
+            del x, ways
+            torch.cuda.empty_cache()
+        model.fused_front_end = True
+    for variant, model in models.items():
+        for b in (1, 8):
+            x = torch.randn(b, 3, 224, 224, device=dev)
+            runs = {"on": [], "off": []}
+            for _ in range(3):
+                for k in ("off", "on"):
+                    model.fused_front_end = k == "on"
+                    runs[k].append(timed(lambda: model(x), max(2, launches // 4)))
+            model.fused_front_end = True
+            result["forward"].setdefault(variant, {})[f"B={b}"] = {
+                k: {"runs": v, "min": min(v), "max": max(v)} for k, v in runs.items()}
+    print(json.dumps(result))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--classify-front", action="store_true",
+                    help="time the 1x1-conv and pixel classifier hand-offs (pio_conv1x1_tokens, pio_assemble_tokens)")
     ap.add_argument("--image-prep", action="store_true", help="time pio_prepare_images against the torch chain")
     ap.add_argument("--flow-front", action="store_true", help="time pio_flow_patch_tokens against the torch chain")
     ap.add_argument("--multimodal-front", action="store_true", help="time pio_assemble_tokens against the torch chain")
@@ -883,7 +980,9 @@ if __name__ == "__main__":
     ap.add_argument("--launches", type=int, default=20)
     args = ap.parse_args()
     with torch.no_grad():
-        if args.image_prep:
+        if args.classify_front:
+            classify_front(args.repeats, args.launches)
+        elif args.image_prep:
             image_prep(args.repeats, args.launches)
         elif args.flow_front:
             flow_front(args.repeats, args.launches)
