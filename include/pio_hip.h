@@ -18,7 +18,7 @@
  *     stale 16-bit activations, fp32 scores, key-bit words and key-split partials of an earlier, larger call, NaN
  *     patterns included -- and no result depends on it: every pad region a kernel reads is written by its producer
  *     inside the call, or masked by assignment.  The same holds for the caller-owned query cache of
- *     pio_decoder_fwd_qcache while q16_valid == 0 (tests/test_workspace_stale_gpu.py runs every block entry point and
+ *     pio_decoder_fwd (pio_decoder_call_t.q16_hi) while q16_valid == 0 (tests/test_workspace_stale_gpu.py runs every block entry point and
  *     route of tests/workspace_stale_cases.py on a zeroed, a 0xFF- and a 0x7B-filled workspace, bit for bit).
  *   - tensors at the boundary are float32, last dimension contiguous; batch / row strides are given
  *     in ELEMENTS (a batch stride of 0 is a broadcast view, e.g. the latent table of
@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PIO_VERSION 100 /* 0.1.0 */
+#define PIO_VERSION 101 /* 0.1.1 */
 
 enum {
     PIO_OK = 0,
@@ -241,7 +241,7 @@ enum {
 enum { PIO_RP_ATTENTION = 0, PIO_RP_CROSS = 1, PIO_RP_STACK = 2, PIO_RP_DECODER = 3 };
 /* Process-wide switch (modelled on pio_logit_probe_begin / _end; the two probes may be active together): while active,
  * EVERY 16-bit activation buffer produced inside the block entry points (pio_attention_fwd, pio_mlp_fwd ...
- * pio_encoder_fwd_* / pio_decoder_fwd_*) gets one pio_absmax16 on the call's stream, right behind its producer, into
+ * pio_encoder_fwd / pio_decoder_fwd) gets one pio_absmax16 on the call's stream, right behind its producer, into
  * records[n++]; the library keeps (part, kind) of every record on the host.  Hi halves only (a lo residual is below one
  * ulp of its hi half); the probabilities P (at most 1), a projected-query cache that is read but not written, and the
  * transposed copy of the LayerNorm'd inputs a K / V-folded cross-attend makes produce no record.  `records`: caller-zeroed
@@ -783,9 +783,10 @@ size_t pio_mlp_workspace_bytes(const pio_mlp_t *m, int64_t rows);
 int pio_mlp_fwd(const pio_mlp_t *m, const pio_tensor3_t *x, float *out, void *workspace,
                 size_t workspace_bytes, void *stream);
 
-/* Per-call options of the *_opts entry points (NULL or all zero = the library defaults).  They replace, call by call
- * and thread by thread, the process-wide switches pio_ln_fold_enable / pio_set_cu_budget (which stay as test / A-B
- * overrides): two threads driving two encoders on two devices never see each other's choice.
+/* Per-call options of pio_encoder_fwd (pio_encoder_call_t.opts, by value) and pio_self_attention_fwd (a pointer; NULL or
+ * all zero = the library defaults).  They replace, call by call and thread by thread, the process-wide switches
+ * pio_ln_fold_enable / pio_set_cu_budget (which stay as test / A-B overrides): two threads driving two encoders on two
+ * devices never see each other's choice.
  *   ln_fold:   0 = process-wide setting, 1 = LayerNorm fold off (the range guard's un-folded repeat), 2 = where it pays,
  *              3 = wherever a block offers it
  *   cu_budget: CUs the persistent GEMM kernels size their grids for (a CU-masked stream's share); 0 = process-wide */
@@ -796,16 +797,12 @@ typedef struct pio_call_opts_t {
 
 /* SelfAttention.forward (transformer_primitives.py:275-297), no mask (perceiver.py:106 never passes one;
  * masks, attention_bias [B,H,N,N] and probs_out [B,H,N,N] (return_matrix) are accepted for interface
- * parity, all optional).  out [B,N,D] fp32 contiguous; out may alias x.data when x is contiguous. */
+ * parity, all optional).  out [B,N,D] fp32 contiguous; out may alias x.data when x is contiguous.  opts: NULL = defaults. */
 size_t pio_self_attention_workspace_bytes(const pio_self_attention_t *s, int32_t B, int32_t N);
 int pio_self_attention_fwd(const pio_self_attention_t *s, const pio_tensor3_t *x, const uint8_t *kv_mask,
                            const uint8_t *q_mask, const uint8_t *full_mask, const float *attention_bias,
-                           float *out, float *probs_out, void *workspace, size_t workspace_bytes, void *stream);
-
-int pio_self_attention_fwd_opts(const pio_self_attention_t *s, const pio_tensor3_t *x, const uint8_t *kv_mask,
-                                const uint8_t *q_mask, const uint8_t *full_mask, const float *attention_bias,
-                                float *out, float *probs_out, void *workspace, size_t workspace_bytes, void *stream,
-                                const pio_call_opts_t *opts);
+                           float *out, float *probs_out, const pio_call_opts_t *opts, void *workspace,
+                           size_t workspace_bytes, void *stream);
 
 /* CrossAttention.forward (transformer_primitives.py:371-406). out [B,Tq,q_in] fp32 contiguous. */
 size_t pio_cross_attention_workspace_bytes(const pio_cross_attention_t *c, int32_t B, int32_t Tq, int32_t Tk);
@@ -815,72 +812,67 @@ int pio_cross_attention_fwd(const pio_cross_attention_t *c, const pio_tensor3_t 
                             void *workspace, size_t workspace_bytes, void *stream);
 
 /* PerceiverEncoder.forward (perceiver.py:98-107): cross-attend(latents <- inputs, key mask = input_mask)
- * then num_blocks x [layers[0..L)] weight-shared self-attends.  `latents` is the query tensor the
- * caller built (PerceiverEncoder.latents, perceiver.py:94-96: normally a stride-0 broadcast of the
- * [N,D] table).  out [B,N,D] fp32 contiguous. */
+ * then num_blocks x [layers[0..L)] weight-shared self-attends, as ONE call on one record (a zeroed record with cross,
+ * layers, L, num_blocks, inputs, latents and out set is the plain call). */
+typedef struct pio_encoder_call_t {
+    const pio_cross_attention_t *cross;
+    const pio_self_attention_t *layers; /* L descriptors (num_blocks * L with per_block); may be NULL when L == 0 */
+    int32_t L, num_blocks;
+    /* != 0: ONE SET OF PACKED IMAGES PER BLOCK, block b runs layers[b*L .. b*L + L).  The reference shares the parameters
+     * of the L layers over the num_blocks blocks (perceiver.py:104-106); with one 16-bit image per weight its rounding
+     * error then acts num_blocks times in the same direction.  Under the "fp16sd" policy the binder packs block b from
+     * fp16(W + E_{b-1}), E_b = (W + E_{b-1}) - image_b (error feedback over the block index: every image is a rounding of
+     * W within one ulp, their accumulated error stays below half an ulp) -- same shapes, same kernels, same time. */
+    int32_t per_block;
+    const pio_tensor3_t *inputs; /* [B,M,C] */
+    /* optional: the encoder input given as two channel-wise concatenated arrays [inputs | inputs_tail] (inputs_tail->B
+     * == 1: one batch-invariant table): the ImageNet preprocessor's 64 conv features [B,3136,64] and its [3136,258]
+     * Fourier table instead of the replicated [B,3136,322] array (preprocessors.py:176-200); layer_norm_kv runs over the
+     * virtual concatenation, nothing is concatenated in HBM. */
+    const pio_tensor3_t *inputs_tail;
+    /* the query tensor the caller built (PerceiverEncoder.latents, perceiver.py:94-96: normally a stride-0 broadcast of
+     * the [N,D] table) */
+    const pio_tensor3_t *latents;
+    const uint8_t *input_mask; /* optional [B,M] */
+    float *out;                /* [B,N,D] fp32 contiguous */
+    pio_call_opts_t opts;      /* all zero = the library defaults */
+} pio_encoder_call_t;
 size_t pio_encoder_workspace_bytes(const pio_cross_attention_t *cross, const pio_self_attention_t *layers,
                                    int32_t L, int32_t B, int32_t M, int32_t N);
-int pio_encoder_fwd(const pio_cross_attention_t *cross, const pio_self_attention_t *layers, int32_t L,
-                    int32_t num_blocks, const pio_tensor3_t *inputs, const pio_tensor3_t *latents,
-                    const uint8_t *input_mask, float *out, void *workspace, size_t workspace_bytes,
-                    void *stream);
+/* PIO_E_ARG: NULL record, cross, inputs, latents, out or workspace, NULL layers with L > 0. */
+int pio_encoder_fwd(const pio_encoder_call_t *c, void *workspace, size_t workspace_bytes, void *stream);
 
-/* The same with the encoder input given as two channel-wise concatenated arrays [inputs | inputs_tail] (inputs_tail
- * may be NULL = pio_encoder_fwd; inputs_tail->B == 1: one batch-invariant table): the ImageNet preprocessor's 64 conv
- * features [B,3136,64] and its [3136,258] Fourier table instead of the replicated [B,3136,322] array
- * (preprocessors.py:176-200).  Workspace as pio_encoder_workspace_bytes. */
-int pio_encoder_fwd_split(const pio_cross_attention_t *cross, const pio_self_attention_t *layers, int32_t L,
-                          int32_t num_blocks, const pio_tensor3_t *inputs, const pio_tensor3_t *inputs_tail,
-                          const pio_tensor3_t *latents, const uint8_t *input_mask, float *out, void *workspace,
-                          size_t workspace_bytes, void *stream);
-
-/* The same with ONE SET OF PACKED IMAGES PER BLOCK (per_block != 0): block b runs layers[b*L .. b*L + L).  The
- * reference shares the parameters of the L layers over the num_blocks blocks (perceiver.py:104-106); with one 16-bit
- * image per weight its rounding error then acts num_blocks times in the same direction.  Under the "fp16sd" policy
- * the binder packs block b from fp16(W + E_{b-1}), E_b = (W + E_{b-1}) - image_b (error feedback over the block index:
- * every image is a rounding of W within one ulp, their accumulated error stays below half an ulp) -- same shapes,
- * same kernels, same time.  per_block == 0: pio_encoder_fwd_split.  Workspace as pio_encoder_workspace_bytes. */
-int pio_encoder_fwd_blocks(const pio_cross_attention_t *cross, const pio_self_attention_t *layers, int32_t L,
-                           int32_t num_blocks, int32_t per_block, const pio_tensor3_t *inputs,
-                           const pio_tensor3_t *inputs_tail, const pio_tensor3_t *latents, const uint8_t *input_mask,
-                           float *out, void *workspace, size_t workspace_bytes, void *stream);
-
-/* pio_encoder_fwd_blocks with per-call options (opts == NULL: the same call). */
-int pio_encoder_fwd_opts(const pio_cross_attention_t *cross, const pio_self_attention_t *layers, int32_t L,
-                         int32_t num_blocks, int32_t per_block, const pio_tensor3_t *inputs,
-                         const pio_tensor3_t *inputs_tail, const pio_tensor3_t *latents, const uint8_t *input_mask,
-                         float *out, void *workspace, size_t workspace_bytes, void *stream,
-                         const pio_call_opts_t *opts);
-
-/* PerceiverDecoder.forward (perceiver.py:166-180): cross-attend(query <- latents, query mask) and the
- * optional final nn.Linear (final == NULL => final_project=False).  out [B,Q,out_channels] fp32. */
+/* PerceiverDecoder.forward (perceiver.py:166-180): cross-attend(query <- latents, query mask) and the optional final
+ * nn.Linear, as ONE call on one record (a zeroed record with cross, query, latents and out set is the plain call). */
+typedef struct pio_decoder_call_t {
+    const pio_cross_attention_t *cross;
+    const pio_linear_t *final_layer; /* NULL => final_project=False */
+    int32_t final_out;               /* output channels of final_layer */
+    const pio_tensor3_t *query;      /* [B,Q,C] */
+    /* optional: the query rows handed over as TWO arrays whose channels are concatenated, [query | query_tail]
+     * (query_tail->B == 1: one batch-invariant table) -- the dense decoders whose queries ARE the network's preprocessed
+     * input (flow_perceiver.py: FlowQuery = [conv features | Fourier position table]): layer_norm_q runs over the virtual
+     * concatenation, nothing is concatenated in HBM.  Needs cross->use_query_residual == 0, a per-sample query tensor and
+     * q16_hi == NULL: PIO_E_ARG otherwise, before anything is launched. */
+    const pio_tensor3_t *query_tail;
+    const pio_tensor3_t *latents;
+    const uint8_t *query_mask; /* optional [B,Q] */
+    float *out;                /* [B,Q,out_channels] fp32 */
+    /* optional: the PROJECTED QUERIES kept by the caller across calls.  A decoder whose query array depends on parameters
+     * and constants only (the multimodal model's per-chunk Fourier queries, multimodal_perceiver.py:146-161) normalises
+     * and projects it once: q16_hi (and q16_lo when the attention descriptor carries split activations) are caller-owned
+     * device buffers of pio_decoder_qcache_bytes(cross, Bq, Q) bytes each, Bq = 1 for a stride-0 (batch-invariant) query
+     * tensor, else B.  q16_valid == 0: LayerNorm_q + proj_q run and leave their result there; != 0: both are skipped and
+     * the buffers are read.  Only for cross->use_query_residual == 0 (PIO_E_ARG otherwise: the query rows themselves are
+     * needed then); the caller invalidates when the query array, layer_norm_q, proj_q or the precision policy change. */
+    void *q16_hi, *q16_lo;
+    int32_t q16_valid;
+} pio_decoder_call_t;
 size_t pio_decoder_workspace_bytes(const pio_cross_attention_t *cross, const pio_linear_t *final_layer,
                                    int32_t B, int32_t Q, int32_t N);
-int pio_decoder_fwd(const pio_cross_attention_t *cross, const pio_linear_t *final_layer, int32_t final_out,
-                    const pio_tensor3_t *query, const pio_tensor3_t *latents, const uint8_t *query_mask,
-                    float *out, void *workspace, size_t workspace_bytes, void *stream);
-
-/* The same with the PROJECTED QUERIES kept by the caller across calls (q16_hi == NULL: pio_decoder_fwd).  A decoder
- * whose query array depends on parameters and constants only (the multimodal model's per-chunk Fourier queries,
- * multimodal_perceiver.py:146-161) normalises and projects it once: q16_hi (and q16_lo when the attention descriptor
- * carries split activations) are caller-owned device buffers of pio_decoder_qcache_bytes(cross, Bq, Q) bytes each, Bq = 1
- * for a stride-0 (batch-invariant) query tensor, else B.  q16_valid == 0: LayerNorm_q + proj_q run and leave their result
- * there; != 0: both are skipped and the buffers are read.  Only for cross->use_query_residual == 0 (PIO_E_ARG otherwise:
- * the query rows themselves are needed then); the caller invalidates when the query array, layer_norm_q, proj_q or the
- * precision policy change. */
 size_t pio_decoder_qcache_bytes(const pio_cross_attention_t *cross, int32_t Bq, int32_t Q);
-int pio_decoder_fwd_qcache(const pio_cross_attention_t *cross, const pio_linear_t *final_layer, int32_t final_out,
-                           const pio_tensor3_t *query, const pio_tensor3_t *latents, const uint8_t *query_mask,
-                           float *out, void *workspace, size_t workspace_bytes, void *stream, void *q16_hi,
-                           void *q16_lo, int32_t q16_valid);
-
-/* PerceiverDecoder.forward (perceiver.py:166-180) with the query rows handed over as TWO arrays whose channels are
- * concatenated, [query | query_tail] (query_tail->B == 1: one batch-invariant table) -- the dense decoders whose queries ARE
- * the network's preprocessed input (flow_perceiver.py: FlowQuery = [conv features | Fourier position table]): layer_norm_q
- * runs over the virtual concatenation, nothing is concatenated in HBM.  Needs use_query_residual == 0. */
-int pio_decoder_fwd_split(const pio_cross_attention_t *cross, const pio_linear_t *final_layer, int32_t final_out,
-                          const pio_tensor3_t *query, const pio_tensor3_t *query_tail, const pio_tensor3_t *latents,
-                          const uint8_t *query_mask, float *out, void *workspace, size_t workspace_bytes, void *stream);
+/* PIO_E_ARG: NULL record, cross, query, latents, out or workspace; PIO_E_ALIGN: q16_hi / q16_lo not 16-byte aligned. */
+int pio_decoder_fwd(const pio_decoder_call_t *c, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

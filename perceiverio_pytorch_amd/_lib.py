@@ -67,8 +67,24 @@ class Tensor3(C.Structure):
 
 
 class CallOpts(C.Structure):
-    """pio_call_opts_t: per-call (thread-local inside the library) LayerNorm-fold mode and CU budget."""
+    """pio_call_opts_t: per-call LayerNorm-fold mode and CU budget."""
     _fields_ = [("ln_fold", C.c_int32), ("cu_budget", C.c_int32)]
+
+
+class EncoderCall(C.Structure):
+    """pio_encoder_call_t: one pio_encoder_fwd call (a zeroed field is its default: no tail, no mask, shared images)."""
+    _fields_ = [("cross", C.POINTER(CrossAttention)), ("layers", C.POINTER(SelfAttention)), ("L", C.c_int32),
+                ("num_blocks", C.c_int32), ("per_block", C.c_int32), ("inputs", C.POINTER(Tensor3)),
+                ("inputs_tail", C.POINTER(Tensor3)), ("latents", C.POINTER(Tensor3)), ("input_mask", C.c_void_p),
+                ("out", C.c_void_p), ("opts", CallOpts)]
+
+
+class DecoderCall(C.Structure):
+    """pio_decoder_call_t: one pio_decoder_fwd call (a zeroed field is its default: no final layer, tail, mask, cache)."""
+    _fields_ = [("cross", C.POINTER(CrossAttention)), ("final_layer", C.POINTER(Linear)), ("final_out", C.c_int32),
+                ("query", C.POINTER(Tensor3)), ("query_tail", C.POINTER(Tensor3)), ("latents", C.POINTER(Tensor3)),
+                ("query_mask", C.c_void_p), ("out", C.c_void_p), ("q16_hi", C.c_void_p), ("q16_lo", C.c_void_p),
+                ("q16_valid", C.c_int32)]
 
 
 PIO_TOKENS_ROWS = 0
@@ -209,29 +225,16 @@ SIGNATURES = {
     "pio_mlp_workspace_bytes": (_sz, [P(Mlp), _i64]),
     "pio_mlp_fwd": (C.c_int, [P(Mlp), P(Tensor3), _vp, _vp, _sz, _vp]),
     "pio_self_attention_workspace_bytes": (_sz, [P(SelfAttention), _i32, _i32]),
-    "pio_self_attention_fwd": (C.c_int, [P(SelfAttention), P(Tensor3), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "pio_self_attention_fwd_opts": (C.c_int, [P(SelfAttention), P(Tensor3), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
-                                              P(CallOpts)]),
+    "pio_self_attention_fwd": (C.c_int, [P(SelfAttention), P(Tensor3), _vp, _vp, _vp, _vp, _vp, _vp, P(CallOpts), _vp, _sz,
+                                         _vp]),
     "pio_cross_attention_workspace_bytes": (_sz, [P(CrossAttention), _i32, _i32, _i32]),
     "pio_cross_attention_fwd": (C.c_int, [P(CrossAttention), P(Tensor3), P(Tensor3), _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _sz, _vp]),
     "pio_encoder_workspace_bytes": (_sz, [P(CrossAttention), P(SelfAttention), _i32, _i32, _i32, _i32]),
-    "pio_encoder_fwd": (C.c_int, [P(CrossAttention), P(SelfAttention), _i32, _i32, P(Tensor3), P(Tensor3), _vp, _vp,
-                                  _vp, _sz, _vp]),
-    "pio_encoder_fwd_split": (C.c_int, [P(CrossAttention), P(SelfAttention), _i32, _i32, P(Tensor3), P(Tensor3),
-                                        P(Tensor3), _vp, _vp, _vp, _sz, _vp]),
-    "pio_encoder_fwd_blocks": (C.c_int, [P(CrossAttention), P(SelfAttention), _i32, _i32, _i32, P(Tensor3), P(Tensor3),
-                                         P(Tensor3), _vp, _vp, _vp, _sz, _vp]),
-    "pio_encoder_fwd_opts": (C.c_int, [P(CrossAttention), P(SelfAttention), _i32, _i32, _i32, P(Tensor3), P(Tensor3),
-                                       P(Tensor3), _vp, _vp, _vp, _sz, _vp, P(CallOpts)]),
+    "pio_encoder_fwd": (C.c_int, [P(EncoderCall), _vp, _sz, _vp]),
     "pio_decoder_workspace_bytes": (_sz, [P(CrossAttention), P(Linear), _i32, _i32, _i32]),
-    "pio_decoder_fwd": (C.c_int, [P(CrossAttention), P(Linear), _i32, P(Tensor3), P(Tensor3), _vp, _vp, _vp, _sz,
-                                  _vp]),
     "pio_decoder_qcache_bytes": (_sz, [P(CrossAttention), _i32, _i32]),
-    "pio_decoder_fwd_qcache": (C.c_int, [P(CrossAttention), P(Linear), _i32, P(Tensor3), P(Tensor3), _vp, _vp, _vp, _sz,
-                                         _vp, _vp, _vp, _i32]),
-    "pio_decoder_fwd_split": (C.c_int, [P(CrossAttention), P(Linear), _i32, P(Tensor3), P(Tensor3), P(Tensor3), _vp, _vp, _vp,
-                                        _sz, _vp]),
+    "pio_decoder_fwd": (C.c_int, [P(DecoderCall), _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -151,6 +151,19 @@ inline AttnCore fused_core(int dkp, int dvp, int Tk, bool mask_vectors, bool fla
     return xtall_supported(dkp, dvp, Tk) ? AttnCore::XTALL : AttnCore::MATERIALISED;
 }
 
+// The optional operands of one attention call, as they travel from an entry point down to the core (all null = none):
+// key mask [B,Tk], query mask [B,Tq], full mask [B,Tq,Tk], bias [B,H,Tq,Tk], probability output [B,H,Tq,Tk].
+struct AttnOptional {
+    const uint8_t *kv_mask = nullptr, *q_mask = nullptr, *full_mask = nullptr;
+    const float *bias = nullptr;
+    float *probs = nullptr;
+};
+// ... as the facts of an AttnCall / SelfCall (pio_block_route.h)
+template <class Call>
+inline void note_optional(Call &c, const AttnOptional &o) {
+    c.kv_mask = o.kv_mask; c.q_mask = o.q_mask; c.full_mask = o.full_mask; c.bias = o.bias; c.probs = o.probs;
+}
+
 struct AttnCall {  // what attention_core knows about one call, as plain facts
     int B, Bq, Tq, Tk;  // Bq = 1 for batch-invariant queries (q_bcast), else B
     bool q_bcast;

@@ -1,8 +1,9 @@
 // Block composition (host only, plain C++17: no HIP, no environment, no state): the workspace layout of every block
 // entry point (the *Plan structs), whether and on which kernel family a SelfAttention block runs with its LayerNorms
-// folded into the GEMMs around them (self_fold_route), and whether a decoder's fc2 writes the final Linear's 16-bit operand
-// itself (decoder_y16_direct).  pio_blocks.hip reads the switches and launches what these return; the plans only add
-// offsets to the caller's base pointer, nothing here reads through one.  tests/test_block_route.py checks them on the CPU.
+// folded into the GEMMs around them (self_fold_route), whether a decoder's fc2 writes the final Linear's 16-bit operand
+// itself (decoder_y16_direct), and the GEMM descriptor of one nn.Linear in each form a block asks for (linear_gemm).
+// pio_blocks.hip reads the switches and launches what these return; the plans only add offsets to the caller's base
+// pointer, nothing here reads through one.  tests/test_block_route.py checks them on the CPU.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -266,6 +267,139 @@ inline SelfFold self_fold_route(const pio_self_attention_t &sa, const SelfCall &
 // rows directly when the packed image's K is the channel pitch of those rows.
 inline bool decoder_y16_direct(const pio_linear_t *final_layer, int q_c) {
     return final_layer && final_layer->k == padc(q_c);
+}
+
+// ======================================================================================================
+// the GEMM descriptor of one nn.Linear
+// ======================================================================================================
+inline pio_gemm_t gemm_defaults(int dtype) {
+    pio_gemm_t g = {};
+    g.batch = 1;
+    g.nh = 1;
+    g.alpha = 1.f;
+    g.dtype = dtype;
+    return g;
+}
+
+struct Residual {
+    const float *ptr = nullptr;
+    int64_t ld = 0, stride_b = 0;
+    int rows_per_batch = 0;
+};
+
+inline Residual residual_of(const pio_tensor3_t &t) { return Residual{t.data, t.stride_t, t.stride_b, t.T}; }
+
+// LayerNorm fold plumbing of one GEMM (pio_ln_fold_t; all null = plain GEMM).  Consumer side: the 16-bit input is the
+// UN-normalised activation and `in_part` its per-row partial sums -- the GEMM then uses the folded weights `w` / row
+// sums `c`.  Producer side: where the (fp32 + residual) GEMM leaves the 16-bit copy and the partial sums of its result.
+struct LnFold {
+    const float *in_part = nullptr;
+    const pio_linear_t *w = nullptr;
+    const float *c = nullptr;
+    float eps = 0.f;
+    void *out16 = nullptr;
+    int64_t ld16 = 0;
+    float *out_part = nullptr;
+    // ... and the residual stream as a 16-bit pair: lo half of the result, residual given as (hi, lo); with both the
+    // fp32 output pointer of the GEMM may be null
+    void *out16_lo = nullptr;
+    const void *res16_hi = nullptr, *res16_lo = nullptr;
+    int32_t *range_flag = nullptr;  // producer: the caller's range-guard word (pio_ln_fold_t.range_flag)
+    // slot form of the row statistics (pio_gemm_t.ln_slots / row_slot_w): 128-column slots = the 256 x 256-tile kernel,
+    // 64-column slots = the tile kernels (stacks of fewer rows)
+    int in_slots = 0, slot_w = 0;
+};
+
+constexpr int kActNone = 0, kActGelu = 1;  // pio_gemm_t.act
+
+// Where and how the result of one linear leaves.  Three forms, each with a name (below); the optional parts of a form
+// are added behind it: pair16_at(h, ld).gelu().folded(&f), f32_at(out, n, ld).plus(&res).folded(&f).zeros_to(n8).
+struct LinearOut {
+    void *y = nullptr, *y_lo = nullptr;
+    bool f32 = false;
+    int n_logical = 0;              // fp32 form: logical width (a 16-bit form computes all lin.n packed columns)
+    int64_t ldc = 0;                // row pitch of y (elements)
+    int act = kActNone;
+    const Residual *res = nullptr;  // fp32 residual (null, or ptr null: none)
+    const LnFold *fold = nullptr;   // consumer (in_part) or producer (out16) of a LayerNorm fold
+    int n_store16 = 0;              // columns written per row when wider than those computed: the rest as zeros
+
+    LinearOut gelu() const { LinearOut o = *this; o.act = kActGelu; return o; }
+    LinearOut plus(const Residual *r) const { LinearOut o = *this; o.res = r; return o; }
+    LinearOut folded(const LnFold *f) const { LinearOut o = *this; o.fold = f; return o; }
+    LinearOut zeros_to(int n) const { LinearOut o = *this; o.n_store16 = n; return o; }
+};
+// a 16-bit pair (lo may be null) at row pitch ld
+inline LinearOut pair16_at(Pair y, int64_t ld) {
+    LinearOut o;
+    o.y = y.hi; o.y_lo = y.lo; o.ldc = ld;
+    return o;
+}
+// fp32 rows of n_logical columns at row pitch ld
+inline LinearOut f32_at(float *y, int n_logical, int64_t ld) {
+    LinearOut o;
+    o.y = y; o.f32 = true; o.n_logical = n_logical; o.ldc = ld;
+    return o;
+}
+// the decoders' y in front of their final Linear: fc2 leaves (+ residual) as the 16-bit operand rows of that GEMM, pitch
+// ld = padc(channels), zero-filled behind the computed columns
+inline LinearOut out16_at(Pair y, int64_t ld, const Residual *res) {
+    return pair16_at(y, ld).plus(res).zeros_to((int)ld);
+}
+
+// y[rows, n] = x16[rows, lin.k] * W^T (+bias) (act) (+R); a 16-bit output has ldc = lin.n (padded).
+inline pio_gemm_t linear_gemm(const pio_linear_t &lin_plain, int dtype, Pair x, int64_t rows, const LinearOut &o) {
+    const LnFold *fold = o.fold;
+    const pio_linear_t &lin = (fold && fold->in_part) ? *fold->w : lin_plain;
+    pio_gemm_t g = gemm_defaults(dtype);
+    if (fold && fold->in_part) {
+        g.ln_part = fold->in_part;
+        g.ln_c = fold->c;
+        g.ln_eps = fold->eps;
+        g.ln_slots = fold->in_slots;
+    }
+    if (fold && fold->out16) {
+        g.X16 = fold->out16;
+        g.ld16 = fold->ld16;
+        g.row_part = fold->out_part;
+        g.X16_lo = fold->out16_lo;
+        g.R16_hi = fold->res16_hi;
+        g.R16_lo = fold->res16_lo;
+        g.range_flag = fold->range_flag;
+        g.row_slot_w = fold->slot_w;
+    }
+    g.A = x.hi;
+    g.A_lo = x.lo;
+    g.B = lin.w_hi;
+    g.B_lo = lin.w_lo;
+    g.b_lo_n0 = lin.w_lo ? lin.lo_row0 : 0;
+    g.C = o.y;
+    g.C_lo = o.y_lo;
+    g.M = (int)rows;
+    g.N = o.f32 ? o.n_logical : lin.n;
+    // fp32 rows with a rounded-up pitch (pitch4: internal buffers): compute whole float4 groups -- the packed image has
+    // zero rows / zero bias behind the logical ones -- so that every store and residual load is a 16-byte one
+    // (n_store16 on an fp32 result -- x1 of a cross-attend, pitch8: the columns up to it are written as zeros, so a residual
+    //  there adds nothing a caller's wider rows might hold behind the logical columns)
+    if (o.f32 && (o.n_logical & 3) && o.ldc >= pitch4(o.n_logical) && lin.n >= pitch4(o.n_logical) &&
+        !(o.res && o.res->ptr && (o.res->ld < pitch4(o.n_logical) || o.n_store16 > o.n_logical)))
+        g.N = pitch4(o.n_logical);
+    g.K = lin.k;
+    g.lda = lin.k;
+    g.ldb = lin.k;
+    g.ldc = o.ldc;
+    g.bias = lin.bias;
+    g.bias_mode = lin.bias ? 1 : 0;
+    g.act = o.act;
+    g.out_f32 = o.f32 ? 1 : 0;
+    g.n_store = o.n_store16 > g.N ? o.n_store16 : g.N;   // (rows zero-filled up to the channel pitch / the pitch of x1)
+    if (o.res && o.res->ptr && !(fold && fold->res16_hi)) {
+        g.R = o.res->ptr;
+        g.ldr = o.res->ld;
+        g.r_stride_b = o.res->stride_b;
+        g.r_rows_per_batch = o.res->rows_per_batch;
+    }
+    return g;
 }
 
 }  // namespace pio

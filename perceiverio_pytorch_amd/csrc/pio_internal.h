@@ -92,8 +92,6 @@ int rowstats_cast_launch(const float *x, int64_t rows, int C, int slot_w, void *
                          hipStream_t s);
 // VT[b][c][t] = X[b][t][c] (16-bit; columns t in [T, tkv) zero): the values of a K / V-folded cross-attend
 int transpose16_launch(const void *x, int64_t ldx, int B, int T, int C, void *vt, int64_t tkv, hipStream_t s);
-int ln_fold_enable(int on);   // returns the previous setting
-bool ln_fold_enabled();
 int softmax_rows_launch(const float *S, int64_t lds, void *P, void *P_lo, int64_t ldp, int B, int H, int Tq, int Tk,
                         float scale, const uint8_t *kv_mask, const uint8_t *q_mask, const uint8_t *full_mask,
                         const float *bias, int dtype, float *probs_out, hipStream_t s);

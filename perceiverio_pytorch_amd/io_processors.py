@@ -187,7 +187,7 @@ class _PosMixin:
 
     def _split_pos(self, feats: torch.Tensor):
         """(features [B,M,C1], position table [M,C2]) when the network input is their concatenation and the position
-        features are ONE batch-invariant table -- the form pio_encoder_fwd_split consumes without ever building the
+        features are ONE batch-invariant table -- the form pio_encoder_fwd consumes (inputs_tail) without ever building the
         replicated [B,M,C1+C2] array; None otherwise."""
         if self._concat_or_add_pos != "concat" or self._n_extra_pos_mlp > 0:
             return None

@@ -63,7 +63,7 @@ class PerceiverEncoder(R.PackedOwner):
     def forward(self, inputs, latents, *, input_mask=None):
         """Reference signature (perceiver.py:98).  Extension: `inputs` may be a pair (features [B,M,C1], table [M,C2] or
         [1,M,C2]) standing for their channel-wise concatenation with the table broadcast over the batch -- the
-        encoder then never sees a materialised [B,M,C1+C2] array (pio_encoder_fwd_split)."""
+        encoder then never sees a materialised [B,M,C1+C2] array (pio_encoder_call_t.inputs_tail)."""
         if R.cpu_plumbing(inputs[0] if isinstance(inputs, (tuple, list)) else inputs, "PerceiverEncoder.forward"):
             from . import cpu_plumbing as CP
             return CP.encoder(self, inputs, latents, input_mask)
@@ -116,20 +116,18 @@ class PerceiverEncoder(R.PackedOwner):
 
         layers = self._packed.get((tuple(id(d) for ds in descs for d in ds), flag.data_ptr() if guard else 0), build_layers)
 
-        def launch(xs, tail, zs, mask_ptr, out_ptr, blockwise, opts):
-            """One pio_encoder_fwd_opts call on the current stream's workspace."""
-            LP.expect("cross", *["stack"] * (Lyr * self._num_blocks))    # (one attention call per block, this order)
-            LP.mark_range("cross")           # (range probe: the library marks "stack" behind the cross-attend itself)
-            try:
-                ws = R.workspace(dev, lib.pio_encoder_workspace_bytes(cross, layers, Lyr, xs.shape[0], M, N))
-                R.call(dev, "pio_encoder_fwd_opts", cross, layers, Lyr, self._num_blocks, blockwise, R.tensor3(xs), tail,
-                       R.tensor3(zs), mask_ptr, out_ptr, ws.data_ptr(), ws.numel(), tail=(opts,),
-                       what="pio_encoder_fwd")
-            finally:
-                LP.mark_range("attention")
-
-        # (the un-folded repeat of the range guard is a PER-CALL option: no process state changes around the call)
-        launch(x, tail3, z0, im_ptr, out.data_ptr(), int(per_block), L.CallOpts(1 if self._range_fallback else 0, 0))
+        # one pio_encoder_fwd call on the current stream's workspace (the un-folded repeat of the range guard is a PER-CALL
+        # option, opts.ln_fold = 1: no process state changes around the call)
+        rec = L.EncoderCall(C.pointer(cross), C.cast(layers, C.POINTER(L.SelfAttention)), Lyr, self._num_blocks,
+                            int(per_block), C.pointer(R.tensor3(x)), C.pointer(tail3) if tail3 is not None else None,
+                            C.pointer(R.tensor3(z0)), im_ptr, out.data_ptr(), L.CallOpts(1 if self._range_fallback else 0, 0))
+        LP.expect("cross", *["stack"] * (Lyr * self._num_blocks))    # (one attention call per block, this order)
+        LP.mark_range("cross")           # (range probe: the library marks "stack" behind the cross-attend itself)
+        try:
+            ws = R.workspace(dev, lib.pio_encoder_workspace_bytes(cross, layers, Lyr, B, M, N))
+            R.call(dev, "pio_encoder_fwd", C.byref(rec), ws.data_ptr(), ws.numel())
+        finally:
+            LP.mark_range("attention")
         return self._finish(out, flag, inputs, inputs_tail, latents, input_mask)
 
     _range_fallback = False   # True while the call is being repeated un-folded (the guard's fallback)
@@ -202,12 +200,12 @@ class PerceiverDecoder(R.PackedOwner):
         """Reference signature (perceiver.py:166) plus `q_cache`: a dict the CALLER keeps per query array whose content
         depends on parameters and constants only (MultiModalPerceiver's per-chunk queries).  The decoder leaves the
         normalised + projected queries there on the first call and skips LayerNorm_q / proj_q afterwards
-        (pio_decoder_fwd_qcache); it revalidates the entry against its own parameters and the precision policy.  Only
+        (pio_decoder_call_t.q16_hi); it revalidates the entry against its own parameters and the precision policy.  Only
         without the query residual.
 
         Extension (as PerceiverEncoder.forward's): `query` may be a pair (features [B,Q,C1], table [Q,C2] or [1,Q,C2])
         standing for their channel-wise concatenation -- dense decoders whose queries are the network's preprocessed
-        input (FlowQuery): LayerNorm_q reads the two arrays, nothing is concatenated (pio_decoder_fwd_split).  Only
+        input (FlowQuery): LayerNorm_q reads the two arrays, nothing is concatenated (pio_decoder_call_t.query_tail).  Only
         without the query residual."""
         query_tail = None
         if isinstance(query, (tuple, list)):
@@ -233,7 +231,7 @@ class PerceiverDecoder(R.PackedOwner):
         out_ch = self._output_num_channels if self._final_project else self.query_channels
         qm, qm_ptr = R.mask_u8(query_mask, (B, Q), dev)
         out = torch.empty((B, Q, out_ch), dtype=torch.float32, device=dev)
-        fin_ptr = C.byref(fin.desc) if fin is not None else None
+        fin_ptr = C.pointer(fin.desc) if fin is not None else None
         ws = R.workspace(dev, lib.pio_decoder_workspace_bytes(cross, fin_ptr, B, Q, N))
         qhi = qlo = None
         valid = 0
@@ -258,15 +256,13 @@ class PerceiverDecoder(R.PackedOwner):
                 qhi = q_cache["hi"].data_ptr()
                 qlo = q_cache["lo"].data_ptr() if q_cache["lo"] is not None else None
                 valid = 1 if q_cache["valid"] else 0
+        rec = L.DecoderCall(C.pointer(cross), fin_ptr, out_ch, C.pointer(R.tensor3(q)),
+                            C.pointer(R.tensor3(query_tail)) if query_tail is not None else None, C.pointer(R.tensor3(z)),
+                            qm_ptr, out.data_ptr(), qhi, qlo, valid)
         LP.expect("decoder")
         LP.mark_range("decoder")
         try:
-            if query_tail is not None:
-                R.call(dev, "pio_decoder_fwd_split", cross, fin_ptr, out_ch, R.tensor3(q), R.tensor3(query_tail),
-                       R.tensor3(z), qm_ptr, out.data_ptr(), ws.data_ptr(), ws.numel())
-            else:
-                R.call(dev, "pio_decoder_fwd_qcache", cross, fin_ptr, out_ch, R.tensor3(q), R.tensor3(z), qm_ptr,
-                       out.data_ptr(), ws.data_ptr(), ws.numel(), tail=(qhi, qlo, valid), what="pio_decoder_fwd")
+            R.call(dev, "pio_decoder_fwd", C.byref(rec), ws.data_ptr(), ws.numel())
         finally:
             LP.mark_range("attention")
         if qhi is not None:

@@ -568,15 +568,15 @@ class on_device:
         return self._ctx.__exit__(*exc)
 
 
-def call(dev, name, *args, stream=None, what=None, declines=(), tail=()):
+def call(dev, name, *args, stream=None, declines=()):
     """One launch through the C-ABI with `dev` current: entry point `name` with `args`, then the stream (the current one of
-    `dev` unless given), then `tail` (what pio_encoder_fwd_opts / pio_decoder_fwd_qcache take behind their stream).  An error
-    code raises PioError labelled `what or name`; a code in `declines` (the entry refused, nothing launched) returns False."""
+    `dev` unless given): every launching entry point ends in its stream.  An error code raises PioError labelled `name`;
+    a code in `declines` (the entry refused, nothing launched) returns False."""
     with on_device(dev):
-        code = getattr(L.lib(), name)(*args, stream_ptr(dev) if stream is None else stream, *tail)
+        code = getattr(L.lib(), name)(*args, stream_ptr(dev) if stream is None else stream)
     if code in declines:
         return False
-    L.check(code, what or name)
+    L.check(code, name)
     return True
 
 

@@ -70,10 +70,11 @@ def _no_training_dropout(mod: nn.Module, *probs: float) -> None:
         raise NotImplementedError("the HIP path is forward/inference only: call .eval() or use dropout_prob=0")
 
 
-def _block_call(entry, ws_entry, ws_args, d, tensors, dims, out_channels, mask, bias, return_matrix, deps):
+def _block_call(entry, ws_entry, ws_args, d, tensors, dims, out_channels, mask, bias, return_matrix, deps, opts=()):
     """The common tail of the three block forwards: full mask to bytes, bias broadcast over `dims` = (B, H, Tq, Tk), the
     `out` / `probs` buffers, the workspace of `ws_entry(d, *ws_args)`, the launch of `entry` on `tensors`, and the
-    result tied to `deps` (runtime.forward_only).  Returns out, or (probs, out) with `return_matrix`."""
+    result tied to `deps` (runtime.forward_only).  Returns out, or (probs, out) with `return_matrix`.  `opts`: what the
+    entry takes between its outputs and its workspace (pio_self_attention_fwd: its pio_call_opts_t pointer)."""
     B, H, Tq, Tk = dims
     dev = tensors[0].device
     fm, fm_ptr = R.mask_u8(mask, (B, Tq, Tk), dev)
@@ -86,7 +87,7 @@ def _block_call(entry, ws_entry, ws_args, d, tensors, dims, out_channels, mask, 
     LP.expect("attention")
     R.call(dev, entry, d, *[R.tensor3(t) for t in tensors], None, None, fm_ptr,
            bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
-           probs.data_ptr() if probs is not None else None, ws.data_ptr(), ws.numel())
+           probs.data_ptr() if probs is not None else None, *opts, ws.data_ptr(), ws.numel())
     out = R.forward_only(out, *deps)
     return (probs, out) if return_matrix else out
 
@@ -385,7 +386,7 @@ class SelfAttention(_HipModule):
         B, N, D = x.shape
         return _block_call("pio_self_attention_fwd", "pio_self_attention_workspace_bytes", (B, N), self._desc(), (x,),
                            (B, self.attention._num_heads, N, N), D, attention_mask, attention_bias, return_matrix,
-                           (inputs,) + self._params())
+                           (inputs,) + self._params(), opts=(None,))     # (NULL: the library's defaults)
 
 
 # ==================================================================================================

@@ -4,7 +4,11 @@ small driver; descriptors and the workspace base are fake, aligned pointers that
 line is `total bytes, member=offset from the base ...` (-1: not carved; equal offsets: an alias).  The expected values
 were produced by the structs and the fold expression this header replaced (pasted into a driver of the same cases) and
 the byte totals also by the pio_*_workspace_bytes entry points of the library before the move; a sweep of old against
-new over 1.5e9 fold calls and 8.9e6 plans showed no disagreement.  The tables are a readable extract of it."""
+new over 1.5e9 fold calls and 8.9e6 plans showed no disagreement.  The tables are a readable extract of it.
+
+The same for the GEMM descriptor of one nn.Linear (linear_gemm, LINEARS below): expected values from the body of
+pio_blocks.hip's linear_fwd before it moved here, run on the same cases; a sweep of old against new over randomised
+arguments (widths 1..2048, pitches, residual, fold, n_store16) showed no disagreement."""
 import os
 import subprocess
 import tempfile
@@ -336,11 +340,130 @@ static void y16_cases() {
     printf("y16 k_is_pad8_only %d\n", decoder_y16_direct(&k328, 322));
 }
 
+// ---- the GEMM descriptor of one nn.Linear, in every form pio_blocks.hip asks for ------------------------------------------
+// every non-pointer field of the pio_gemm_t, then the pointer fields that are set
+static void show_linear(const char *id, const pio_gemm_t &g) {
+    printf("linear %s M=%d N=%d K=%d lda=%lld ldb=%lld ldc=%lld batch=%d nh=%d sAb=%lld sAh=%lld sBb=%lld sBh=%lld sCb=%lld "
+           "sCh=%lld bias_mode=%d act=%d alpha=%g ldr=%lld r_stride_b=%lld r_rows_per_batch=%d out_f32=%d n_store=%d dtype=%d "
+           "ld16=%lld ln_eps=%g b_lo_n0=%d ln_slots=%d row_slot_w=%d ptrs=",
+           id, g.M, g.N, g.K, (long long)g.lda, (long long)g.ldb, (long long)g.ldc, g.batch, g.nh, (long long)g.sAb,
+           (long long)g.sAh, (long long)g.sBb, (long long)g.sBh, (long long)g.sCb, (long long)g.sCh, g.bias_mode, g.act,
+           g.alpha, (long long)g.ldr, (long long)g.r_stride_b, g.r_rows_per_batch, g.out_f32, g.n_store, g.dtype,
+           (long long)g.ld16, g.ln_eps, g.b_lo_n0, g.ln_slots, g.row_slot_w);
+    const struct { const char *n; const void *p; } ps[] = {
+        {"A", g.A}, {"A_lo", g.A_lo}, {"B", g.B}, {"B_lo", g.B_lo}, {"C", g.C}, {"C_lo", g.C_lo}, {"bias", g.bias}, {"R", g.R},
+        {"X16", g.X16}, {"X16_lo", g.X16_lo}, {"row_part", g.row_part}, {"ln_part", g.ln_part}, {"ln_c", g.ln_c},
+        {"R16_hi", g.R16_hi}, {"R16_lo", g.R16_lo}, {"range_flag", g.range_flag}};
+    const char *sep = "";
+    for (const auto &q : ps)
+        if (q.p) { printf("%s%s", sep, q.n); sep = ","; }
+    printf("\n");
+}
+static pio_linear_t biased(pio_linear_t l) { l.bias = (const float *)W; return l; }   // (as every packed nn.Linear but kq)
+
+static void linear_cases() {
+    void *const P = BASE;                  // any 16-bit buffer
+    float *const F = (float *)BASE;        // any fp32 buffer
+    const Pair hi = {P, nullptr}, both = {P, P};
+    const int F16 = PIO_DT_F16;
+    // the classifier's stack (1024 channels, 8 heads of 128; 32 x 512 rows) and its decoder (1024-channel queries, 1000
+    // classes), the flow model (322-channel inputs AND queries: pitch8 328, pitch4 324, padc 384) and the multimodal
+    // decoder (1026-channel queries: pitch8 1032, pitch4 1028, padc 1088)
+    const pio_self_attention_t st = self_block(FP16, 1024, 8);
+    const pio_cross_attention_t im_d = cross_block(X2AF, 1024, 1024, 1), fl_x = cross_block(FP16, 512, 322, 1),
+                                fl_d = cross_block(X2AF, 322, 512, 1, 0, 0, false),
+                                mm_d = cross_block(X2AFO, 1026, 512, 1, 0, 0, false);
+    const pio_linear_t im_f = biased(final_layer(X2AF, 1024, 1000)), fl_f = biased(final_layer(X2AF, 322, 2)),
+                       mm_f = biased(final_layer(X2AFO, 1026, 512));
+    const int64_t rows = 32 * 512, hdk = 1024, ld3 = 3072;
+    const pio_tensor3_t x = {F, 512 * 1024, 1024, 32, 512, 1024};
+    const Residual rx = residual_of(x);
+
+    // q, k, q|k, q|k|v: 16-bit pairs at the pitch of the (stacked) heads
+    show_linear("q_plain", linear_gemm(biased(im_d.attn.q), F16, both, 1000, pair16_at(both, hdk)));
+    show_linear("q_322", linear_gemm(biased(fl_d.attn.q), F16, both, 182528, pair16_at(both, 512)));
+    show_linear("q_1026", linear_gemm(biased(mm_d.attn.q), F16, both, 6288, pair16_at(both, 512)));
+    show_linear("k_plain", linear_gemm(biased(im_d.attn.k), F16, both, rows, pair16_at(both, hdk)));
+    show_linear("k_322", linear_gemm(biased(fl_x.attn.k), F16, hi, 182528, pair16_at(hi, 328)));
+    show_linear("qk_plain", linear_gemm(biased(st.attn.qk), F16, hi, rows, pair16_at(hi, 2 * hdk)));
+    show_linear("qkv_plain", linear_gemm(biased(st.attn.qkv), F16, hi, rows, pair16_at(hi, ld3)));
+    pio_self_attention_t folded = st;
+    folded.fold.qkv = biased(folded.fold.qkv); folded.fold.fc1 = biased(folded.fold.fc1);
+    LnFold f_qkv, f_out, f_fc1, f_fc2;       // as self_attention_run wires them (WIDE family: 128-column slots)
+    f_qkv.in_part = F; f_qkv.w = &folded.fold.qkv; f_qkv.c = F; f_qkv.eps = 1e-5f; f_qkv.in_slots = 8;
+    f_fc1 = f_qkv; f_fc1.w = &folded.fold.fc1;
+    f_out.out16 = P; f_out.ld16 = 1024; f_out.out_part = F; f_out.out16_lo = P; f_out.res16_hi = P; f_out.res16_lo = P;
+    f_out.range_flag = (int32_t *)BASE; f_out.slot_w = 128;
+    f_fc2 = f_out;
+    show_linear("qkv_folded", linear_gemm(biased(st.attn.qkv), F16, hi, rows, pair16_at(hi, ld3).folded(&f_qkv)));
+    LnFold f_small = f_qkv; f_small.in_slots = 16;
+    show_linear("qkv_folded_small", linear_gemm(biased(st.attn.qkv), F16, hi, 600, pair16_at(hi, ld3).folded(&f_small)));
+    const pio_self_attention_t s2 = self_block(X2S, 1024, 8);     // (the fold's q|k|v image with a lo half for its V rows)
+    LnFold f_s2 = f_qkv; f_s2.w = &s2.fold.qkv;
+    show_linear("qkv_folded_v_lo", linear_gemm(s2.attn.qkv, F16, hi, rows, pair16_at(hi, ld3).folded(&f_s2)));
+    // kq (K / V projection fold: Q Wk, no bias), at 322 channels on pad8
+    show_linear("kq_322", linear_gemm(fl_x.attn.kq, F16, hi, 2048, pair16_at(hi, 328)));
+
+    // out projection: fp32 rows
+    show_linear("out_plain", linear_gemm(biased(st.attn.o), F16, hi, rows, f32_at(F, 1024, 1024)));
+    show_linear("out_322_plain", linear_gemm(biased(fl_d.attn.o), F16, both, 182528, f32_at(F, 322, 322)));
+    show_linear("out_residual", linear_gemm(biased(st.attn.o), F16, hi, rows, f32_at(F, 1024, 1024).plus(&rx)));
+    show_linear("out_fold_producer",
+                linear_gemm(biased(st.attn.o), F16, hi, rows, f32_at(nullptr, 1024, 1024).plus(&rx).folded(&f_out)));
+    // ... into x1 of a cross-attend at its internal pitch (pitch8), zeros behind the logical columns
+    const pio_tensor3_t z = {F, 0, 512, 1, 2048, 512};
+    const Residual rz = residual_of(z), none;
+    show_linear("out_pitch8_1024", linear_gemm(biased(im_d.attn.o), F16, both, 32000, f32_at(F, 1024, 1024).plus(&none)));
+    show_linear("out_pitch8_322", linear_gemm(biased(fl_d.attn.o), F16, both, 182528, f32_at(F, 322, 328).zeros_to(328)));
+    show_linear("out_pitch8_1026", linear_gemm(biased(mm_d.attn.o), F16, both, 6288, f32_at(F, 1026, 1032).zeros_to(1032)));
+    show_linear("out_pitch8_vo_residual", linear_gemm(biased(fl_x.attn.vo), F16, hi, 2048, f32_at(F, 512, 512).plus(&rz)));
+    pio_cross_attention_t odd = cross_block(FP16, 322, 512, 1);   // a 322-channel block WITH the query residual
+    const pio_tensor3_t q322 = {F, 100 * 322, 322, 2, 100, 322};
+    const Residual rq = residual_of(q322);
+    show_linear("out_pitch8_322_residual",
+                linear_gemm(biased(odd.attn.o), F16, hi, 200, f32_at(F, 322, 328).plus(&rq).zeros_to(328)));
+
+    // fc1: 16-bit pair, GELU
+    show_linear("fc1_plain", linear_gemm(biased(st.mlp.fc1), F16, hi, rows, pair16_at(hi, st.mlp.fc1.n).gelu()));
+    show_linear("fc1_1026", linear_gemm(biased(mm_d.mlp.fc1), F16, both, 6288, pair16_at(both, mm_d.mlp.fc1.n).gelu()));
+    show_linear("fc1_322", linear_gemm(biased(fl_d.mlp.fc1), F16, both, 182528, pair16_at(both, fl_d.mlp.fc1.n).gelu()));
+    show_linear("fc1_folded", linear_gemm(biased(st.mlp.fc1), F16, hi, rows, pair16_at(hi, st.mlp.fc1.n).gelu().folded(&f_fc1)));
+    // fc2: fp32 (+ residual x1), the fold's producer, the decoders' 16-bit y
+    const pio_tensor3_t t1 = {F, 512 * 1024, 1024, 32, 512, 1024};
+    const Residual r1 = residual_of(t1);
+    show_linear("fc2_f32", linear_gemm(biased(st.mlp.fc2), F16, hi, rows, f32_at(F, 1024, 1024).plus(&r1)));
+    show_linear("fc2_no_residual", linear_gemm(biased(st.mlp.fc2), F16, hi, rows, f32_at(F, 1024, 1024)));
+    show_linear("fc2_fold_producer",
+                linear_gemm(biased(st.mlp.fc2), F16, hi, rows, f32_at(F, 1024, 1024).plus(&r1).folded(&f_fc2)));
+    show_linear("fc2_fold_producer_no_f32",
+                linear_gemm(biased(st.mlp.fc2), F16, hi, rows, f32_at(nullptr, 1024, 1024).plus(&r1).folded(&f_fc2)));
+    // (a cross-attend's x1 has pitch8 rows; `out` the caller's pitch, or pitch4 for a decoder's internal y)
+    const pio_tensor3_t t322 = {F, 182528ll * 328, 328, 1, 182528, 322}, t1026 = {F, 6288 * 1032, 1032, 1, 6288, 1026};
+    const Residual r322 = residual_of(t322), r1026 = residual_of(t1026);
+    show_linear("fc2_f32_322_caller_pitch", linear_gemm(biased(fl_d.mlp.fc2), F16, both, 182528, f32_at(F, 322, 322).plus(&r322)));
+    show_linear("fc2_f32_322_pitch4", linear_gemm(biased(fl_d.mlp.fc2), F16, both, 182528, f32_at(F, 322, 324).plus(&r322)));
+    show_linear("fc2_f32_1026_caller_pitch", linear_gemm(biased(mm_d.mlp.fc2), F16, both, 6288, f32_at(F, 1026, 1026).plus(&r1026)));
+    show_linear("fc2_f32_1026_pitch4", linear_gemm(biased(mm_d.mlp.fc2), F16, both, 6288, f32_at(F, 1026, 1028).plus(&r1026)));
+    const Residual r322_narrow = residual_of(q322);   // (a residual at the logical pitch keeps the logical width)
+    show_linear("fc2_f32_322_pitch4_narrow_residual",
+                linear_gemm(biased(fl_d.mlp.fc2), F16, both, 200, f32_at(F, 322, 324).plus(&r322_narrow)));
+    const pio_tensor3_t t1024 = {F, 1000 * 1024, 1024, 32, 1000, 1024};
+    const Residual r1024 = residual_of(t1024);
+    show_linear("fc2_out16_1024", linear_gemm(biased(im_d.mlp.fc2), F16, both, 32000, out16_at(both, padc(1024), &r1024)));
+    show_linear("fc2_out16_322", linear_gemm(biased(fl_d.mlp.fc2), F16, both, 182528, out16_at(both, padc(322), &r322)));
+    show_linear("fc2_out16_1026", linear_gemm(biased(mm_d.mlp.fc2), F16, both, 6288, out16_at(both, padc(1026), &r1026)));
+    // the decoders' final Linear
+    show_linear("final_1000", linear_gemm(im_f, F16, both, 32000, f32_at(F, 1000, 1000)));
+    show_linear("final_2_from_322", linear_gemm(fl_f, F16, both, 182528, f32_at(F, 2, 2)));
+    show_linear("final_512_from_1026", linear_gemm(mm_f, PIO_DT_BF16, both, 6288, f32_at(F, 512, 512)));
+}
+
 int main() {
     plan_cases();
     chunk_cases();
     fold_cases();
     y16_cases();
+    linear_cases();
     return 0;
 }
 '''
@@ -671,6 +794,171 @@ ENCODER = {
 
 Y16 = {"no_final_layer": 0, "k_is_padc": 1, "k_is_pad8_only": 0}
 
+# linear_gemm: id -> every non-pointer field of the pio_gemm_t, then the pointer fields that are set.  One line per form in
+# which pio_blocks.hip asks for an nn.Linear (pair16_at / f32_at / out16_at and their optional parts) at the shapes of the
+# shipped models, the ragged widths 322 and 1026 included: there the pitch4 widening of N and the n_store rule turn.
+LINEARS = {
+    "q_plain":
+        "M=1000 N=1024 K=1024 lda=1024 ldb=1024 ldc=1024 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=1024 dtype=0 "
+        "ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,C_lo,bias",
+    "q_322":
+        "M=182528 N=512 K=384 lda=384 ldb=384 ldc=512 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=512 dtype=0 ld16=0 "
+        "ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,C_lo,bias",
+    "q_1026":
+        "M=6288 N=512 K=1088 lda=1088 ldb=1088 ldc=512 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=512 dtype=0 ld16=0 "
+        "ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,C_lo,bias",
+    "k_plain":
+        "M=16384 N=1024 K=1024 lda=1024 ldb=1024 ldc=1024 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=1024 dtype=0 "
+        "ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,C_lo,bias",
+    "k_322":
+        "M=182528 N=328 K=384 lda=384 ldb=384 ldc=328 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=328 dtype=0 ld16=0 "
+        "ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,B,C,bias",
+    "qk_plain":
+        "M=16384 N=2048 K=1024 lda=1024 ldb=1024 ldc=2048 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=2048 dtype=0 "
+        "ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,B,C,bias",
+    "qkv_plain":
+        "M=16384 N=3072 K=1024 lda=1024 ldb=1024 ldc=3072 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=3072 dtype=0 "
+        "ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,B,C,bias",
+    "qkv_folded":
+        "M=16384 N=3072 K=1024 lda=1024 ldb=1024 ldc=3072 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=3072 dtype=0 "
+        "ld16=0 ln_eps=1e-05 b_lo_n0=0 ln_slots=8 row_slot_w=0 ptrs=A,B,C,bias,ln_part,ln_c",
+    "qkv_folded_small":
+        "M=600 N=3072 K=1024 lda=1024 ldb=1024 ldc=3072 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=3072 dtype=0 "
+        "ld16=0 ln_eps=1e-05 b_lo_n0=0 ln_slots=16 row_slot_w=0 ptrs=A,B,C,bias,ln_part,ln_c",
+    "qkv_folded_v_lo":
+        "M=16384 N=3072 K=1024 lda=1024 ldb=1024 ldc=3072 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=0 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=3072 dtype=0 "
+        "ld16=0 ln_eps=1e-05 b_lo_n0=2048 ln_slots=8 row_slot_w=0 ptrs=A,B,B_lo,C,ln_part,ln_c",
+    "kq_322":
+        "M=2048 N=328 K=328 lda=328 ldb=328 ldc=328 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=0 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=328 dtype=0 ld16=0 "
+        "ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,B,B_lo,C",
+    "out_plain":
+        "M=16384 N=1024 K=1024 lda=1024 ldb=1024 ldc=1024 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=1 n_store=1024 dtype=0 "
+        "ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,B,C,bias",
+    "out_322_plain":
+        "M=182528 N=322 K=512 lda=512 ldb=512 ldc=322 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=1 n_store=322 dtype=0 ld16=0 "
+        "ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,bias",
+    "out_residual":
+        "M=16384 N=1024 K=1024 lda=1024 ldb=1024 ldc=1024 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=1024 r_stride_b=524288 r_rows_per_batch=512 out_f32=1 n_store=1024 "
+        "dtype=0 ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,B,C,bias,R",
+    "out_fold_producer":
+        "M=16384 N=1024 K=1024 lda=1024 ldb=1024 ldc=1024 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=1 n_store=1024 dtype=0 "
+        "ld16=1024 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=128 "
+        "ptrs=A,B,bias,X16,X16_lo,row_part,R16_hi,R16_lo,range_flag",
+    "out_pitch8_1024":
+        "M=32000 N=1024 K=1024 lda=1024 ldb=1024 ldc=1024 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=1 n_store=1024 dtype=0 "
+        "ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,bias",
+    "out_pitch8_322":
+        "M=182528 N=324 K=512 lda=512 ldb=512 ldc=328 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=1 n_store=328 dtype=0 ld16=0 "
+        "ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,bias",
+    "out_pitch8_1026":
+        "M=6288 N=1028 K=512 lda=512 ldb=512 ldc=1032 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=1 n_store=1032 dtype=0 "
+        "ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,B_lo,C,bias",
+    "out_pitch8_vo_residual":
+        "M=2048 N=512 K=328 lda=328 ldb=328 ldc=512 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=512 r_stride_b=0 r_rows_per_batch=2048 out_f32=1 n_store=512 dtype=0 "
+        "ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,B,B_lo,C,bias,R",
+    "out_pitch8_322_residual":
+        "M=200 N=322 K=512 lda=512 ldb=512 ldc=328 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=322 r_stride_b=32200 r_rows_per_batch=100 out_f32=1 n_store=328 "
+        "dtype=0 ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,B,C,bias,R",
+    "fc1_plain":
+        "M=16384 N=1024 K=1024 lda=1024 ldb=1024 ldc=1024 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=1 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=1024 dtype=0 "
+        "ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,B,C,bias",
+    "fc1_1026":
+        "M=6288 N=1088 K=1088 lda=1088 ldb=1088 ldc=1088 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=1 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=1088 dtype=0 "
+        "ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,C_lo,bias",
+    "fc1_322":
+        "M=182528 N=384 K=384 lda=384 ldb=384 ldc=384 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=1 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=384 dtype=0 ld16=0 "
+        "ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,C_lo,bias",
+    "fc1_folded":
+        "M=16384 N=1024 K=1024 lda=1024 ldb=1024 ldc=1024 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=1 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=0 n_store=1024 dtype=0 "
+        "ld16=0 ln_eps=1e-05 b_lo_n0=0 ln_slots=8 row_slot_w=0 ptrs=A,B,C,bias,ln_part,ln_c",
+    "fc2_f32":
+        "M=16384 N=1024 K=1024 lda=1024 ldb=1024 ldc=1024 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=1024 r_stride_b=524288 r_rows_per_batch=512 out_f32=1 n_store=1024 "
+        "dtype=0 ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,B,C,bias,R",
+    "fc2_no_residual":
+        "M=16384 N=1024 K=1024 lda=1024 ldb=1024 ldc=1024 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=1 n_store=1024 dtype=0 "
+        "ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,B,C,bias",
+    "fc2_fold_producer":
+        "M=16384 N=1024 K=1024 lda=1024 ldb=1024 ldc=1024 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=1 n_store=1024 dtype=0 "
+        "ld16=1024 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=128 "
+        "ptrs=A,B,C,bias,X16,X16_lo,row_part,R16_hi,R16_lo,range_flag",
+    "fc2_fold_producer_no_f32":
+        "M=16384 N=1024 K=1024 lda=1024 ldb=1024 ldc=1024 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=1 n_store=1024 dtype=0 "
+        "ld16=1024 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=128 "
+        "ptrs=A,B,bias,X16,X16_lo,row_part,R16_hi,R16_lo,range_flag",
+    "fc2_f32_322_caller_pitch":
+        "M=182528 N=322 K=384 lda=384 ldb=384 ldc=322 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=328 r_stride_b=59869184 r_rows_per_batch=182528 out_f32=1 n_store=322 "
+        "dtype=0 ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,bias,R",
+    "fc2_f32_322_pitch4":
+        "M=182528 N=324 K=384 lda=384 ldb=384 ldc=324 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=328 r_stride_b=59869184 r_rows_per_batch=182528 out_f32=1 n_store=324 "
+        "dtype=0 ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,bias,R",
+    "fc2_f32_1026_caller_pitch":
+        "M=6288 N=1026 K=1088 lda=1088 ldb=1088 ldc=1026 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=1032 r_stride_b=6489216 r_rows_per_batch=6288 out_f32=1 n_store=1026 "
+        "dtype=0 ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,bias,R",
+    "fc2_f32_1026_pitch4":
+        "M=6288 N=1028 K=1088 lda=1088 ldb=1088 ldc=1028 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=1032 r_stride_b=6489216 r_rows_per_batch=6288 out_f32=1 n_store=1028 "
+        "dtype=0 ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,bias,R",
+    "fc2_f32_322_pitch4_narrow_residual":
+        "M=200 N=322 K=384 lda=384 ldb=384 ldc=324 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=322 r_stride_b=32200 r_rows_per_batch=100 out_f32=1 n_store=322 "
+        "dtype=0 ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,bias,R",
+    "fc2_out16_1024":
+        "M=32000 N=1024 K=1024 lda=1024 ldb=1024 ldc=1024 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=1024 r_stride_b=1024000 r_rows_per_batch=1000 out_f32=0 n_store=1024 "
+        "dtype=0 ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,C_lo,bias,R",
+    "fc2_out16_322":
+        "M=182528 N=328 K=384 lda=384 ldb=384 ldc=384 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=328 r_stride_b=59869184 r_rows_per_batch=182528 out_f32=0 n_store=384 "
+        "dtype=0 ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,C_lo,bias,R",
+    "fc2_out16_1026":
+        "M=6288 N=1032 K=1088 lda=1088 ldb=1088 ldc=1088 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=1032 r_stride_b=6489216 r_rows_per_batch=6288 out_f32=0 n_store=1088 "
+        "dtype=0 ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,C_lo,bias,R",
+    "final_1000":
+        "M=32000 N=1000 K=1024 lda=1024 ldb=1024 ldc=1000 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=1 n_store=1000 dtype=0 "
+        "ld16=0 ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,bias",
+    "final_2_from_322":
+        "M=182528 N=2 K=384 lda=384 ldb=384 ldc=2 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=1 n_store=2 dtype=0 ld16=0 "
+        "ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,C,bias",
+    "final_512_from_1026":
+        "M=6288 N=512 K=1088 lda=1088 ldb=1088 ldc=512 batch=1 nh=1 sAb=0 sAh=0 sBb=0 sBh=0 sCb=0 sCh=0 "
+        "bias_mode=1 act=0 alpha=1 ldr=0 r_stride_b=0 r_rows_per_batch=0 out_f32=1 n_store=512 dtype=1 ld16=0 "
+        "ln_eps=0 b_lo_n0=0 ln_slots=0 row_slot_w=0 ptrs=A,A_lo,B,B_lo,C,bias",
+}
+
 
 POLICY_CONSTANTS = {"FP16": "fp16", "X2O": "fp16x2o", "X2S": "fp16x2s", "X2W": "fp16x2w", "X2AF": "fp16x2af",
                     "X2AFO": "fp16x2afo", "X3": "fp16x3", "X3F": "fp16x3f", "X3FQ": "fp16x3fq"}
@@ -697,11 +985,11 @@ def _run_driver():
         exe = os.path.join(d, "route")
         subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", inc, "-I", csrc, src, "-o", exe])
         out = subprocess.check_output([exe]).decode().split("\n")
-    got = {"plan": {}, "fold": {}, "chunks": {}, "encoder": {}, "y16": {}}
+    got = {"plan": {}, "fold": {}, "chunks": {}, "encoder": {}, "y16": {}, "linear": {}}
     for line in filter(None, out):
         kind, name, rest = line.split(" ", 2)
         vals = tuple(int(x) if x.lstrip("-").isdigit() else x for x in rest.split())
-        got[kind][name] = rest if kind == "plan" else vals[0] if len(vals) == 1 else vals
+        got[kind][name] = rest if kind in ("plan", "linear") else vals[0] if len(vals) == 1 else vals
     return got
 
 
@@ -732,6 +1020,13 @@ def test_plan_table():
 
 def test_fold_table():
     assert _got()["fold"] == FOLDS
+
+
+def test_linear_table():
+    got = _got()["linear"]
+    assert sorted(got) == sorted(LINEARS)
+    for name, line in LINEARS.items():
+        assert dict(f.split("=") for f in got[name].split()) == dict(f.split("=") for f in line.split()), name
 
 
 def test_score_chunks_and_y16_direct():

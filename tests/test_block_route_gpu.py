@@ -1,4 +1,4 @@
-"""GPU: ties perceiverio_pytorch_amd/csrc/pio_block_route.h to what pio_self_attention_fwd_opts actually launches, through
+"""GPU: ties perceiverio_pytorch_amd/csrc/pio_block_route.h to what pio_self_attention_fwd actually launches, through
 the library's pio_prof_begin / pio_prof_end accounting: an un-folded SelfAttention block runs two LayerNorm-cast passes
 and four flat tile GEMMs, a folded one a single row-statistics cast and its four GEMMs on the tile kernels (small family)
 or on the 256 x 256-tile kernel (wide family); split activations ("fp16x3") take the materialised attention path.  The expected per-class launch counts are literals: they are not computed by calling
@@ -59,9 +59,9 @@ def test_self_attention_fwd_launches_the_routed_family(dev, case):
         opts = L.CallOpts(ln_fold, 0)
         L.check(lib.pio_prof_begin(64), "pio_prof_begin")
         try:
-            L.check(lib.pio_self_attention_fwd_opts(d, R.tensor3(x), None, None, None, None, out.data_ptr(), None,
-                                                    ws.data_ptr(), ws.numel(), R.stream_ptr(dev), C.byref(opts)),
-                    "pio_self_attention_fwd_opts")
+            L.check(lib.pio_self_attention_fwd(d, R.tensor3(x), None, None, None, None, out.data_ptr(), None,
+                                               C.byref(opts), ws.data_ptr(), ws.numel(), R.stream_ptr(dev)),
+                    "pio_self_attention_fwd")
         finally:
             launches = (C.c_int64 * 9)()
             assert lib.pio_prof_end(None, None, None, launches) >= 0

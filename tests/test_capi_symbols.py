@@ -38,7 +38,7 @@ def test_ctypes_table_matches_header():
 def test_host_side_queries_need_no_gpu():
     from perceiverio_pytorch_amd import _lib as L
     lib = L.lib()
-    assert lib.pio_version() == 100
+    assert lib.pio_version() == 101
     assert lib.pio_pad8(322) == 328 and lib.pio_pad8(8) == 8
     assert [lib.pio_padc(c) for c in (96, 250, 322, 504, 512, 1026, 1280)] == [96, 256, 384, 512, 512, 1088, 1280]
     assert lib.pio_packed_weight_bytes(1024, 1024, 8, 1) == 1024 * 1024 * 2
@@ -55,9 +55,10 @@ def test_struct_sizes_match_the_c_layout():
     prog = r'''
 #include <stdio.h>
 #include "pio_hip.h"
-int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(pio_linear_t), sizeof(pio_layernorm_t),
+int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(pio_linear_t), sizeof(pio_layernorm_t),
  sizeof(pio_attention_t), sizeof(pio_mlp_t), sizeof(pio_self_attention_t), sizeof(pio_cross_attention_t),
- sizeof(pio_tensor3_t), sizeof(pio_gemm_t)); return 0;}
+ sizeof(pio_tensor3_t), sizeof(pio_gemm_t), sizeof(pio_call_opts_t), sizeof(pio_encoder_call_t),
+ sizeof(pio_decoder_call_t)); return 0;}
 '''
     with tempfile.TemporaryDirectory() as d:
         c = os.path.join(d, "s.c")
@@ -65,5 +66,6 @@ int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(pio_linear_t),
         exe = os.path.join(d, "s")
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
         sizes = [int(v) for v in subprocess.check_output([exe]).split()]
-    mirrors = [L.Linear, L.LayerNorm, L.Attention, L.Mlp, L.SelfAttention, L.CrossAttention, L.Tensor3, L.Gemm]
+    mirrors = [L.Linear, L.LayerNorm, L.Attention, L.Mlp, L.SelfAttention, L.CrossAttention, L.Tensor3, L.Gemm, L.CallOpts,
+               L.EncoderCall, L.DecoderCall]
     assert sizes == [ctypes.sizeof(m) for m in mirrors]

@@ -126,14 +126,11 @@ def test_call_appends_the_stream_labels_errors_and_honours_the_stand_ins(monkeyp
     assert seen == [(1, None, p, ("stream of", "dev0"))]                     # the arguments in order, then the stream
     assert entered == [("in", "dev0"), ("out", "dev0")]                      # inside the patched on_device
     assert R.call("dev0", "pio_thing", 1, stream=77) is True and seen[-1] == (1, 77)                # a given stream
-    assert R.call("dev0", "pio_thing", 1, tail=(8, 9)) is True and seen[-1] == (1, ("stream of", "dev0"), 8, 9)
     with pytest.raises(AttributeError):
         R.call("dev0", "pio_missing")                                        # a missing entry point is an error
     lib.code = -1
     with pytest.raises(L.PioError, match=r"^pio_thing: PIO_E_SHAPE$"):
         R.call("dev0", "pio_thing")
-    with pytest.raises(L.PioError, match=r"^pio_encoder_fwd: PIO_E_SHAPE$"):
-        R.call("dev0", "pio_thing", what="pio_encoder_fwd")
     assert R.call("dev0", "pio_thing", 5, declines=(-1, -2)) is False and seen[-1] == (5, ("stream of", "dev0"))
     lib.code = -5
     with pytest.raises(L.PioError, match=r"^pio_thing: PIO_E_LAUNCH$"):

@@ -296,7 +296,7 @@ def test_feedback_images_are_roundings_whose_errors_cancel(dt):
 
 def test_per_call_options_replace_the_process_wide_switches():
     """compute calls are thread-safe per (stream, workspace).  The LayerNorm-fold switch and the CU budget
-    travel with the call (pio_call_opts_t -> thread-local inside the library for the duration of the call); the nn.Module
+    travel with the call (pio_call_opts_t: inside pio_encoder_call_t, a pointer for pio_self_attention_fwd); the nn.Module
     layer no longer flips pio_ln_fold_enable / pio_set_cu_budget around its calls.  CPU side: (a) the module sources hold
     no call of the process-wide setters, (b) two threads building their per-call option blocks and descriptor arrays
     concurrently get independent objects with the values they asked for."""
@@ -307,8 +307,9 @@ def test_per_call_options_replace_the_process_wide_switches():
     for mod in (perceiver, transformer_primitives):
         src = inspect.getsource(mod)
         assert "pio_ln_fold_enable(" not in src and "pio_set_cu_budget(" not in src, mod.__name__
-    assert "pio_encoder_fwd_opts" in L.SIGNATURES and "pio_self_attention_fwd_opts" in L.SIGNATURES
-    assert L.SIGNATURES["pio_encoder_fwd_opts"][1][-1]._type_ is L.CallOpts
+    assert dict(L.EncoderCall._fields_)["opts"] is L.CallOpts
+    assert L.SIGNATURES["pio_encoder_fwd"][1][0]._type_ is L.EncoderCall
+    assert L.SIGNATURES["pio_self_attention_fwd"][1][8]._type_ is L.CallOpts      # (in front of the workspace)
 
     from perceiverio_pytorch_amd.transformer_primitives import SelfAttention
     results, errors = {}, []

@@ -299,7 +299,7 @@ def _block(dev, name):
                 if extra == "self":
                     ws = R.workspace(dev, lib.pio_self_attention_workspace_bytes(d, B, Tq))
                     code = lib.pio_self_attention_fwd(d, R.tensor3(xq_t), None, None, None, None, out.data_ptr(), None,
-                                                      ws.data_ptr(), ws.numel(), s)
+                                                      None, ws.data_ptr(), ws.numel(), s)
                 else:
                     ws = R.workspace(dev, lib.pio_attention_workspace_bytes(d, B, Tq, Tk))
                     code = lib.pio_attention_fwd(d, R.tensor3(xq_t), R.tensor3(xkv_t), R.tensor3(xkv_t),

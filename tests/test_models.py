@@ -259,7 +259,7 @@ def test_model_outputs_match_reference(name, policy):
             _close(out["image"], g["out_image"], name + " image", tol)
             _close(out["audio"], g["out_audio"], name + " audio", tol)
             _close(out["label"], g["out_label"], name + " label", tol)
-            # the decoder's cache of the projected chunk queries (pio_decoder_fwd_qcache): first call fills it, second
+            # the decoder's cache of the projected chunk queries (pio_decoder_call_t.q16_hi): first call fills it, second
             # reads it, without it the same arithmetic runs per call -- all three bit-identical
             again = model(ins[0], ins[1], n_chunks=2)
             model.cache_projected_queries = False
@@ -332,7 +332,7 @@ def test_tied_embedding_projection_runs_in_hip(policy):
 @pytest.mark.gpu
 def test_split_encoder_input_is_bit_identical_to_the_concatenated_one():
     """ImageNet conv preprocessing: the encoder fed with (64 conv features, one [3136, 258] Fourier table)
-    (pio_encoder_fwd_split / pio_layernorm_cast_cat) gives the logits of the materialised [B, 3136, 322] hand-off bit
+    (pio_encoder_call_t.inputs_tail / pio_layernorm_cast_cat) gives the logits of the materialised [B, 3136, 322] hand-off bit
     for bit (same LayerNorm arithmetic, same lane <-> channel mapping), and the reference golden within 1e-3."""
     dev = torch.device("cuda:0")
     name = "model_classify_conv"
@@ -352,7 +352,7 @@ def test_split_encoder_input_is_bit_identical_to_the_concatenated_one():
 @pytest.mark.gpu
 def test_flow_inputs_reach_encoder_and_decoder_as_two_arrays():
     """FlowPerceiver: the preprocessed inputs are [64 conv-after-patches features | one 258-channel Fourier table] and ARE the
-    decoder's query rows (FlowQuery).  Encoder (pio_encoder_fwd_split) and decoder (pio_decoder_fwd_split: LayerNorm_q over
+    decoder's query rows (FlowQuery).  Encoder (inputs_tail) and decoder (query_tail: LayerNorm_q over
     the two arrays) both take the pair -- the [1, 182 528, 322] fp32 array is never built -- and give the flow field of the
     materialised hand-off bit for bit, and the reference golden within 1e-3."""
     dev = torch.device("cuda:0")

@@ -1479,7 +1479,7 @@ def test_fold_range_guard_falls_back_on_overflow(dev, policy):
 
 @pytest.mark.parametrize("D,fold", [(1024, True), (72, False)])
 def test_per_block_images_path_equals_shared_path_when_images_are_equal(dev, D, fold, monkeypatch):
-    """Policy "fp16sd" hands pio_encoder_fwd_blocks one descriptor set per block.  With the error feedback switched off
+    """Policy "fp16sd" hands pio_encoder_fwd one descriptor set per block (per_block).  With the error feedback switched off
     (every block gets the round-to-nearest image) the result must equal policy "fp16" bit for bit -- same kernels, same
     order, only the weight pointers differ -- with and without the LayerNorm fold; with the feedback on it must differ
     (the images do) and stay as close to the fp16x3 result."""

@@ -436,8 +436,8 @@ def test_workspace_self_attention(dev, fp16_policy):
     x = _randn(dev, 2, 128, 64)
     need = lib.pio_self_attention_workspace_bytes(d, 2, 128)
     _workspace_contract(dev, "pio_self_attention_fwd", need, (2, 128, 64),
-                        lambda o, w, n: lib.pio_self_attention_fwd(d, R.tensor3(x), None, None, None, None, o, None, w, n,
-                                                                   _stream()))
+                        lambda o, w, n: lib.pio_self_attention_fwd(d, R.tensor3(x), None, None, None, None, o, None, None, w,
+                                                                   n, _stream()))
 
 
 def test_workspace_cross_attention(dev, fp16_policy):
@@ -463,9 +463,13 @@ def test_workspace_decoder(dev, fp16_policy):
     cross, fin = m.decoding_cross_attn._desc(), m._final_desc()
     q, z = _randn(dev, 2, 16, 64, seed=3), _randn(dev, 2, 32, 64, seed=4)
     need = lib.pio_decoder_workspace_bytes(cross, C.byref(fin.desc), 2, 16, 32)
-    _workspace_contract(dev, "pio_decoder_fwd", need, (2, 16, 10),
-                        lambda o, w, n: lib.pio_decoder_fwd(cross, C.byref(fin.desc), 10, R.tensor3(q), R.tensor3(z), None, o,
-                                                            w, n, _stream()))
+    rec = L.DecoderCall(C.pointer(cross), C.pointer(fin.desc), 10, C.pointer(R.tensor3(q)), None, C.pointer(R.tensor3(z)))
+
+    def call(o, w, n):
+        rec.out = o
+        return lib.pio_decoder_fwd(C.byref(rec), w, n, _stream())
+
+    _workspace_contract(dev, "pio_decoder_fwd", need, (2, 16, 10), call)
 
 
 @pytest.mark.parametrize("case", PC.ATTN_WS_CASES, ids=[c[0] for c in PC.ATTN_WS_CASES])

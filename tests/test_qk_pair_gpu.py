@@ -284,7 +284,7 @@ def test_self_attention_block_trained_like_under_fp16x3fq(dev):
         out = torch.empty((B, N, D), dtype=torch.float32, device=dev)
         ws = R.workspace(dev, lib.pio_self_attention_workspace_bytes(d, B, N))
         launches = _profiled(lib, lambda: L.check(lib.pio_self_attention_fwd(
-            d, R.tensor3(xt), None, None, None, None, out.data_ptr(), None, ws.data_ptr(), ws.numel(), R.stream_ptr(dev)),
+            d, R.tensor3(xt), None, None, None, None, out.data_ptr(), None, None, ws.data_ptr(), ws.numel(), R.stream_ptr(dev)),
             "pio_self_attention_fwd"))
         with torch.inference_mode():
             assert torch.equal(m(xt), out)                # the nn.Module front end runs the same call

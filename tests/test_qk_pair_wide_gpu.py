@@ -202,12 +202,12 @@ def test_self_attention_block_wide_heads_under_fp16x3fq(dev):
         out, out_m = (torch.empty((B, N, D), dtype=torch.float32, device=dev) for _ in range(2))
         ws = R.workspace(dev, lib.pio_self_attention_workspace_bytes(d, B, N))
         launches = _profiled(lib, lambda: L.check(lib.pio_self_attention_fwd(
-            d, R.tensor3(xt), None, None, None, None, out.data_ptr(), None, ws.data_ptr(), ws.numel(), R.stream_ptr(dev)),
+            d, R.tensor3(xt), None, None, None, None, out.data_ptr(), None, None, ws.data_ptr(), ws.numel(), R.stream_ptr(dev)),
             "pio_self_attention_fwd"))
         with torch.inference_mode():
             assert torch.equal(m(xt), out)                # the nn.Module front end runs the same call
         launches_m = _profiled(lib, lambda: L.check(lib.pio_self_attention_fwd(
-            d, R.tensor3(xt), kmt.data_ptr(), None, None, None, out_m.data_ptr(), None, ws.data_ptr(), ws.numel(),
+            d, R.tensor3(xt), kmt.data_ptr(), None, None, None, out_m.data_ptr(), None, None, ws.data_ptr(), ws.numel(),
             R.stream_ptr(dev)), "pio_self_attention_fwd"))
     finally:
         P.set_precision_policy(prev)

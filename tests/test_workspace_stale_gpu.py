@@ -12,7 +12,7 @@ with
 and the three results (probability outputs included) must be bit-identical, the guards intact, the launches per
 profiler class the literals of the case, and the baseline within the project's tolerance for the policy of the float64
 oracle (oracle/perceiver_oracle.py) -- three runs that are identically wrong do not pass.  Caller-owned scratch (the
-projected-query cache of pio_decoder_fwd_qcache while q16_valid == 0) is poisoned the same way.  Poison values are data:
+projected-query cache, pio_decoder_call_t.q16_hi, while q16_valid == 0) is poisoned the same way.  Poison values are data:
 no kernel reads an index or an offset from its scratch (the key-bit words are bit masks, the partials fp32 numbers;
 csrc/pio_xattn.hip, pio_xtall.hip), so a poisoned run reads and writes the addresses of the zeroed one."""
 import ctypes as C
@@ -181,7 +181,7 @@ def _prep_self(case, dev, lib, R):
 
     def call(o, w, n, s, valid):
         src = L.Tensor3(o[0], N * Cc, Cc, B, N, Cc) if alias else R.tensor3(xd)
-        return lib.pio_self_attention_fwd_opts(d, src, None, None, None, None, o[0], None, w, n, _stream(), C.byref(opts))
+        return lib.pio_self_attention_fwd(d, src, None, None, None, None, o[0], None, C.byref(opts), w, n, _stream())
 
     return Prepared(need, [("out", (B, N, Cc))], call, {"out": O.self_attention(_f64(p), x.astype(np.float64), H)},
                     [m, xd, opts], pre=(lambda ts: ts[0].copy_(xd)) if alias else None)
@@ -241,24 +241,20 @@ def _prep_encoder(case, dev, lib, R):
     need = lib.pio_encoder_workspace_bytes(cross, layers, Ly, B, M, N)
     tx, tz = R.tensor3(xd), R.tensor3(zd)
     tt = R.tensor3(td) if tail else None
-    e = case["entry"]
+    rec = L.EncoderCall(C.pointer(cross), C.cast(layers, C.POINTER(L.SelfAttention)), Ly, nblk, per_block, C.pointer(tx),
+                        C.pointer(tt) if tail else None, C.pointer(tz), _ptr(imd), None, opts)
 
     def call(o, w, n, s, valid):
-        if e == "encoder_fwd":
-            return lib.pio_encoder_fwd(cross, layers, Ly, nblk, tx, tz, _ptr(imd), o[0], w, n, _stream())
-        if e == "encoder_fwd_split":
-            return lib.pio_encoder_fwd_split(cross, layers, Ly, nblk, tx, tt, tz, _ptr(imd), o[0], w, n, _stream())
-        if e == "encoder_fwd_blocks":
-            return lib.pio_encoder_fwd_blocks(cross, layers, Ly, nblk, per_block, tx, tt, tz, _ptr(imd), o[0], w, n, _stream())
-        return lib.pio_encoder_fwd_opts(cross, layers, Ly, nblk, per_block, tx, tt, tz, _ptr(imd), o[0], w, n, _stream(),
-                                        C.byref(opts))
+        rec.out = o[0]
+        return lib.pio_encoder_fwd(C.byref(rec), w, n, _stream())
 
     ref = O.encoder(_f64(p), x.astype(np.float64), num_blocks=nblk, num_self_attends_per_block=Ly, num_cross_attend_heads=1,
                     num_self_attend_heads=H, input_mask=im)
-    return Prepared(need, [("out", (B, N, D))], call, {"out": ref}, [enc, layers, xd, td, zd, imd, opts])
+    return Prepared(need, [("out", (B, N, D))], call, {"out": ref}, [enc, layers, xd, td, zd, imd, rec])
 
 
 def _prep_decoder(case, dev, lib, R):
+    from perceiverio_pytorch_amd import _lib as L
     from perceiverio_pytorch_amd.perceiver import PerceiverDecoder
     B, Q, N, Dq, D, final, resid = (case[k] for k in ("B", "Q", "N", "Dq", "D", "final", "resid"))
     p = O.gen_decoder(Dq, D, case["out"] if final else None, seed=16)
@@ -266,7 +262,7 @@ def _prep_decoder(case, dev, lib, R):
                                  final_project=final), p, dev)
     cross = dec.decoding_cross_attn._desc()
     fin = dec._final_desc() if final else None
-    fin_ptr = C.byref(fin.desc) if fin is not None else None
+    fin_ptr = C.pointer(fin.desc) if fin is not None else None
     rng = W.rng_for(case)
     q = rng.standard_normal((B, Q, Dq)).astype(np.float32)
     z = rng.standard_normal((B, N, D)).astype(np.float32)
@@ -285,7 +281,7 @@ def _prep_decoder(case, dev, lib, R):
         qm[0, Q - 1] = False
     qmd = _dev(qm.astype(np.uint8), dev) if qm is not None else None
     need = lib.pio_decoder_workspace_bytes(cross, fin_ptr, B, Q, N)
-    e, out_ch = case["entry"], case["out"]
+    out_ch = case["out"]
     scratch = ()
     if case.get("qcache"):
         nb = lib.pio_decoder_qcache_bytes(cross, 1 if case.get("q_bcast") else B, Q)
@@ -294,18 +290,18 @@ def _prep_decoder(case, dev, lib, R):
         used = (1 if case.get("q_bcast") else B) * Q * cross.attn.heads * cross.attn.dkp * 2
         assert used <= nb < used + 256
 
+    rec = L.DecoderCall(C.pointer(cross), fin_ptr, out_ch, C.pointer(R.tensor3(qd)), C.pointer(R.tensor3(td)) if tail else None,
+                        C.pointer(R.tensor3(zd)), _ptr(qmd))
+
     def call(o, w, n, s, valid):
-        if e == "decoder_fwd":
-            return lib.pio_decoder_fwd(cross, fin_ptr, out_ch, R.tensor3(qd), R.tensor3(zd), _ptr(qmd), o[0], w, n, _stream())
-        if e == "decoder_fwd_split":
-            return lib.pio_decoder_fwd_split(cross, fin_ptr, out_ch, R.tensor3(qd), R.tensor3(td), R.tensor3(zd), _ptr(qmd),
-                                             o[0], w, n, _stream())
-        return lib.pio_decoder_fwd_qcache(cross, fin_ptr, out_ch, R.tensor3(qd), R.tensor3(zd), _ptr(qmd), o[0], w, n,
-                                          _stream(), s[0], s[1], valid)
+        rec.out = o[0]
+        if scratch:
+            rec.q16_hi, rec.q16_lo, rec.q16_valid = s[0], s[1], valid
+        return lib.pio_decoder_fwd(C.byref(rec), w, n, _stream())
 
     ref = O.decoder(_f64(p), q.astype(np.float64), z.astype(np.float64), num_heads=1, use_query_residual=resid,
                     final_project=final, query_mask=qm)
-    pr = Prepared(need, [("out", (B, Q, out_ch))], call, {"out": ref}, [dec, fin, qd, td, zd, qmd], scratch=scratch)
+    pr = Prepared(need, [("out", (B, Q, out_ch))], call, {"out": ref}, [dec, fin, qd, td, zd, qmd, rec], scratch=scratch)
     pr.scratch_used = used if scratch else 0
     return pr
 
@@ -413,7 +409,7 @@ def test_result_does_not_depend_on_stale_workspace(dev, case):
 
 
 def test_query_cache_is_scratch_until_valid(dev):
-    """q16_hi / q16_lo of pio_decoder_fwd_qcache: with q16_valid == 0 their content is undefined on entry (the parametrised
+    """q16_hi / q16_lo of pio_decoder_call_t: with q16_valid == 0 their content is undefined on entry (the parametrised
     test above poisons them with the workspace); what the call leaves there serves a q16_valid == 1 call on a freshly
     poisoned workspace, which skips LayerNorm_q and proj_q and returns the same bits."""
     case = W.BY_ID["decoder_qcache"]

@@ -163,7 +163,7 @@ def _lines(c):
         Bq = 1 if c.get("q_bcast") else B
         return [f'attention_entry("{c["id"]}", {a}, call({B}, {Bq}, {c["Tq"]}, {c["Tk"]}, 0, {int(c["inputs"] != "three")}, '
                 f'{flags()}, 0));']
-    if e == "self_attention_fwd_opts":
+    if e == "self_attention_fwd":
         a, has_qkv = _attn_expr(c["policy"], c["H"], c["C"], c["C"], c["C"], c["C"], c["C"])
         return [f'self_entry("{c["id"]}", {a}, {B}, {c["N"]}, {int(_fold_offered(c["policy"], c["C"], has_qkv))}, '
                 f'{c["ln_fold"]}, 0);']
@@ -255,3 +255,46 @@ def test_labelled_routes_are_what_the_headers_return():
     for c in W.CASES:
         if c["entry"].startswith("decoder"):
             assert got["y16"][c["id"]] == [["1" if c["final"] else "0"]], c["id"]
+
+
+def _fake_decoder(resid):
+    """pio_cross_attention_t of the smallest decoder cases (Dq 60, D 44, one head) on fake, aligned pointers."""
+    from perceiverio_pytorch_amd import _lib as L
+    W_, Dq, D = 0x10000000, 60, 44
+    pad8 = lambda c: (c + 7) & ~7  # noqa: E731
+    ca = L.CrossAttention()
+    a, m = ca.attn, ca.mlp
+    a.heads, a.dk, a.dv, a.dkp, a.dvp = 1, D, D, pad8(D), pad8(D)
+    a.q_in, a.k_in, a.v_in, a.out, a.dtype = Dq, D, D, Dq, L.PIO_DT_F16
+    for lin, n, k in ((a.q, pad8(D), pad8(Dq)), (a.k, pad8(D), pad8(D)), (a.v, pad8(D), pad8(D)), (a.o, pad8(Dq), pad8(D)),
+                      (m.fc1, pad8(Dq), pad8(Dq)), (m.fc2, pad8(Dq), pad8(Dq))):
+        lin.w_hi, lin.n, lin.k = W_, n, k
+    m.in_, m.hidden, m.out, m.dtype = Dq, Dq, Dq, L.PIO_DT_F16
+    ca.use_query_residual = int(resid)
+    return ca
+
+
+def test_decoder_refuses_a_query_tail_with_a_cache_or_a_residual_before_any_launch():
+    """pio_decoder_fwd: query_tail together with q16_hi -- which no entry point could express before the call record --
+    and query_tail with use_query_residual are PIO_E_ARG, as is a NULL record.  Fake aligned pointers throughout: the
+    refusals come before the first launch (a launch would read them), and the library loads without a device."""
+    import ctypes as C
+    from perceiverio_pytorch_amd import _lib as L
+    lib = L.lib()
+    B, Q, N, Dq, D, tail = 2, 33, 13, 60, 44, 6
+    X, WS, Q16 = 0x20000000, 0x40000000, 0x30000000
+    query = L.Tensor3(X, Q * (Dq - tail), Dq - tail, B, Q, Dq - tail)
+    table = L.Tensor3(X + 0x100000, Q * tail, tail, 1, Q, tail)
+    latents = L.Tensor3(X + 0x200000, N * D, D, B, N, D)
+    stream = None
+    for resid, q16_hi in ((0, Q16), (1, None)):
+        ca = _fake_decoder(resid)
+        need = lib.pio_decoder_workspace_bytes(ca, None, B, Q, N)
+        assert need > 0
+        rec = L.DecoderCall(C.pointer(ca), None, Dq, C.pointer(query), C.pointer(table), C.pointer(latents), None,
+                            X + 0x300000, q16_hi, None, 0)
+        assert lib.pio_decoder_fwd(C.byref(rec), WS, need, stream) == -6, (resid, q16_hi)       # PIO_E_ARG
+        # (the record is otherwise in order: one byte less of workspace is what the call objects to first)
+        assert lib.pio_decoder_fwd(C.byref(rec), WS, need - 1, stream) == -4                    # PIO_E_WORKSPACE
+    assert lib.pio_decoder_fwd(None, WS, need, stream) == -6
+    assert lib.pio_encoder_fwd(None, WS, need, stream) == -6

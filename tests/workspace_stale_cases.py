@@ -100,11 +100,11 @@ _attn("kvfold_xtall", "fp16", "KVFOLD_XTALL", 1, 762, 762, 8, 100, [0, 0, 3, 0, 
 
 
 # ----------------------------------------------------------------------------------------------------
-# pio_self_attention_fwd_opts       (ln_fold: pio_call_opts_t.ln_fold; alias: `out` is `x`)
+# pio_self_attention_fwd            (ln_fold: pio_call_opts_t.ln_fold; alias: `out` is `x`)
 #   launches as tests/test_block_route_gpu.py: un-folded 2 casts, 4 flat GEMMs, 1 core; folded 1 row-statistics cast
 # ----------------------------------------------------------------------------------------------------
 def _self(id, policy, core, fold, C, H, B, N, ln_fold, launches, **kw):
-    _add(id=id, entry="self_attention_fwd_opts", policy=policy, plan="SelfPlan", cores=(core,), fold=fold, C=C, H=H, B=B, N=N,
+    _add(id=id, entry="self_attention_fwd", policy=policy, plan="SelfPlan", cores=(core,), fold=fold, C=C, H=H, B=B, N=N,
          ln_fold=ln_fold, launches=launches, **kw)
 
 
@@ -145,6 +145,7 @@ _cross("cross_same_input", "FLASH", 60, 60, 2, 33, 33, True, [0, 1, 3, 0, 0, 1, 
 
 # ----------------------------------------------------------------------------------------------------
 # encoders: L = 2 layers x 2 blocks (the ping-pong / in-place streams are reused inside one call), stride-0 latents
+#   one entry point, pio_encoder_fwd; a case's fields fill its record: tail (inputs_tail), per_block, ln_fold (opts), input_mask
 #   launches: cross-attend as above (un-fused: 3 casts, 5 flat + 1 batched, core) + 4 self-attend blocks
 # ----------------------------------------------------------------------------------------------------
 def _enc(id, entry, cores, fold, launches, C_in=44, M=100, N=33, D=60, H=2, policy="fp16", **kw):
@@ -156,17 +157,18 @@ _enc("encoder_input_mask", "encoder_fwd", ("XATTN", "QKV_FLASH"), "NONE", [0, 1,
      ragged="M 100, N 33, 44 / 60 channels on 48 / 64, dk 30 < 32")
 # un-masked single-head cross-attend over 200 keys for 33 stride-0 query rows: the K / V fold (Q, Q Wk, out, fc1, fc2; the
 # 16-bit transpose counts as a cast)
-_enc("encoder_split_tail_kvfold", "encoder_fwd_split", ("KVFOLD_XATTN", "QKV_FLASH"), "NONE",
+_enc("encoder_split_tail_kvfold", "encoder_fwd", ("KVFOLD_XATTN", "QKV_FLASH"), "NONE",
      [0, 0, 12, 0, 0, 5, 21, 0, 0], tail=6, ragged="M 100, N 33, inputs as 38 + 6 channels of a [1, M, 6] table")
-_enc("encoder_per_block_images", "encoder_fwd_blocks", ("KVFOLD_XATTN", "QKV_FLASH"), "NONE",
+_enc("encoder_per_block_images", "encoder_fwd", ("KVFOLD_XATTN", "QKV_FLASH"), "NONE",
      [0, 0, 12, 0, 0, 5, 21, 0, 0], per_block=1, ragged="M 100, N 33, 44 / 60 channels on 48 / 64")
 # the folded stack: ONE row-statistics cast for four blocks, the 16-bit residual stream updated in place
-_enc("encoder_opts_fold_stack", "encoder_fwd_opts", ("XATTN", "QKV_FLASH"), "SMALL", [0, 1, 4, 0, 0, 5, 21, 0, 0],
+_enc("encoder_opts_fold_stack", "encoder_fwd", ("XATTN", "QKV_FLASH"), "SMALL", [0, 1, 4, 0, 0, 5, 21, 0, 0],
      N=300, D=512, H=8, input_mask=True, ln_fold=0, ragged="M 100, N 300 (600 rows), 44 input channels on 48")
 
 
 # ----------------------------------------------------------------------------------------------------
 # decoders: one single-head cross-attend (queries x latents), optional final Linear on y16 rows of pitch padc(Dq)
+#   one entry point, pio_decoder_fwd; a case's fields fill its record: tail (query_tail), qcache (q16_hi / q16_lo), query_mask
 #   launches: LN_kv, LN_q, LN2 | q, k, out, fc1, fc2 (+ final) flat + V^T batched | the core
 # ----------------------------------------------------------------------------------------------------
 def _dec(id, entry, launches, final, resid, policy="fp16", Dq=60, D=44, Q=33, N=13, out=10, **kw):
@@ -178,9 +180,9 @@ _dec("decoder_final_query_mask", "decoder_fwd", [0, 1, 3, 0, 0, 1, 6, 0, 0], Tru
      ragged="Q 33, 13 latents, 60 query channels on y16 rows of pitch 64, 44 = dk < 48")
 _dec("decoder_no_final_query_mask", "decoder_fwd", [0, 1, 3, 0, 0, 1, 5, 0, 0], False, True, query_mask=True,
      ragged="Q 33, 13 latents, 60 / 44 channels on 64 / 48")
-_dec("decoder_split_query", "decoder_fwd_split", [0, 1, 3, 0, 0, 1, 6, 0, 0], True, False, tail=6,
+_dec("decoder_split_query", "decoder_fwd", [0, 1, 3, 0, 0, 1, 6, 0, 0], True, False, tail=6,
      ragged="Q 33, 13 latents, queries as 54 + 6 channels of a [1, Q, 6] table")
-_dec("decoder_qcache", "decoder_fwd_qcache", [0, 1, 3, 0, 0, 1, 6, 0, 0], True, False, policy="fp16x2af", q_bcast=True,
+_dec("decoder_qcache", "decoder_fwd", [0, 1, 3, 0, 0, 1, 6, 0, 0], True, False, policy="fp16x2af", q_bcast=True,
      qcache=True, launches_valid=[0, 1, 2, 0, 0, 1, 5, 0, 0],      # q16_valid = 1: no LayerNorm_q, no proj_q
      ragged="Q 33, 13 latents, stride-0 queries, the projected queries as a caller-owned (hi, lo) pair")
 
