@@ -594,6 +594,29 @@ int pio_flow_blend_tiles(const pio_flow_blend_t *p, float *out, int64_t on, int6
 int pio_flow_to_image(const float *flow, int64_t sn, int64_t sy, int64_t sx, int64_t sc, int32_t b, int32_t h, int32_t w,
                       float clip_flow, int32_t has_clip, int32_t bgr, uint8_t *out, uint32_t *rad_max, void *stream);
 
+/* Media samples from an fp32 model output (what example_multimodal.py of the reference does on the host behind forward:
+ * (np.clip(image, 0, 1) * 255).astype(np.uint8) frame by frame, (audio * 2**15).astype(np.int16)) as ONE launch.
+ * x: fp32, element (i, r, p, c) of [n, h, w, C] at x[i*sn + r*sy + p*sx + c*sc], read in place (the stride of a dimension
+ * of size 1 is not read); y: contiguous [n, h, w, C] of uint8 (PIO_MEDIA_U8) or int16 (PIO_MEDIA_S16); C in [1, 4].
+ *   PIO_MEDIA_U8:   v = x < 0 ? 0 : x > 1 ? 1 : x, and v = 0 for a NaN;   y[.., reverse ? C - 1 - c : c] = (uint8) trunc(fmul_rn(v, 255))
+ *                   -- numpy's fp32 bits of the expression above: -0.0 gives 0, 1 - ulp gives 254, 1 gives 255; reverse is
+ *                   the channel order OpenCV's writer wants;
+ *   PIO_MEDIA_S16:  t = fmul_rn(x, 32768) (exact);   y = trunc(t) saturated to [-32768, 32767], 0 for a NaN;  reverse must
+ *                   be 0 -- inside [-1, 1) numpy's (a * 2**15).astype(np.int16); outside it numpy's conversion is undefined
+ *                   (it wraps on common builds), here the sample SATURATES: 1.0 gives 32767, +-inf give 32767 / -32768.
+ * Every output depends on its own input element only.  A lane writes four consecutive pixels of the flat [n*h*w] list, as
+ * the widest vectors y's alignment allows where y is 4-byte aligned (the last, partial group element by element), as bytes
+ * / shorts throughout otherwise.  sc == 1, sx == C, rows and images adjacent and x 16-byte aligned reads 16-byte vectors;
+ * any other strides work, element by element.  Only the bytes of y are written.  No atomics, no workspace, no device
+ * allocation, no synchronisation; the call can be captured into a graph.
+ * PIO_E_ARG: NULL x / y, kind neither PIO_MEDIA_U8 nor PIO_MEDIA_S16, reverse with PIO_MEDIA_S16; PIO_E_SHAPE: n, h or w
+ * < 1, C outside [1, 4], h*w beyond 2^31 - 1, ceil(n*h*w / 1024) workgroups beyond 2^31 - 1; PIO_E_ALIGN: x not 4-byte
+ * aligned, an int16 y not 2-byte aligned.  A refused call launches nothing. */
+#define PIO_MEDIA_U8 0
+#define PIO_MEDIA_S16 1
+int pio_finish_media(const float *x, int64_t sn, int64_t sy, int64_t sx, int64_t sc, int32_t n, int32_t h, int32_t w,
+                     int32_t C, int32_t kind, int32_t reverse, void *y, void *stream);
+
 /* Input images: crop, bilinear resize (with or without antialiasing), channel reversal and (v - mean) / std of a list of
  * images as ONE launch.  nsrc (1 .. PIO_MAX_IMAGE_SOURCES) descriptors, each n images of C channels and H x W pixels of uint8
  * or fp32 read in place: element (i, c, y, x) at data[i*sb + c*sc + y*sy + x*sx] (element strides, all >= 0; the stride of

@@ -17,4 +17,11 @@ from .image_prep import prepare_images  # noqa: E402,F401
 # False sends them down the torch chain (image_prep.chain), which CPU tensors and whatever the plan declines take
 fused_image_prep = True
 
+from .media import to_frames, to_pcm16, top_labels  # noqa: E402,F401
+
+# to_frames / to_pcm16 of a CUDA fp32 tensor under the hip backend: pio_finish_media (one launch, the tensor read in place)
+# when True; False sends them down the torch restatement of the same formulas (media.restatement, the same bits), which
+# every other input takes
+fused_media = True
+
 __version__ = "0.1.0"

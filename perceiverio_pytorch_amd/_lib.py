@@ -141,6 +141,8 @@ PIO_MAX_IMAGE_SOURCES = 32
 PIO_IMAGE_MAX_REDUCTION = 40
 PIO_IMAGE_U8 = 0
 PIO_IMAGE_F32 = 1
+PIO_MEDIA_U8 = 0
+PIO_MEDIA_S16 = 1
 # output channels of pio_conv1x1_tokens: a lane keeps 4 C weights + 4 biases per 256 of them in registers
 PIO_CONV1X1_MAX_N = 1024
 
@@ -210,6 +212,7 @@ SIGNATURES = {
                                    _i32, _i32, _vp]),
     "pio_flow_blend_tiles": (C.c_int, [P(FlowBlend), _vp, _i64, _i64, _i64, _vp]),
     "pio_flow_to_image": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _f, _i32, _i32, _vp, _vp, _vp]),
+    "pio_finish_media": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "pio_prepare_images": (C.c_int, [P(ImageSource), _i32, _i32, _i32, _i32, _i32, _i32, P(_f), P(_f), _vp, _i64, _vp]),
     "pio_gemm_nt": (C.c_int, [P(Gemm), _vp]),
     "pio_softmax_rows": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f, _vp, _vp, _vp, _vp, _i32, _vp]),

@@ -233,6 +233,11 @@ int pio_flow_to_image(const float *flow, int64_t sn, int64_t sy, int64_t sx, int
     return flow_to_image_launch(flow, sn, sy, sx, sc, b, h, w, clip_flow, has_clip, bgr, out, rad_max, (hipStream_t)stream);
 }
 
+int pio_finish_media(const float *x, int64_t sn, int64_t sy, int64_t sx, int64_t sc, int32_t n, int32_t h, int32_t w,
+                     int32_t C, int32_t kind, int32_t reverse, void *y, void *stream) {
+    return finish_media_launch(x, sn, sy, sx, sc, n, h, w, C, kind, reverse, y, (hipStream_t)stream);
+}
+
 int pio_prepare_images(const pio_image_src_t *srcs, int32_t nsrc, int32_t C, int32_t oh, int32_t ow, int32_t antialias,
                        int32_t reverse_channels, const float *mean, const float *std, float *out, int64_t out_sb,
                        void *stream) {

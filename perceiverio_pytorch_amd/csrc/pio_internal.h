@@ -150,6 +150,9 @@ int flow_blend_tiles_launch(const pio_flow_blend_t *p, float *out, int64_t on, i
 // flow visualisation: the Middlebury colour wheel of a batch of flow fields, one maximum radius per image (two launches)
 int flow_to_image_launch(const float *flow, int64_t sn, int64_t sy, int64_t sx, int64_t sc, int b, int h, int w,
                          float clip_flow, int has_clip, int bgr, uint8_t *out, uint32_t *rad_max, hipStream_t s);
+// media samples: fp32 [n, h, w, C] read through strides -> clipped uint8 (optionally channel-reversed) or saturated int16
+int finish_media_launch(const float *x, int64_t sn, int64_t sy, int64_t sx, int64_t sc, int n, int h, int w, int C, int kind,
+                        int reverse, void *y, hipStream_t s);
 // input images: crop, bilinear resize (antialiased or not), channel reversal and (v - mean) / std of up to 32 sources
 int prepare_images_launch(const pio_image_src_t *srcs, int nsrc, int C, int oh, int ow, int antialias, int reverse,
                           const float *mean, const float *std, float *out, int64_t out_sb, hipStream_t s);

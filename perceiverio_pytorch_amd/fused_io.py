@@ -567,6 +567,43 @@ def vocab_topk(post, x, k, return_logits=False):
     return ids.long(), logprob, (None if logits is None else R.forward_only(logits, x, w, bias))
 
 
+def top_labels(logits, k):
+    """(ids int64 [.., k], probs fp32 [.., k]) of logits [.., V] from ONE pio_vocab_topk call in its selection mode -- the k
+    largest logits of every row, largest first, the lower id first among equal logits, probs = exp(logit - log-sum-exp) -- or
+    None when it declines: the torch backend, anything but a CUDA fp32 tensor with at least one row, V > 1024, k outside
+    [1, min(8, V)], 2^31 rows or more, an active range probe."""
+    if not gate(True, logits) or LP.range_active() or logits.dim() < 1:
+        return None
+    v = logits.shape[-1]
+    n = logits.numel() // v if v else 0
+    if not 1 <= v <= 1024 or not 1 <= k <= min(8, v) or not 1 <= n < 2 ** 31:
+        return None
+    dev, lead = logits.device, tuple(logits.shape[:-1])
+    flat = logits.detach().reshape(n, v).contiguous()
+    ids = torch.empty((n, k), dtype=torch.int32, device=dev)
+    logprob = torch.empty((n, k), dtype=torch.float32, device=dev)
+    R.call(dev, "pio_vocab_topk", None, 0, 0, None, 0, None, 1, n, v, 0, k, ids.data_ptr(), logprob.data_ptr(), None,
+           flat.data_ptr(), v)
+    return ids.long().reshape(lead + (k,)), R.forward_only(torch.exp(logprob).reshape(lead + (k,)), logits)
+
+
+def finish_media(on, x, kind, reverse=False):
+    """The media samples of an fp32 [n, h, w, C] view `x` from ONE pio_finish_media call: contiguous uint8 (kind
+    PIO_MEDIA_U8; reverse: channel c written to C - 1 - c) or int16 (PIO_MEDIA_S16) [n, h, w, C] on x's device, x read in
+    place through its strides -- or None when it declines: the switch off, the torch backend, anything but a 4-D CUDA fp32
+    tensor with 1 to 4 channels and no empty axis, h * w or the workgroup count beyond 2^31 - 1, a data pointer that is not
+    4-byte aligned."""
+    if not gate(on, x) or x.dim() != 4:
+        return None
+    n, h, w, c = x.shape
+    if min(n, h, w) < 1 or not 1 <= c <= 4 or h * w >= 2 ** 31 or n * h * w >= 2 ** 41 or x.data_ptr() % 4:
+        return None
+    y = torch.empty((n, h, w, c), dtype=torch.uint8 if kind == L.PIO_MEDIA_U8 else torch.int16, device=x.device)
+    sn, sy, sx, sc = x.stride()
+    R.call(x.device, "pio_finish_media", x.data_ptr(), sn, sy, sx, sc, n, h, w, c, kind, int(bool(reverse)), y.data_ptr())
+    return y
+
+
 def _covers(corners, length, size):
     """True when the intervals [c, c + length) of the corners cover [0, size)."""
     pos = 0

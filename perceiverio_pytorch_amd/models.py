@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from . import fused_io as FIO
 from . import image_prep
 from . import io_processors
+from . import media
 from . import runtime as R
 from .io_processors import (AudioPostprocessor, AudioPreprocessor, ClassificationPostprocessor,
                             EmbeddingPostprocessor, EmbeddingPreprocessor, FlowPostprocessor, ImagePreprocessor,
@@ -199,6 +200,34 @@ class ClassificationPerceiver(nn.Module):
         """img: (batch, channels, H, W) -> logits (batch, num_classes)."""
         with _policy_scope(self):
             return self.perceiver(img)
+
+    def classify(self, images: torch.Tensor, k: int = 5, return_logits: bool = False) -> "Labels":
+        """Labels(ids int64 [B, k], probs fp32 [B, k], logits [B, num_classes] or None): the k most probable classes, most
+        probable first (media.top_labels: on the device, nothing read back).  The forward of this call decodes query row 0
+        alone, whatever decode_row0_only says; the setting is restored afterwards, also when the forward raises."""
+        core = self.perceiver
+        saved = core.decoder_query_rows
+        core.decoder_query_rows = slice(0, 1)
+        try:
+            logits = self.forward(images)
+        finally:
+            core.decoder_query_rows = saved
+        ids, probs = media.top_labels(logits, k)
+        return Labels(ids, probs, logits if return_logits else None)
+
+
+class Labels(NamedTuple):
+    """classify(): ids int64 [B, k], probs fp32 [B, k] (softmax, most probable first), logits fp32 [B, num_classes] or None."""
+    ids: torch.Tensor
+    probs: torch.Tensor
+    logits: Optional[torch.Tensor]
+
+
+class Media(NamedTuple):
+    """MultiModalPerceiver.reconstruct: frames uint8 [B, T, H, W, 3], pcm int16 of the audio's shape, label logits [B, classes]."""
+    frames: torch.Tensor
+    pcm: torch.Tensor
+    label: torch.Tensor
 
 
 class Prediction(NamedTuple):
@@ -508,6 +537,32 @@ class MultiModalPerceiver(R.PackedOwner):
     def forward(self, images: torch.Tensor, audio: torch.Tensor, n_chunks: int = 128):
         with _policy_scope(self):
             return self._forward(images, audio, n_chunks)
+
+    def classify(self, images: torch.Tensor, audio: torch.Tensor, k: int = 5, return_logits: bool = False) -> "Labels":
+        """Labels(ids int64 [B, k], probs fp32 [B, k], logits [B, num_classes] or None) without the reconstruction: the label
+        is ONE query row and decoder rows are independent, so after the same preprocess + encode as forward the decoder runs
+        once on that row (no chunk loop, no video or audio query, no narrow heads, nothing kept in the query cache), then the
+        label head and media.top_labels.  forward's label is the mean of one estimate per chunk -- copies of this row."""
+        b = images.shape[0]
+        inputs = {"image": images, "audio": audio, "label": torch.zeros((b, self.num_classes), device=images.device)}
+        P = self.perceiver
+        with _policy_scope(self):
+            x, sizes, without_pos = P._multi_preprocessor(inputs, pos=None)
+            with precision(P.encoder_policy):
+                latents = P._encoder(x, P._encoder.latents(x))
+            query, _ = P.decoder_query(x, sizes, without_pos, modalities=("label",))
+            with precision(P.decoder_policy):
+                row = P._decoder(query, latents)
+                logits = P._output_postprocessors["label"](row, pos=None, modality_sizes=None)
+        ids, probs = media.top_labels(logits, k)
+        return Labels(ids, probs, logits if return_logits else None)
+
+    def reconstruct(self, images: torch.Tensor, audio: torch.Tensor, n_chunks: int = 128, bgr: bool = False) -> "Media":
+        """forward, then the outputs as the example writes them, made on the device: Media(frames uint8 [B, T, H, W, 3] --
+        clipped to [0, 1], times 255, truncated; bgr: in OpenCV's channel order --, pcm int16 of audio's shape -- times 2**15,
+        truncated, saturated --, label logits): two pio_finish_media launches behind forward, its image view read in place."""
+        out = self.forward(images, audio, n_chunks)
+        return Media(media.to_frames(out["image"], bgr=bgr, channels_first=True), media.to_pcm16(out["audio"]), out["label"])
 
     def prepare_video(self, frames, bgr: bool = True) -> torch.Tensor:
         """Decoded frames (a [T, H, W, 3] tensor or a list of [H, W, 3] ones, values 0 .. 255; bgr: in OpenCV's channel

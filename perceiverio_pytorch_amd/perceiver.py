@@ -492,15 +492,26 @@ class PerceiverIO(nn.Module):
     def _project_heads(self, outputs, query_sizes, into=None):
         return FIO.project_heads(self, outputs, query_sizes, into)
 
-    def decoder_query(self, inputs, modality_sizes, inputs_without_pos=None, subsampled_points=None):
+    def decoder_query(self, inputs, modality_sizes, inputs_without_pos=None, subsampled_points=None, modalities=None):
+        """`modalities` (None = all of them, which changes nothing): the names of the output queries to build -- those
+        segments only, in sorted order, by the chain of torch ops (never the fused launch, which builds every segment), with
+        the same bits for their rows (MultiModalPerceiver.classify: the label row alone)."""
         per_mod = restructure(modality_sizes, inputs)
         subsampled_points = subsampled_points or {}
-        fused = self._fused_decoder_query(inputs, subsampled_points)
-        if fused is not None:
-            return fused
+        if modalities is not None:
+            unknown = [m for m in modalities if m not in self._output_queries]
+            if unknown or len(modalities) < 1:
+                raise ValueError(f"decoder_query: modalities {list(modalities)!r} must name some of "
+                                 f"{sorted(self._output_queries.keys())}")
+        else:
+            fused = self._fused_decoder_query(inputs, subsampled_points)
+            if fused is not None:
+                return fused
         any_input = next(iter(per_mod.values()))
         queries = {}
         for m, make_query in self._output_queries.items():
+            if modalities is not None and m not in modalities:
+                continue
             wo = inputs_without_pos.get(m) if inputs_without_pos is not None else None
             src = per_mod.get(m)
             if src is None:      # a query without a matching input still needs batch size / device

@@ -33,6 +33,12 @@
     python tools/prep_bench.py --classify-front     the encoder hand-off of the 1x1-conv and pixel classifiers
                                                 (pio_conv1x1_tokens, pio_assemble_tokens) against the torch chain at B = 1, 8
                                                 and 32, and the whole forward with the switch on and off; prints one JSON line
+    python tools/prep_bench.py --media              to_frames / to_pcm16 (pio_finish_media) on the multimodal model's outputs
+                                                ([1, 16, 3, 224, 224] and [1, 30720, 1]) against .cpu().numpy() plus the
+                                                example's numpy expressions, with and without the copy of the samples to the
+                                                host, and the entry alone in TB/s; prints one JSON line
+    python tools/prep_bench.py --multimodal-classify   MultiModalPerceiver.classify against forward + softmax + topk at
+                                                B = 1 and B = 4, full size; prints one JSON line
 """
 import argparse
 import json
@@ -961,6 +967,131 @@ def classify_front(repeats, launches):
     print(json.dumps(result))
 
 
+def _host_clock(f, n):
+    import time
+    f()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        f()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n * 1e6
+
+
+def media(repeats, launches):
+    """to_frames on the multimodal model's image output ([1, 16, 3, 224, 224], the moveaxis view of [1, 16*224*224, 3]
+    storage) and to_pcm16 on its audio output ([1, 30720, 1]), both resident on the device:
+      device      -- perceiverio_pytorch_amd.to_frames / to_pcm16: one allocation and one launch; the samples stay on the
+                     device (device events around `launches` back-to-back calls after 3 warm-up calls)
+      entry       -- pio_finish_media alone into a resident output (timed the same way), with its TB/s over one read of the
+                     fp32 array and one write of the samples
+      entry_chw   -- frames only: the entry on a channels-first CONTIGUOUS copy of the image (the strided path at full size)
+      device+copy -- the public function, then .cpu() of the samples (host clock)
+      host        -- the example's path: .cpu().numpy(), then np.clip / * 255 / astype per frame, or (a * 2**15).astype
+                     (host clock, the copy synchronises)
+    `repeats` alternating runs each: median and (min, max) in microseconds."""
+    import numpy as np
+    import perceiverio_pytorch_amd as P
+    from perceiverio_pytorch_amd import _lib as L
+    lib, stream = L.lib(), torch.cuda.current_stream().cuda_stream
+    t, h, w = 16, 224, 224
+    store = torch.rand(1, t * h * w, 3, device=dev) * 1.2 - 0.1
+    image = store.reshape(1, t, h, w, 3).moveaxis(-1, -3)
+    planar = image.contiguous()
+    audio = torch.rand(1, 30720, 1, device=dev) * 2 - 1
+    frames = torch.empty(t, h, w, 3, dtype=torch.uint8, device=dev)
+    frames2 = torch.empty_like(frames)
+    pcm = torch.empty(30720, dtype=torch.int16, device=dev)
+
+    def entry_frames():
+        L.check(lib.pio_finish_media(store.data_ptr(), h * w * 3, w * 3, 3, 1, t, h, w, 3, L.PIO_MEDIA_U8, 0, frames.data_ptr(),
+                                     stream), "pio_finish_media")
+
+    def entry_chw():
+        L.check(lib.pio_finish_media(planar.data_ptr(), 3 * h * w, w, 1, h * w, t, h, w, 3, L.PIO_MEDIA_U8, 0,
+                                     frames2.data_ptr(), stream), "pio_finish_media")
+
+    def entry_pcm():
+        L.check(lib.pio_finish_media(audio.data_ptr(), 0, 0, 1, 1, 1, 1, 30720, 1, L.PIO_MEDIA_S16, 0, pcm.data_ptr(), stream),
+                "pio_finish_media")
+
+    def host_frames():
+        video = image.cpu().numpy()[0]
+        return [(np.clip(np.moveaxis(f, 0, -1), 0, 1) * 255).astype(np.uint8) for f in video]
+
+    def host_pcm():
+        return (audio.cpu().numpy()[0, :, 0] * 2 ** 15).astype(np.int16)
+    n_host = max(2, launches // 5)
+    work = {
+        "frames": {"device": lambda: timed(lambda: P.to_frames(image), launches),
+                   "entry": lambda: timed(entry_frames, launches), "entry_chw": lambda: timed(entry_chw, launches),
+                   "device+copy": lambda: _host_clock(lambda: P.to_frames(image).cpu(), n_host),
+                   "host": lambda: _host_clock(host_frames, n_host)},
+        "pcm": {"device": lambda: timed(lambda: P.to_pcm16(audio), launches), "entry": lambda: timed(entry_pcm, launches),
+                "device+copy": lambda: _host_clock(lambda: P.to_pcm16(audio).cpu(), n_host),
+                "host": lambda: _host_clock(host_pcm, n_host)},
+    }
+    entry_frames(), entry_chw(), entry_pcm()
+    torch.cuda.synchronize()
+    got = P.to_frames(image)
+    assert torch.equal(got[0], frames) and torch.equal(frames, frames2), "public function and raw entry disagree"
+    assert np.array_equal(got[0].cpu().numpy(), np.stack(host_frames())), "device frames differ from numpy's"
+    assert torch.equal(P.to_pcm16(audio).reshape(-1), pcm) and np.array_equal(pcm.cpu().numpy(), host_pcm())
+    result = {"tool": "tools/prep_bench.py --media", "repeats": repeats, "launches_per_repeat": launches,
+              "host_calls_per_repeat": n_host, "unit": "us", "image": [1, t, 3, h, w], "audio": [1, 30720, 1], "cases": {}}
+    need = {"frames": 5.0 * t * h * w * 3, "pcm": 6.0 * 30720}
+    for name, ways in work.items():
+        times = {k: [] for k in ways}
+        for _ in range(repeats):
+            for k, f in ways.items():
+                times[k].append(f())
+        case = {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in times.items()}
+        for k in ("entry", "entry_chw"):
+            if k in case:
+                case[k]["algorithm_bytes"] = need[name]
+                case[k]["TB_per_s_at_median"] = need[name] / (case[k]["median"] * 1e-6) / 1e12
+        result["cases"][name] = case
+    result["cases"]["frames"]["device"]["one_call"] = _kernel_launches(lambda: P.to_frames(image))
+    result["cases"]["pcm"]["device"]["one_call"] = _kernel_launches(lambda: P.to_pcm16(audio))
+    print(json.dumps(result))
+
+
+def multimodal_classify(repeats, launches):
+    """MultiModalPerceiver.classify (one decoder row, top-5 on the device) against what there was before it: forward (128
+    chunks), then softmax + topk of its label, at B = 1 and B = 4 on the full-size model.  Whole calls, device events around
+    `launches` / 4 back-to-back calls after 3 warm-up calls, three alternating runs each: the runs, min and max in
+    microseconds; and whether the two agree on the labels."""
+    from perceiverio_pytorch_amd.models import MultiModalPerceiver
+    torch.manual_seed(3)
+    model = MultiModalPerceiver().to(dev).eval()
+    n = max(2, launches // 4)
+    result = {"tool": "tools/prep_bench.py --multimodal-classify", "calls_per_run": n, "unit": "us", "cases": {}}
+    for b in (1, 4):
+        images, audio = torch.rand(b, 16, 3, 224, 224, device=dev), torch.rand(b, 30720, 1, device=dev) * 2 - 1
+
+        def before():
+            probs, ids = torch.softmax(model(images, audio)["label"], dim=-1).topk(5, dim=-1)
+            return ids, probs
+
+        def classify():
+            lab = model.classify(images, audio, k=5)
+            return lab.ids, lab.probs
+        ways = {"forward+softmax+topk": before, "classify": classify}
+        a, c = before(), classify()
+        runs = {k: [] for k in ways}
+        for _ in range(3):
+            for k, f in ways.items():
+                runs[k].append(timed(f, n))
+        case = {k: {"runs": v, "min": min(v), "max": max(v)} for k, v in runs.items()}
+        case["same_top5_ids"] = bool(torch.equal(a[0], c[0]))
+        case["max_abs_prob_difference"] = float((a[1] - c[1]).abs().max())
+        case["classify"]["one_call"] = _kernel_launches(classify)
+        result["cases"][f"B={b}"] = case
+        del images, audio
+        torch.cuda.empty_cache()
+    print(json.dumps(result))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--classify-front", action="store_true",
@@ -975,6 +1106,9 @@ if __name__ == "__main__":
     ap.add_argument("--flow-blend", action="store_true", help="time pio_flow_blend_tiles against the torch chain")
     ap.add_argument("--flow-blend-forward", action="store_true", help="time the whole tiled forward of the flow model")
     ap.add_argument("--flow-image", action="store_true", help="time flow_to_image on the device against the numpy path")
+    ap.add_argument("--media", action="store_true", help="time to_frames / to_pcm16 (pio_finish_media) against the numpy path")
+    ap.add_argument("--multimodal-classify", action="store_true",
+                    help="time MultiModalPerceiver.classify against forward + softmax + topk")
     ap.add_argument("--package-root", default=None, help="--flow-blend-forward: the checkout whose package is timed")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--launches", type=int, default=20)
@@ -1002,5 +1136,9 @@ if __name__ == "__main__":
             flow_blend_forward(args.repeats, args.launches)
         elif args.flow_image:
             flow_image(args.repeats, args.launches)
+        elif args.media:
+            media(args.repeats, args.launches)
+        elif args.multimodal_classify:
+            multimodal_classify(args.repeats, args.launches)
         else:
             conv_tail()
