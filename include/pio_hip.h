@@ -310,6 +310,38 @@ int pio_layernorm_cast(const pio_tensor3_t *x, const pio_layernorm_t *ln, void *
 int pio_layernorm_cast_cat(const pio_tensor3_t *x1, const pio_tensor3_t *x2, const pio_layernorm_t *ln, void *y,
                            void *y_lo, int32_t c_pad, int32_t dtype, void *stream);
 
+/* First pass of a LayerNorm-folded self-attend stack (pio_ln_fold_t), exposed for tests and tools: the fp32 residual stream
+ * x [rows, C] (contiguous rows) is cast -- NOT normalised -- to a 16-bit pair and its row statistics are left in the slot
+ * form the first consumer GEMM reads (pio_gemm_t.ln_part):
+ *   y16[r, c]       = rn(x[r, c]),   y16_lo[r, c] = rn(x[r, c] - float(y16[r, c]))        (y16_lo optional: NULL = not written)
+ *   part[r][s][0]   = sum of x[r, c],  part[r][s][1] = sum of x[r, c]^2  over the slot_w columns c in [s slot_w, (s+1) slot_w)
+ * with s < C / slot_w: part is [rows][C / slot_w][2] fp32, dense.  slot_w = 128 is the form gemm_nt_wide consumes, 64 the
+ * tile kernels'.  The sums are fp32, four columns of a lane first, then a tree over the lanes of the slot; the squares may
+ * be fused into the sum.  With integer-valued x every sum is exact (as pio_gemm_t's producer); a non-finite or overflowing
+ * element makes the sum of squares of ITS slot non-finite and nothing else (the range guard of the fold reads that).
+ *   read:    x rows < rows, columns < C -- nothing behind the last row;
+ *   written: rows < rows x columns < C of y16 (and y16_lo), every slot of part of rows < rows; nothing behind them, and
+ *            y16_lo == NULL is never touched.  One wave per row, four rows a workgroup: rows need not be a multiple of 4.
+ * No workspace, no device allocation, no synchronisation.
+ * PIO_E_ARG: NULL x / y16 / part, rows <= 0, unknown dtype; PIO_E_SHAPE: C <= 0 or C % 256 != 0, slot_w neither 64 nor 128;
+ * PIO_E_ALIGN: x not 16-byte, y16 / y16_lo / part not 8-byte aligned.  Tested in that order.  A refused call launches
+ * nothing. */
+int pio_rowstats_cast(const float *x, int64_t rows, int32_t C, int32_t slot_w, void *y16, void *y16_lo, float *part,
+                      int32_t dtype, void *stream);
+
+/* The V^T operand of a K / V-folded cross-attend (pio_attention_t.kq / vo), exposed for tests and tools: a batched transpose
+ * of a 16-bit array, pure data movement on the bit patterns (NaN payloads and -0 included; no dtype):
+ *   vt[b][c][t] = x[b][t][c]   for b < B, c < C, t < T;      vt[b][c][t] = +0   for T <= t < tkv
+ * x: [B][T][ldx] (row pitch ldx >= C elements, sample stride T * ldx), vt: [B][C][tkv] dense.  The zero columns are what
+ * the cross-attention cores require behind key T - 1 of V^T (pio_flash_attention_pair); tkv may exceed T by whole tiles.
+ *   read:    x rows < T of every sample, columns < C -- never the pitch columns [C, ldx), never a row behind T - 1 of the
+ *            last sample;
+ *   written: all B * C * tkv elements of vt and nothing else.
+ * 64 x 64 tiles through LDS, 16-byte accesses on both sides.  No workspace, no device allocation, no synchronisation.
+ * PIO_E_ARG: NULL x / vt, B, T or C <= 0; PIO_E_SHAPE: C, ldx or tkv not a multiple of 8, tkv < T, B > 65535;
+ * PIO_E_ALIGN: x or vt not 16-byte aligned.  Tested in that order.  A refused call launches nothing. */
+int pio_transpose16(const void *x, int64_t ldx, int32_t B, int32_t T, int32_t C, void *vt, int64_t tkv, void *stream);
+
 /* Tail of Conv2DDownsample (processor_utils.py:163-180) in one pass over the conv's output x [B,C,H,W] fp32:
  * y[b, oh*OW + ow, c] = max over the 3x3 stride-2 TF-"SAME" window of relu(x * scale[c] + shift[c]) -- eval-mode
  * BatchNorm folded into (scale, shift) = (gamma / sqrt(var + eps), beta - mean * scale), or (1, 0) without one.

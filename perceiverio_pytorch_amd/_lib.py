@@ -199,6 +199,8 @@ SIGNATURES = {
     "pio_pack_linear": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "pio_layernorm_cast": (C.c_int, [P(Tensor3), P(LayerNorm), _vp, _vp, _i32, _i32, _vp]),
     "pio_layernorm_cast_cat": (C.c_int, [P(Tensor3), P(Tensor3), P(LayerNorm), _vp, _vp, _i32, _i32, _vp]),
+    "pio_rowstats_cast": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "pio_transpose16": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
     "pio_bn_relu_maxpool_tokens": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "pio_flow_patch_tokens": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32,
                                         _i32, _i32, _vp]),

@@ -178,6 +178,15 @@ int pio_layernorm_cast_cat(const pio_tensor3_t *x1, const pio_tensor3_t *x2, con
     return layernorm_cast_cat_launch(*x1, *x2, *ln, y, y_lo, c_pad, dtype, (hipStream_t)stream);
 }
 
+int pio_rowstats_cast(const float *x, int64_t rows, int32_t C, int32_t slot_w, void *y16, void *y16_lo, float *part,
+                      int32_t dtype, void *stream) {
+    return rowstats_cast_launch(x, rows, C, slot_w, y16, y16_lo, part, dtype, (hipStream_t)stream);
+}
+
+int pio_transpose16(const void *x, int64_t ldx, int32_t B, int32_t T, int32_t C, void *vt, int64_t tkv, void *stream) {
+    return transpose16_launch(x, ldx, B, T, C, vt, tkv, (hipStream_t)stream);
+}
+
 int pio_bn_relu_maxpool_tokens(const float *x, const float *scale, const float *shift, float *y, int32_t B, int32_t C,
                                int32_t H, int32_t W, int32_t pad_top, int32_t pad_left, void *stream) {
     return bn_relu_pool_nhwc_launch(x, scale, shift, y, B, C, H, W, pad_top, pad_left, (hipStream_t)stream);

@@ -287,8 +287,8 @@ int rowstats_cast_launch(const float *x, int64_t rows, int C, int slot_w, void *
     if (C <= 0 || (C % 256) || (slot_w != 64 && slot_w != 128)) return PIO_E_SHAPE;
     if (((uintptr_t)x & 15) || ((uintptr_t)y16 & 7) || ((uintptr_t)part & 7)) return PIO_E_ALIGN;
     if ((uintptr_t)y16_lo & 7) return PIO_E_ALIGN;
+    if (!rows_dtype_ok(dtype)) return PIO_E_ARG;  // (in front of the ProfScope: a refused call records no launch)
     ProfScope prof(PROF_LAYERNORM, 0.0, (double)rows * C * (y16_lo ? 8.0 : 6.0), s);
-    if (!rows_dtype_ok(dtype)) return PIO_E_ARG;
     for_dtype(dtype, [&](auto dt) {
         constexpr int DT = decltype(dt)::value;
         typedef typename Op<DT>::T OT;
