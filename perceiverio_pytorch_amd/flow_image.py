@@ -98,7 +98,7 @@ def flow_to_image(flow: torch.Tensor, clip_flow: Optional[float] = None, convert
         img = torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev)
         rad_max = torch.empty(b, dtype=torch.int32, device=dev)
         sn, sy, sx, sc = f4.stride()
-        R.call(dev, "pio_flow_to_image", f4.data_ptr(), sn, sy, sx, sc, b, h, w,
-               0.0 if clip_flow is None else float(clip_flow), clip_flow is not None, bool(convert_to_bgr),
-               img.data_ptr(), rad_max.data_ptr())
+        R.call_named(dev, "pio_flow_to_image", flow=f4.data_ptr(), sn=sn, sy=sy, sx=sx, sc=sc, b=b, h=h, w=w,
+                     clip_flow=0.0 if clip_flow is None else float(clip_flow), has_clip=clip_flow is not None,
+                     bgr=bool(convert_to_bgr), out=img.data_ptr(), rad_max=rad_max.data_ptr())
     return img[0] if flow.dim() == 3 else img

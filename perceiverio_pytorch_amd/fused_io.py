@@ -73,9 +73,10 @@ def embed_tokens(prep, inputs):
     y = torch.empty((b, t, c), dtype=torch.float32, device=dev)
     tokens = torch.empty((b, t, c), dtype=torch.float32, device=dev) if prep.need_tokens else None
     flag = prep.bad_ids_flag(dev).zero_()
-    R.call(dev, "pio_embed_tokens", inputs.data_ptr(), inputs.element_size(), inputs.stride(0), table.data_ptr(),
-           table.stride(0), v, ptab.data_ptr(), ptab.stride(0), y.data_ptr(), t * c, c,
-           None if tokens is None else tokens.data_ptr(), t * c, c, flag.data_ptr(), b, t, c)
+    R.call_named(dev, "pio_embed_tokens", ids=inputs.data_ptr(), id_bytes=inputs.element_size(), ids_sb=inputs.stride(0),
+                 table=table.data_ptr(), ldt=table.stride(0), V=v, pos=ptab.data_ptr(), ldp=ptab.stride(0), y=y.data_ptr(),
+                 y_sb=t * c, ldy=c, tokens=None if tokens is None else tokens.data_ptr(), tok_sb=t * c, ldtok=c,
+                 bad_ids=flag.data_ptr(), B=b, T=t, C=c)
     y = R.forward_only(y, w, p)
     return y, (None if tokens is None else R.forward_only(tokens, w, p))
 
@@ -108,10 +109,10 @@ def flow_patch_tokens(prep, pair):
     pair = rows(pair) if w > 1 else pair        # (one pixel per image row: its stride is never used)
     ldy = (out + 3) // 4 * 4
     y = torch.empty((n, h * w, ldy), dtype=torch.float32, device=pair.device)
-    R.call(pair.device, "pio_flow_patch_tokens", pair[:, 0].data_ptr(), pair[:, 1].data_ptr(), pair.stride(0),
-           pair.stride(2), pair.stride(3), pair.stride(0), pair.stride(2), pair.stride(3),
-           None if wt is None else wt.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(), ldy, n, c, h,
-           w, out)
+    R.call_named(pair.device, "pio_flow_patch_tokens", frame0=pair[:, 0].data_ptr(), frame1=pair[:, 1].data_ptr(),
+                 sn0=pair.stride(0), sc0=pair.stride(2), sy0=pair.stride(3), sn1=pair.stride(0), sc1=pair.stride(2),
+                 sy1=pair.stride(3), w=None if wt is None else wt.data_ptr(), bias=None if bias is None else bias.data_ptr(),
+                 y=y.data_ptr(), ldy=ldy, N=n, C=c, H=h, W=w, out=out)
     return R.forward_only(y if ldy == out else y[:, :, :out], *deps)
 
 
@@ -149,8 +150,9 @@ def conv1x1_tokens(prep, x):
     w2 = rows(wt.reshape(n, c), min_stride=True)
     bias_c = None if bias is None else bias.detach().contiguous()
     y = torch.empty((b, m, n), dtype=torch.float32, device=dev)
-    R.call(dev, "pio_conv1x1_tokens", x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), x.stride(3), w2.data_ptr(),
-           w2.stride(0), None if bias_c is None else bias_c.data_ptr(), y.data_ptr(), n, m * n, b, c, h, w, s, n)
+    R.call_named(dev, "pio_conv1x1_tokens", x=x.data_ptr(), sb=x.stride(0), sc=x.stride(1), sy=x.stride(2), sx=x.stride(3),
+                 w=w2.data_ptr(), ldw=w2.stride(0), bias=None if bias_c is None else bias_c.data_ptr(), y=y.data_ptr(), ldy=n,
+                 sYb=m * n, B=b, C=c, H=h, W=w, s=s, N=n)
     return R.forward_only(y, x, wt, bias)
 
 
@@ -223,8 +225,8 @@ def bn_relu_pool_tokens(convnet, x):
         scale, shift = torch.ones(c, device=x.device), torch.zeros(c, device=x.device)
     pads = IO.same_padding(x.shape[1:], 3, 2)          # [left, right, top, bottom]
     y = torch.empty((b, ((h + 1) // 2) * ((w + 1) // 2), c), dtype=torch.float32, device=x.device)
-    R.call(x.device, "pio_bn_relu_maxpool_tokens", x.data_ptr(), scale.contiguous().data_ptr(),
-           shift.contiguous().data_ptr(), y.data_ptr(), b, c, h, w, pads[2], pads[0])
+    R.call_named(x.device, "pio_bn_relu_maxpool_tokens", x=x.data_ptr(), scale=scale.contiguous().data_ptr(),
+                 shift=shift.contiguous().data_ptr(), y=y.data_ptr(), B=b, C=c, H=h, W=w, pad_top=pads[2], pad_left=pads[0])
     return R.forward_only(y, x, *convnet.parameters())     # (x carries the network input's and the convs' autograd)
 
 
@@ -320,7 +322,8 @@ def assemble_tokens(mm, inputs, pos):
     if segs is None:
         return None
     y = torch.empty((batch, mtot, cc), dtype=torch.float32, device=dev)
-    R.call(dev, "pio_assemble_tokens", segs, len(names), y.data_ptr(), cc, mtot * cc, batch, mtot, cc)
+    R.call_named(dev, "pio_assemble_tokens", segs=segs, nseg=len(names), y=y.data_ptr(), ldy=cc, sYb=mtot * cc, B=batch,
+                 Mtot=mtot, Cc=cc)
     x = R.forward_only(y, *deps)
     without_pos = {m: views[m] if s.token else x[:, s.row0:s.row0 + s.M, :s.C1] for m, s in plan.items()}
     return x, {m: s.M for m, s in plan.items()}, without_pos
@@ -408,7 +411,7 @@ def build_queries(io, inputs, subsampled_points):
     if n_fourier < 1 or segs is None:
         return None
     y = torch.empty((1, qtot, cq), dtype=torch.float32, device=dev)
-    R.call(dev, "pio_build_queries", segs, len(names), y.data_ptr(), cq, qtot, cq)
+    R.call_named(dev, "pio_build_queries", segs=segs, nseg=len(names), y=y.data_ptr(), ldy=cq, Qtot=qtot, Cq=cq)
     y = R.forward_only(y, *deps)
     return torch.broadcast_to(y, (inputs.shape[0], qtot, cq)), {m: plan[m].M for m in names}
 
@@ -494,8 +497,8 @@ def project_heads(io, outputs, query_sizes, into=None):
         plan.append(seg)
         keep += [w, b, y]
     if plan:
-        R.call(dev, "pio_project_heads", (L.HeadSegment * len(plan))(*plan), len(plan), outputs.data_ptr(),
-               outputs.stride(0) if batch > 1 else 0, outputs.stride(1), batch, qtot, k)
+        R.call_named(dev, "pio_project_heads", segs=(L.HeadSegment * len(plan))(*plan), nseg=len(plan), x=outputs.data_ptr(),
+                     x_sb=outputs.stride(0) if batch > 1 else 0, ldx=outputs.stride(1), B=batch, Q=qtot, K=k)
     per_mod = PV.restructure(query_sizes, outputs)
     result = {}
     for m, post in posts.items():
@@ -554,13 +557,14 @@ def vocab_topk(post, x, k, return_logits=False):
         wr = rows(w, min_stride=True, stride4=True, aligned=True)
         br = bias.detach().contiguous()
         logits = torch.empty((b, p, v), dtype=torch.float32, device=dev) if return_logits else None
-        R.call(dev, "pio_vocab_topk", xr.data_ptr(), xr.stride(0) if b > 1 else 0, xr.stride(1) if p > 1 else xr.shape[2],
-               wr.data_ptr(), wr.stride(0) if v > 1 else wr.shape[1], br.data_ptr(), b, p, v, xr.shape[2], k, ids.data_ptr(),
-               logprob.data_ptr(), None, None if logits is None else logits.data_ptr(), v)
+        R.call_named(dev, "pio_vocab_topk", x=xr.data_ptr(), x_sb=xr.stride(0) if b > 1 else 0,
+                     ldx=xr.stride(1) if p > 1 else xr.shape[2], w=wr.data_ptr(), ldw=wr.stride(0) if v > 1 else wr.shape[1],
+                     bias=br.data_ptr(), B=b, Q=p, V=v, K=xr.shape[2], k=k, ids=ids.data_ptr(), logprob=logprob.data_ptr(),
+                     lse=None, logits=None if logits is None else logits.data_ptr(), ldl=v)
     else:
         logits = post(x).contiguous()
-        R.call(dev, "pio_vocab_topk", None, 0, 0, None, 0, None, b, p, v, 0, k, ids.data_ptr(), logprob.data_ptr(), None,
-               logits.data_ptr(), v)
+        R.call_named(dev, "pio_vocab_topk", x=None, x_sb=0, ldx=0, w=None, ldw=0, bias=None, B=b, Q=p, V=v, K=0, k=k,
+                     ids=ids.data_ptr(), logprob=logprob.data_ptr(), lse=None, logits=logits.data_ptr(), ldl=v)
         if not return_logits:
             logits = None
     logprob = R.forward_only(logprob, x, w, bias)
@@ -582,8 +586,8 @@ def top_labels(logits, k):
     flat = logits.detach().reshape(n, v).contiguous()
     ids = torch.empty((n, k), dtype=torch.int32, device=dev)
     logprob = torch.empty((n, k), dtype=torch.float32, device=dev)
-    R.call(dev, "pio_vocab_topk", None, 0, 0, None, 0, None, 1, n, v, 0, k, ids.data_ptr(), logprob.data_ptr(), None,
-           flat.data_ptr(), v)
+    R.call_named(dev, "pio_vocab_topk", x=None, x_sb=0, ldx=0, w=None, ldw=0, bias=None, B=1, Q=n, V=v, K=0, k=k,
+                 ids=ids.data_ptr(), logprob=logprob.data_ptr(), lse=None, logits=flat.data_ptr(), ldl=v)
     return ids.long().reshape(lead + (k,)), R.forward_only(torch.exp(logprob).reshape(lead + (k,)), logits)
 
 
@@ -600,7 +604,8 @@ def finish_media(on, x, kind, reverse=False):
         return None
     y = torch.empty((n, h, w, c), dtype=torch.uint8 if kind == L.PIO_MEDIA_U8 else torch.int16, device=x.device)
     sn, sy, sx, sc = x.stride()
-    R.call(x.device, "pio_finish_media", x.data_ptr(), sn, sy, sx, sc, n, h, w, c, kind, int(bool(reverse)), y.data_ptr())
+    R.call_named(x.device, "pio_finish_media", x=x.data_ptr(), sn=sn, sy=sy, sx=sx, sc=sc, n=n, h=h, w=w, C=c, kind=kind,
+                 reverse=int(bool(reverse)), y=y.data_ptr())
     return y
 
 
@@ -658,7 +663,8 @@ def blend_tiles(model, pair, h, w, min_overlap):
     p.N, p.H, p.W, p.h, p.w = b, model.H, model.W, h, w
     out = torch.empty((b, 2, h, w), dtype=torch.float32, device=dev)
     # (PIO_E_SHAPE / PIO_E_ALIGN: a refusal, nothing was launched -- the chain)
-    if not R.call(dev, "pio_flow_blend_tiles", p, out.data_ptr(), 2 * h * w, h * w, w, declines=(-1, -2)):
+    if not R.call_named(dev, "pio_flow_blend_tiles", p=p, out=out.data_ptr(), on=2 * h * w, oc=h * w, oy=w,
+                        declines=(L.PIO_E_SHAPE, L.PIO_E_ALIGN)):
         return None
     return R.forward_only(out, *keep)
 
@@ -707,7 +713,7 @@ def prepare_images(on, items, c, oh, ow, antialias, reverse, mean, std, out):
             d.sb, d.sc, d.sy, d.sx = x.stride()
             d.n, d.C, d.H, d.W = x.shape
             d.y0, d.x0, d.ch, d.cw = y0, x0, ch, cw
-        R.call(dev, "pio_prepare_images", arr, len(group), c, oh, ow, int(bool(antialias)), int(bool(reverse)), mean_c,
-               std_c, out.data_ptr() + 4 * done * sb, sb)
+        R.call_named(dev, "pio_prepare_images", srcs=arr, nsrc=len(group), C=c, oh=oh, ow=ow, antialias=int(bool(antialias)),
+                     reverse_channels=int(bool(reverse)), mean=mean_c, std=std_c, out=out.data_ptr() + 4 * done * sb, out_sb=sb)
         done += sum(x.shape[0] for x, _ in group)
     return out

@@ -124,7 +124,8 @@ class PerceiverEncoder(R.PackedOwner):
         LP.expect("cross", *["stack"] * (Lyr * self._num_blocks))    # (one attention call per block, this order)
         LP.mark_range("cross")           # (range probe: the library marks "stack" behind the cross-attend itself)
         try:
-            ws = R.workspace(dev, lib.pio_encoder_workspace_bytes(cross, layers, Lyr, B, M, N))
+            ws = R.workspace(dev, lib.pio_encoder_workspace_bytes(*L.arguments(
+                "pio_encoder_workspace_bytes", (), dict(cross=cross, layers=layers, L=Lyr, B=B, M=M, N=N))))
             R.call(dev, "pio_encoder_fwd", C.byref(rec), ws.data_ptr(), ws.numel())
         finally:
             LP.mark_range("attention")
@@ -232,7 +233,8 @@ class PerceiverDecoder(R.PackedOwner):
         qm, qm_ptr = R.mask_u8(query_mask, (B, Q), dev)
         out = torch.empty((B, Q, out_ch), dtype=torch.float32, device=dev)
         fin_ptr = C.pointer(fin.desc) if fin is not None else None
-        ws = R.workspace(dev, lib.pio_decoder_workspace_bytes(cross, fin_ptr, B, Q, N))
+        ws = R.workspace(dev, lib.pio_decoder_workspace_bytes(*L.arguments(
+            "pio_decoder_workspace_bytes", (), dict(cross=cross, final_layer=fin_ptr, B=B, Q=Q, N=N))))
         qhi = qlo = None
         valid = 0
         if q_cache is not None and not self._use_query_residual and query_tail is None:

@@ -402,10 +402,11 @@ class PackedLinear:
             b = bias.detach()
             if b.dtype != torch.float32 or not b.is_contiguous():
                 b = b.float().contiguous()
-        L.check(lib.pio_pack_linear(w.data_ptr(), b.data_ptr() if b is not None else None, out, inn, inn,
-                                    row_heads, col_heads, self.hi.data_ptr(),
-                                    self.lo.data_ptr() if two_pass else None, self.bias.data_ptr(), 0, self.k,
-                                    dtype, stream_ptr(dev)), "pio_pack_linear")
+        L.check(lib.pio_pack_linear(*L.arguments("pio_pack_linear", (), dict(
+            w=w.data_ptr(), bias=b.data_ptr() if b is not None else None, out=out, in_=inn, ldw=inn,
+            row_heads=row_heads, col_heads=col_heads, dst_hi=self.hi.data_ptr(),
+            dst_lo=self.lo.data_ptr() if two_pass else None, dst_bias=self.bias.data_ptr(), dst_row0=0, k_pad=self.k,
+            dtype=dtype, stream=stream_ptr(dev)))), "pio_pack_linear")
         self.desc = L.Linear(self.hi.data_ptr(), self.lo.data_ptr() if two_pass else None, self.bias.data_ptr(),
                              self.n, self.k)
 
@@ -442,10 +443,11 @@ class PackedStack:
                 raise ValueError("stacked linears need equal in_features")
             wf = w.detach().float().contiguous()
             bf = b.detach().float().contiguous() if b is not None else None
-            L.check(lib.pio_pack_linear(wf.data_ptr(), bf.data_ptr() if bf is not None else None, w.shape[0], inn,
-                                        inn, row_heads, 1, self.hi.data_ptr(),
-                                        self.lo.data_ptr() if fl else None, self.bias.data_ptr(), r0, self.k,
-                                        dtype, stream_ptr(dev)), "pio_pack_linear")
+            L.check(lib.pio_pack_linear(*L.arguments("pio_pack_linear", (), dict(
+                w=wf.data_ptr(), bias=bf.data_ptr() if bf is not None else None, out=w.shape[0], in_=inn, ldw=inn,
+                row_heads=row_heads, col_heads=1, dst_hi=self.hi.data_ptr(), dst_lo=self.lo.data_ptr() if fl else None,
+                dst_bias=self.bias.data_ptr(), dst_row0=r0, k_pad=self.k, dtype=dtype, stream=stream_ptr(dev)))),
+                "pio_pack_linear")
             if not fl:
                 lo_row0 = r0 + nr
             r0 += nr
@@ -580,6 +582,14 @@ def call(dev, name, *args, stream=None, declines=()):
     return True
 
 
+def call_named(dev, name, *args, stream=None, declines=(), **named):
+    """`call` with the arguments behind `args` given by the header's parameter names: _lib.arguments lays them out and
+    refuses a wrong, missing or repeated name before anything runs.  The header's trailing `stream` is the one `call`
+    fills; `call` itself sees the arguments in the header's order."""
+    argv = L.arguments(name, args, {**named, "stream": stream})
+    return call(dev, name, *argv[:-1], stream=argv[-1], declines=declines)
+
+
 def layernorm_desc(ln: torch.nn.LayerNorm, keep: list) -> L.LayerNorm:
     w, b = ln.weight.detach(), ln.bias.detach()
     if w.dtype != torch.float32:
@@ -607,7 +617,8 @@ def hip_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     x16 = torch.empty((rows, lin.k), dtype=tdt, device=dev)
     x16lo = torch.empty((rows, lin.k), dtype=tdt, device=dev) if split else None
     out = torch.empty((rows, n_out), dtype=torch.float32, device=dev)
-    call(dev, "pio_layernorm_cast", tensor3(x3), None, x16.data_ptr(), x16lo.data_ptr() if split else None, lin.k, dtype)
+    call_named(dev, "pio_layernorm_cast", x=tensor3(x3), ln=None, y=x16.data_ptr(), y_lo=x16lo.data_ptr() if split else None,
+               c_pad=lin.k, dtype=dtype)
     g = L.Gemm()
     g.A, g.B = x16.data_ptr(), lin.hi.data_ptr()
     g.A_lo = x16lo.data_ptr() if split else None

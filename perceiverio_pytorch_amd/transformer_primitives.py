@@ -70,11 +70,12 @@ def _no_training_dropout(mod: nn.Module, *probs: float) -> None:
         raise NotImplementedError("the HIP path is forward/inference only: call .eval() or use dropout_prob=0")
 
 
-def _block_call(entry, ws_entry, ws_args, d, tensors, dims, out_channels, mask, bias, return_matrix, deps, opts=()):
+def _block_call(entry, ws_entry, ws_args, d, tensors, dims, out_channels, mask, bias, return_matrix, deps, **opts):
     """The common tail of the three block forwards: full mask to bytes, bias broadcast over `dims` = (B, H, Tq, Tk), the
-    `out` / `probs` buffers, the workspace of `ws_entry(d, *ws_args)`, the launch of `entry` on `tensors`, and the
-    result tied to `deps` (runtime.forward_only).  Returns out, or (probs, out) with `return_matrix`.  `opts`: what the
-    entry takes between its outputs and its workspace (pio_self_attention_fwd: its pio_call_opts_t pointer)."""
+    `out` / `probs` buffers, the workspace of `ws_entry(d, *ws_args)`, the launch of `entry` on `tensors` (its descriptor
+    and input tensors lead every block prototype; the rest goes by name), and the result tied to `deps`
+    (runtime.forward_only).  Returns out, or (probs, out) with `return_matrix`.  `opts`: what the entry takes beyond the
+    common parameters (pio_self_attention_fwd: opts, its pio_call_opts_t pointer)."""
     B, H, Tq, Tk = dims
     dev = tensors[0].device
     fm, fm_ptr = R.mask_u8(mask, (B, Tq, Tk), dev)
@@ -85,9 +86,10 @@ def _block_call(entry, ws_entry, ws_args, d, tensors, dims, out_channels, mask, 
     probs = torch.empty(dims, dtype=torch.float32, device=dev) if return_matrix else None
     ws = R.workspace(dev, getattr(L.lib(), ws_entry)(d, *ws_args))
     LP.expect("attention")
-    R.call(dev, entry, d, *[R.tensor3(t) for t in tensors], None, None, fm_ptr,
-           bias_t.data_ptr() if bias_t is not None else None, out.data_ptr(),
-           probs.data_ptr() if probs is not None else None, *opts, ws.data_ptr(), ws.numel())
+    R.call_named(dev, entry, d, *[R.tensor3(t) for t in tensors], kv_mask=None, q_mask=None, full_mask=fm_ptr,
+                 attention_bias=bias_t.data_ptr() if bias_t is not None else None, out=out.data_ptr(),
+                 probs_out=probs.data_ptr() if probs is not None else None, workspace=ws.data_ptr(), workspace_bytes=ws.numel(),
+                 **opts)
     out = R.forward_only(out, *deps)
     return (probs, out) if return_matrix else out
 
@@ -269,7 +271,8 @@ class MLP(_HipModule):
         out = torch.empty(x3.shape[:2] + (self.fc2.out_features,), dtype=torch.float32, device=dev)
         rows = x3.shape[0] * x3.shape[1]
         ws = R.workspace(dev, lib.pio_mlp_workspace_bytes(d, rows))
-        R.call(dev, "pio_mlp_fwd", d, R.tensor3(x3), out.data_ptr(), ws.data_ptr(), ws.numel())
+        R.call_named(dev, "pio_mlp_fwd", m=d, x=R.tensor3(x3), out=out.data_ptr(), workspace=ws.data_ptr(),
+                     workspace_bytes=ws.numel())
         out = R.forward_only(out, x, *self._params())
         return out.reshape(shape[:-1] + (self.fc2.out_features,))
 
@@ -386,7 +389,7 @@ class SelfAttention(_HipModule):
         B, N, D = x.shape
         return _block_call("pio_self_attention_fwd", "pio_self_attention_workspace_bytes", (B, N), self._desc(), (x,),
                            (B, self.attention._num_heads, N, N), D, attention_mask, attention_bias, return_matrix,
-                           (inputs,) + self._params(), opts=(None,))     # (NULL: the library's defaults)
+                           (inputs,) + self._params(), opts=None)     # (NULL: the library's defaults)
 
 
 # ==================================================================================================
