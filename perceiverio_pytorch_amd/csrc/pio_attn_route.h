@@ -1,8 +1,11 @@
 // Attention routing (host only, plain C++17: no HIP, no environment, no state): the shape tables of the fused attention
 // kernels, which core one attention call runs on and what its plan has to carve (attn_route / attn_plan), the variant of
-// the self-attention kernel a launch gets (flash_route), and the operand bundle the three launchers share.
-// pio_blocks.hip / pio_flash.hip launch what these return; tests/test_attn_route.py checks them on the CPU.
+// the self-attention kernel a launch gets (flash_route), the operand bundle the three launchers share, and the launch plan
+// of each of them (flash / xattn / xtall_launch_plan: the refusals in the order that decides a bad call's PIO_E_* code,
+// then the grid arithmetic).  pio_blocks.hip and the three launchers launch what these return; tests/test_attn_route.py
+// checks them on the CPU.
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -117,8 +120,9 @@ struct AttnOperands {
     int64_t ldq, ldk, ldvt, ldo;           // row pitches (elements); VT is V^T [B][H*dvp][keys] unless v_rowmajor
     int64_t sQb, sKb, sVb, sOb;            // batch strides (elements); sQb = 0 for batch-invariant queries
 };
+inline bool attn_lo_halves_paired(const AttnOperands &t) { return (!t.Q_lo) == (!t.K_lo); }
 inline int attn_operands_present(const AttnOperands &t) {
-    return (!t.Q || !t.K || !t.VT || !t.O || (!t.Q_lo) != (!t.K_lo)) ? PIO_E_ARG : PIO_OK;
+    return (!t.Q || !t.K || !t.VT || !t.O || !attn_lo_halves_paired(t)) ? PIO_E_ARG : PIO_OK;
 }
 // 16-byte operand rows / pointers (one LDS-DMA piece), 8-byte output rows
 inline int attn_operands_aligned(const AttnOperands &t) {
@@ -126,6 +130,112 @@ inline int attn_operands_aligned(const AttnOperands &t) {
         return PIO_E_ALIGN;
     const uintptr_t in = (uintptr_t)t.Q | (uintptr_t)t.K | (uintptr_t)t.VT | (uintptr_t)t.Q_lo | (uintptr_t)t.K_lo;
     return ((in & 15) || (((uintptr_t)t.O | (uintptr_t)t.O_lo) & 7)) ? PIO_E_ALIGN : PIO_OK;
+}
+
+// ---- launch plans of the three fused cores ---------------------------------------------------------------------------
+// Everything a launcher decides before it fills its kernel's parameter struct.  `err` first: the refusals come in the
+// launcher's own order, which is part of the C ABI's contract (a call that breaks two rules gets the first one's code).
+inline float attn_scale_log2(int dk_logical) { return 1.4426950408889634f / sqrtf((float)dk_logical); }  // log2(e) / sqrt(dk)
+// what the profiler books for one fused-core launch (S recomputed per dv slice counts once: the reference's flops)
+struct AttnWork { double flops, bytes; };
+inline AttnWork attn_work(int dkp, int dvp, int B, int H, int Tq, int Tk) {
+    return AttnWork{2.0 * B * H * (double)Tq * Tk * (dkp + dvp),
+                    2.0 * B * H * ((double)Tq * (dkp + dvp) + (double)Tk * (dkp + dvp))};
+}
+// The checks all three share, behind each launcher's shape table: operands present, the launcher's pair rule (its code,
+// PIO_OK when it has no objection), positive extents, alignment.
+inline int attn_launch_checks(const AttnOperands &t, int pair_err, bool extents_ok) {
+    if (attn_operands_present(t) != PIO_OK) return PIO_E_ARG;
+    if (pair_err != PIO_OK) return pair_err;
+    if (!extents_ok) return PIO_E_SHAPE;
+    return attn_operands_aligned(t);
+}
+constexpr int64_t kGridMax = 0x7fffffffLL, kOffsetLimit = 1ll << 31;  // workgroups of a 1-D grid; 32-bit element offsets
+
+// O_lo only with Q_lo / K_lo: the single-operand instantiations of the self-attention kernel write one half
+inline bool flash_o_lo_allowed(const AttnOperands &t) { return !t.O_lo || t.Q_lo; }
+struct FlashPlan {
+    int err;
+    FlashRoute route;
+    bool pair;      // Q and K as (hi, lo) pairs
+    int o_rows16;   // O rows are 16-byte aligned and leave as one half: the staged whole-row epilogue
+    int64_t grid;
+};
+inline FlashPlan flash_launch_plan(int dtype, int dkp, int dvp, const AttnOperands &t, int B, int H, int Tq, int Tk,
+                                   bool v_rowmajor, bool ksplit_on, int cu_budget) {
+    FlashPlan p = {};
+    p.pair = t.Q_lo != nullptr;
+    const int pair_err = !flash_o_lo_allowed(t) ? PIO_E_ARG
+                         : (p.pair && !flash_pair_supported(dtype, dkp, dvp)) ? PIO_E_SHAPE : PIO_OK;  // (never a silent single-operand run)
+    p.err = !flash_supported(dkp, dvp)
+                ? PIO_E_SHAPE
+                : attn_launch_checks(t, pair_err, B > 0 && H > 0 && Tq > 0 && Tk > 0 && (int64_t)B * H * ((Tq + 127) / 128) <= kGridMax);
+    if (p.err) return p;
+    p.route = p.pair ? flash_pair_route(dkp, dvp, B, H, Tq, Tk, v_rowmajor, ksplit_on, cu_budget)
+                     : flash_route(dkp, dvp, B, H, Tq, Tk, v_rowmajor, ksplit_on, cu_budget);
+    // (an output PAIR leaves through the per-lane 8-byte stores: the staged whole-row epilogue carries one half only)
+    p.o_rows16 = (!t.O_lo && t.ldo % 8 == 0 && t.sOb % 8 == 0 && ((uintptr_t)t.O & 15) == 0) ? 1 : 0;
+    p.grid = (int64_t)p.route.nqt * B * H;
+    return p;
+}
+
+struct XattnPlan {
+    int err;
+    XCfg cfg;
+    bool pair;
+    int nqt, nslice, nsplit, ntiles, tiles_per_split;
+    int64_t grid;
+    size_t part_o_off, part_ml_off;  // bytes into the scratch, behind the key-bit words (part_ml: key splits only)
+};
+inline XattnPlan xattn_launch_plan(int dtype, int dkp, int dvp, const AttnOperands &t, int B, int H, int Tq, int Tk,
+                                   bool has_kv_mask, bool has_scratch) {
+    XattnPlan p = {};
+    const XCfg *c = xattn_cfg(dkp, dvp);
+    p.pair = t.Q_lo != nullptr;
+    const int pair_err = (p.pair && !xattn_pair_supported(dtype, dkp, dvp)) ? PIO_E_SHAPE : PIO_OK;  // (never a silent single-operand run)
+    p.err = !c ? PIO_E_SHAPE
+               : attn_launch_checks(t, pair_err, B > 0 && H > 0 && Tq > 0 && Tk > 0 && !(dkp & 7) && !(dvp & 7));
+    if (p.err) return p;
+    p.cfg = *c;
+    auto refuse = [&p](int err) { p.err = err; return p; };
+    // (the kernel's per-lane source offsets are 32-bit element offsets)
+    if (t.ldvt < 8 || 32 * t.ldk >= kOffsetLimit || (int64_t)dvp * t.ldvt >= kOffsetLimit) return refuse(PIO_E_SHAPE);
+    p.nslice = (dvp + c->dvs - 1) / c->dvs;
+    p.nqt = (Tq + 127) / 128;
+    p.nsplit = xattn_splits(dkp, dvp, B, H, Tq, Tk);
+    p.ntiles = (Tk + 31) / 32;
+    p.tiles_per_split = (p.ntiles + p.nsplit - 1) / p.nsplit;
+    if ((p.nsplit > 1 || has_kv_mask) && !has_scratch) return refuse(PIO_E_WORKSPACE);
+    if (t.ldvt % 32) return refuse(PIO_E_ALIGN);  // V^T rows are read in whole 32-key tiles (zero padded by the caller)
+    p.grid = (int64_t)B * H * p.nqt * p.nslice * p.nsplit;
+    if (p.grid > kGridMax) return refuse(PIO_E_SHAPE);
+    p.part_o_off = keybits_bytes(B, Tk);
+    p.part_ml_off = p.part_o_off + (size_t)B * H * p.nsplit * Tq * dvp * sizeof(float);
+    return p;
+}
+
+// the tall-head kernel has no pair-operand instantiation
+inline bool xtall_takes(int dkp, int dvp, int Tk, const AttnOperands &t) { return xtall_supported(dkp, dvp, Tk) && !t.Q_lo; }
+struct XtallPlan {
+    int err;
+    int nqt, nka, npass;  // query tiles of 128 rows, dk chunks of 32, dv passes of 256
+    int64_t grid;
+};
+inline XtallPlan xtall_launch_plan(int dkp, int dvp, const AttnOperands &t, int B, int H, int Tq, int Tk, bool has_kv_mask,
+                                   bool has_scratch) {
+    XtallPlan p = {};
+    p.err = !xtall_takes(dkp, dvp, Tk, t) ? PIO_E_SHAPE : attn_launch_checks(t, PIO_OK, B > 0 && H > 0 && Tq > 0);
+    if (p.err) return p;
+    auto refuse = [&p](int err) { p.err = err; return p; };
+    if (t.ldvt < 64 || (int64_t)Tk * t.ldk >= kOffsetLimit || (int64_t)Tq * t.ldq >= kOffsetLimit || 256 * t.ldvt >= kOffsetLimit)
+        return refuse(PIO_E_SHAPE);
+    if (has_kv_mask && !has_scratch) return refuse(PIO_E_WORKSPACE);
+    p.nqt = (Tq + 127) / 128;
+    p.nka = dkp / 32;
+    p.npass = dvp / 256;
+    p.grid = (int64_t)B * H * p.nqt;
+    if (p.grid > kGridMax) return refuse(PIO_E_SHAPE);
+    return p;
 }
 
 // ---- which core one attention call runs on ------------------------------------------------------------------------

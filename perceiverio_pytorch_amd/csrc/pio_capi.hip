@@ -287,18 +287,18 @@ int pio_flash_attention_pair(int32_t dtype, int32_t dkp, int32_t dvp, int32_t dk
                              int64_t sKb, int64_t sVb, int64_t sOb, int32_t v_rowmajor, const uint8_t *kv_mask,
                              const uint8_t *q_mask, int32_t core, void *workspace, size_t workspace_bytes, void *stream) {
     if (dtype != PIO_DT_F16 && dtype != PIO_DT_BF16) return PIO_E_ARG;
-    if (core < 0 || core > 3 || (!Q_lo) != (!K_lo)) return PIO_E_ARG;
     const AttnOperands t = {Q, Q_lo, K, K_lo, V, O, O_lo, ldq, ldk, ldv, ldo, sQb, sKb, sVb, sOb};
+    if (core < 0 || core > 3 || !attn_lo_halves_paired(t)) return PIO_E_ARG;
     const bool masked = kv_mask || q_mask;
     // core 0: what attention_core's route takes for the shape (fused_core, pio_attn_route.h), short of the tall-head kernel
     if (core == 1 || (core == 0 && fused_core(dkp, dvp, Tk, masked, true) == AttnCore::FLASH)) {
         if (masked) return PIO_E_ARG;  // (the self-attention kernel takes no mask)
-        if (O_lo && !Q_lo) return PIO_E_ARG;  // (its single-operand instantiations write one half)
+        if (!flash_o_lo_allowed(t)) return PIO_E_ARG;
         return flash_attention_launch(dtype, dkp, dvp, dk, t, B, H, Tq, Tk, v_rowmajor != 0, (hipStream_t)stream);
     }
     if (v_rowmajor) return PIO_E_ARG;  // (the cross-attention kernels read V^T)
     if (core == 3) {                   // the tall-head kernel: no pair operands, key-bit words as its only scratch
-        if (!xtall_supported(dkp, dvp, Tk) || Q_lo) return PIO_E_SHAPE;
+        if (!xtall_takes(dkp, dvp, Tk, t)) return PIO_E_SHAPE;
         if (xtall_scratch_bytes(B) > workspace_bytes) return PIO_E_WORKSPACE;
         return xtall_launch(dtype, dkp, dvp, dk, t, B, H, Tq, Tk, kv_mask, q_mask, workspace, (hipStream_t)stream);
     }

@@ -1,6 +1,6 @@
 // Device-side primitives shared by the kernel translation units: one spelling of each helper the hand-counted waits and
 // the hazard scan (tools/check_asm_hazards.py) depend on.  Device-only (pio_internal.h stays host-includable); an edit
-// here is proved a no-op with tools/isa_diff.py.
+// here is proved a no-op with tools/isa_diff.py.  The steps only the fused attention cores share: pio_attn_device.h.
 #pragma once
 #include <type_traits>
 
@@ -56,14 +56,28 @@ __device__ __forceinline__ void wait_vm_n(int n) {
 #undef PIO_W
 }
 
-// The 32x32x16 MFMA as inline assembly with its accumulator pinned to AGPRs ("+a"), accumulating in place: left to the
-// register allocator the accumulators wander between the two register files and some of them spill.  The compiler's
-// hazard recogniser does not look inside an asm statement: where a VALU instruction reads what this MFMA wrote, or this
-// MFMA reads an accumulator the VALU wrote, the kernel carries explicit s_nop padding (and the build scans for it).
-template <int DT>
-__device__ __forceinline__ void mfma32_agpr(f32x16 &c, typename Op<DT>::V8 a, typename Op<DT>::V8 b) {
-    if constexpr (DT == PIO_DT_F16) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-    else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
+// The 32x32x16 MFMA as inline assembly with its register files pinned: left to the register allocator the accumulators
+// wander between the two register files and some of them spill.  ACC_AGPR: the accumulator lives in AGPRs ("+a") and
+// accumulates in place; else it lives in VGPRs, the B operand in AGPRs (B_AGPR: operands that are only ever MFMA
+// operands) or VGPRs, and ZERO starts the sum (c = a b, SrcC = 0).  The compiler's hazard recogniser does not look inside
+// an asm statement: where a VALU instruction reads what this MFMA wrote, or this MFMA reads an accumulator the VALU
+// wrote, the kernel carries explicit s_nop padding (and the build scans for it).  (pio_gemm_wide.hip's MFMAs are plain
+// asm of another instruction shape and stay there.)
+template <int DT, bool ACC_AGPR, bool B_AGPR = false, bool ZERO = false>
+__device__ __forceinline__ void mfma32_asm(f32x16 &c, typename Op<DT>::V8 a, typename Op<DT>::V8 b) {
+    static_assert(!ACC_AGPR || (!B_AGPR && !ZERO), "an AGPR accumulator accumulates in place over VGPR operands");
+    // (a macro: the constraint letters are part of the asm statement's string literals)
+#define PIO_M(SRCC, CC, BC)                                                                                   \
+    do {                                                                                                      \
+        if constexpr (DT == PIO_DT_F16) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, " SRCC : CC(c) : "v"(a), BC(b)); \
+        else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, " SRCC : CC(c) : "v"(a), BC(b));            \
+    } while (0)
+    if constexpr (ACC_AGPR) PIO_M("%0", "+a", "v");
+    else if constexpr (ZERO && B_AGPR) PIO_M("0", "=&v", "a");
+    else if constexpr (ZERO) PIO_M("0", "=&v", "v");
+    else if constexpr (B_AGPR) PIO_M("%0", "+v", "a");
+    else PIO_M("%0", "+v", "v");
+#undef PIO_M
 }
 
 // Reads one accumulator element where it lives (an AGPR): without this the register allocator moves all 256 to VGPRs
@@ -74,11 +88,24 @@ __device__ __forceinline__ float acc_read(float a) {
     asm("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a));
     return v;
 }
-// acc_read_ordered: asm volatile, stays in program order among the volatile MFMAs (mfma32_agpr) and their s_nop padding.
+// acc_read_ordered: asm volatile, stays in program order among the volatile MFMAs (mfma32_asm) and their s_nop padding.
 __device__ __forceinline__ float acc_read_ordered(float a) {
     float v;
     asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a));
     return v;
+}
+// acc_write_ordered: the way back, `acc[i] = acc_write_ordered(v)` -- the value is written where the element lives.
+__device__ __forceinline__ float acc_write_ordered(float v) {
+    float a;
+    asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(a) : "v"(v));
+    return a;
+}
+
+// 1-D grid, remapped so that consecutive ids land on ONE XCD (ids are dealt round-robin over the 8 XCDs): neighbours that
+// stream the same operand hit that XCD's L2.  Bijective; grids that are no multiple of 8 keep their order.
+__device__ __forceinline__ int xcd_contiguous(int bid, int n) {
+    if ((n & 7) == 0) bid = (bid & 7) * (n >> 3) + (bid >> 3);
+    return bid;
 }
 
 }  // namespace pio

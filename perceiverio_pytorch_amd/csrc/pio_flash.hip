@@ -22,12 +22,15 @@
 //     The same for the 128-wide stack heads (DK = DV = 128, fp16, no key split): there the K fragments are streamed per
 //     k-step for the two small products and K_hi is read from LDS a second time for the large one.  Everything else --
 //     64-wide heads, bf16, a key-split pair variant -- has no pair instantiation: PIO_E_SHAPE from the launcher.
+// Shared with the other fused cores: the block-id remap (pio_device.h), the half-wave maximum, the Q-fragment loader
+// and the 4-wide pair cast (pio_attn_device.h); the launch plan (pio_attn_route.h).  The row-sum combine and the staged
+// whole-row epilogue keep their own spelling: through a helper they reorder instructions of this kernel.
 #include <stdio.h>
 #include <stdlib.h>
 
 #include <type_traits>
 
-#include "pio_device.h"
+#include "pio_attn_device.h"
 
 namespace pio {
 
@@ -107,9 +110,7 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 || (QK_PAIR && DK == 128)) ? 1 : 
     const int r32 = lane & 31, hh = lane >> 5;
     // 1-D grid, remapped so that the q-tiles of one (batch, head) -- which stream the same K / V^T -- are
     // consecutive on ONE XCD (ids are dealt round-robin over the 8 XCDs): their K/V re-reads hit that L2.
-    int bid = blockIdx.x;
-    const int nblk = gridDim.x;
-    if ((nblk & 7) == 0) bid = (bid & 7) * (nblk >> 3) + (bid >> 3);
+    const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int qt = bid % p.nqt, bh = bid / p.nqt;
     const int b = bh / p.H, h = bh % p.H;
     const int qb = KS == 1 ? wave : wave % NWQ, kh = KS == 1 ? 0 : wave / NWQ;   // query block, key half of this wave
@@ -193,18 +194,8 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 || (QK_PAIR && DK == 128)) ? 1 : 
     const int v_swz = (r32 >> 1) & 7;             // 32*dvt is even and a multiple of 16 rows -> drops out as well
 
     stage(0, 0);
-    {  // lane holds Q[q0 + r32][16*s + 8*hh + 0..7]
-        int q = q0 + r32;
-        q = q < p.Tq ? q : p.Tq - 1;
-        const T *qrow = Qg + (int64_t)q * p.ldq + 8 * hh;
-#pragma unroll
-        for (int s = 0; s < NQS; ++s) qf[s] = *(const V8 *)(qrow + 16 * s);
-        if constexpr (QK_PAIR) {
-            const T *lrow = (const T *)p.Q_lo + b * p.sQb + (int64_t)h * DK + (int64_t)q * p.ldq + 8 * hh;
-#pragma unroll
-            for (int s = 0; s < NQS; ++s) ql[s] = *(const V8 *)(lrow + 16 * s);
-        }
-    }
+    load_q_frags<DT>(qf, Qg, q0 + r32, p.Tq, p.ldq, hh);  // lane holds Q[q0 + r32][16*s + 8*hh + 0..7]
+    if constexpr (QK_PAIR) load_q_frags<DT>(ql, (const T *)p.Q_lo + b * p.sQb + (int64_t)h * DK, q0 + r32, p.Tq, p.ldq, hh);
     for (int kt = 0; kt < ntiles; ++kt) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -279,7 +270,7 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 || (QK_PAIR && DK == 128)) ? 1 : 
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[t][i]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * p.scale_log2;
+        mx = max_halves(mx) * p.scale_log2;
         const float m_new = fmaxf(m_run, mx);
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);  // first tile: exp2(-inf) = 0
         m_run = m_new;
@@ -423,19 +414,11 @@ __global__ __launch_bounds__(NW * 64, (NW >= 8 || (QK_PAIR && DK == 128)) ? 1 : 
         for (int d = 0; d < NDT; ++d)
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
-                V4 o;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = Op<DT>::from_f32(oacc[d][4 * g4 + j] * inv);
+                V4 o, l;
+                scaled_pair4<DT>(oacc[d], 4 * g4, inv, o, l);
                 *(V4 *)(orow + 32 * d + 8 * g4 + 4 * hh) = o;
-                if constexpr (QK_PAIR) {
-                    if (p.O_lo) {  // the output as a pair: lo = o - float(hi)
-                        V4 l;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            l[j] = Op<DT>::from_f32(oacc[d][4 * g4 + j] * inv - Op<DT>::to_f32(o[j]));
-                        *(V4 *)((T *)p.O_lo + (orow - (T *)p.O) + 32 * d + 8 * g4 + 4 * hh) = l;
-                    }
-                }
+                if constexpr (QK_PAIR)  // the output as a pair: lo = o - float(hi)
+                    if (p.O_lo) *(V4 *)((T *)p.O_lo + (orow - (T *)p.O) + 32 * d + 8 * g4 + 4 * hh) = l;
             }
     }
 }
@@ -488,26 +471,18 @@ static void flash_launch_dt(int dtype, bool pair, const FlashRoute &r, dim3 grid
 
 int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const AttnOperands &t, int B, int H, int Tq, int Tk,
                            bool v_rowmajor, hipStream_t s) {
-    if (!flash_supported(dkp, dvp)) return PIO_E_SHAPE;
-    if (attn_operands_present(t) != PIO_OK) return PIO_E_ARG;
-    const bool pair = t.Q_lo != nullptr;  // Q and K as (hi, lo) pairs; O_lo only with them
-    if (t.O_lo && !pair) return PIO_E_ARG;
-    if (pair && !flash_pair_supported(dtype, dkp, dvp)) return PIO_E_SHAPE;  // (never a silent single-operand run)
-    if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || (int64_t)B * H * ((Tq + 127) / 128) > 0x7fffffffLL) return PIO_E_SHAPE;
-    if (attn_operands_aligned(t) != PIO_OK) return PIO_E_ALIGN;
     static const bool ksplit_on = [] {
         const char *e = getenv("PIO_FLASH_KSPLIT");
         return !e || atoi(e) != 0;
     }();
-    const FlashRoute r = pair ? flash_pair_route(dkp, dvp, B, H, Tq, Tk, v_rowmajor, ksplit_on, cu_budget())
-                              : flash_route(dkp, dvp, B, H, Tq, Tk, v_rowmajor, ksplit_on, cu_budget());
-    // (an output PAIR leaves through the per-lane 8-byte stores: the staged whole-row epilogue carries one half only)
-    const int o_rows16 = (!t.O_lo && t.ldo % 8 == 0 && t.sOb % 8 == 0 && ((uintptr_t)t.O & 15) == 0) ? 1 : 0;
+    const FlashPlan plan = flash_launch_plan(dtype, dkp, dvp, t, B, H, Tq, Tk, v_rowmajor, ksplit_on, cu_budget());
+    if (plan.err) return plan.err;
+    const FlashRoute &r = plan.route;
     FlashParams p{t.Q, t.K, t.VT, t.O, Tq, Tk, H, r.nqt, t.ldq, t.ldk, t.ldvt, t.ldo, t.sQb, t.sKb, t.sVb, t.sOb,
-                  1.4426950408889634f / sqrtf((float)dk_logical), o_rows16, t.Q_lo, t.K_lo, t.O_lo};
-    dim3 grid((unsigned)(r.nqt * B * H), 1, 1);
-    ProfScope prof(PROF_FLASH, 2.0 * B * H * (double)Tq * Tk * (dkp + dvp),
-                   2.0 * B * H * ((double)Tq * (dkp + dvp) + (double)Tk * (dkp + dvp)), s);
+                  attn_scale_log2(dk_logical), plan.o_rows16, t.Q_lo, t.K_lo, t.O_lo};
+    dim3 grid((unsigned)plan.grid, 1, 1);
+    const AttnWork work = attn_work(dkp, dvp, B, H, Tq, Tk);
+    ProfScope prof(PROF_FLASH, work.flops, work.bytes, s);
     int variant = 0;
 #ifdef PIO_EXPERIMENTS
     variant = flash_variant_override(-2);   // (experiments build: pio_debug_flash_variant / env PIO_FLASH_VARIANT)
@@ -520,7 +495,7 @@ int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const At
         fprintf(stderr, "[pio] fused attention B=%d H=%d Tq=%d Tk=%d dkp=%d dvp=%d v_rowmajor=%d NW=%d KS=%d variant=%d\n", B,
                 H, Tq, Tk, dkp, dvp, (int)v_rowmajor, r.NW, r.KS, variant);
 #ifdef PIO_EXPERIMENTS
-    if (!pair && v_rowmajor && Tq >= 256 && Tk % 128 == 0 && variant == 1 && o_rows16) {
+    if (!plan.pair && v_rowmajor && Tq >= 256 && Tk % 128 == 0 && variant == 1 && plan.o_rows16) {
         FlashParams pp = p;
         pp.nqt = (Tq + 255) / 256;
         dim3 pgrid((unsigned)(pp.nqt * B * H), 1, 1);
@@ -528,16 +503,16 @@ int flash_attention_launch(int dtype, int dkp, int dvp, int dk_logical, const At
         else hipLaunchKernelGGL((flash_attn_pipe_kernel<PIO_DT_BF16>), pgrid, dim3(256), 0, s, pp);
         return launch_status();
     }
-    if (!pair && r.NW == 8 && r.KS == 1 && variant == 2) {
+    if (!plan.pair && r.NW == 8 && r.KS == 1 && variant == 2) {
         if (dtype == PIO_DT_F16) hipLaunchKernelGGL((flash_attn_stag_kernel<PIO_DT_F16>), grid, dim3(512), 0, s, p);
         else hipLaunchKernelGGL((flash_attn_stag_kernel<PIO_DT_BF16>), grid, dim3(512), 0, s, p);
         return launch_status();
     }
 #endif
-    if (dkp == 128) flash_launch_dt<128, 128>(dtype, pair, r, grid, s, p);
-    else if (dkp == 64) flash_launch_dt<64, 64>(dtype, pair, r, grid, s, p);
-    else if (dvp == 32) flash_launch_dt<32, 32>(dtype, pair, r, grid, s, p);
-    else flash_launch_dt<32, 160>(dtype, pair, r, grid, s, p);
+    if (dkp == 128) flash_launch_dt<128, 128>(dtype, plan.pair, r, grid, s, p);
+    else if (dkp == 64) flash_launch_dt<64, 64>(dtype, plan.pair, r, grid, s, p);
+    else if (dvp == 32) flash_launch_dt<32, 32>(dtype, plan.pair, r, grid, s, p);
+    else flash_launch_dt<32, 160>(dtype, plan.pair, r, grid, s, p);
     return launch_status();
 }
 

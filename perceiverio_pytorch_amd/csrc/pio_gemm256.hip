@@ -56,9 +56,7 @@ __global__ __launch_bounds__(512) void gemm_nt_256(const GemmParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
 
-    int bid = blockIdx.x;
-    const int nt = gridDim.x;
-    if ((nt & 7) == 0) bid = (bid & 7) * (nt >> 3) + (bid >> 3);  // XCD-contiguous tile runs (bijective)
+    const int bid = xcd_contiguous(blockIdx.x, gridDim.x);  // XCD-contiguous tile runs
     const int tile_n = bid % p.tiles_n;
     const int tile_m = bid / p.tiles_n;
     const int z = blockIdx.y;

@@ -32,9 +32,13 @@
 //     0..3 of its 16-chunk (256-byte) LDS row, K_lo goes to logical chunks 4..7 -- same pieces, same swizzle, same
 //     conflict-free ds_read_b128 (k-steps 2 and 3 of the row), no extra LDS, no extra barrier.  Everything behind S^T
 //     (scale, masks, softmax, P rounded once, P V, key splits, the O / O_lo pair, the wipe) is the code above, unchanged.
+// Shared with the other fused cores: the block-id remap, the MFMA wrappers and the AGPR read / write (pio_device.h), the
+// half-wave maximum and the key-bit test (pio_attn_device.h); the launch plan (pio_attn_route.h).  The Q-fragment load,
+// the key word's scalar load, the row-sum combine and the pair epilogues keep their own spelling: through a helper they
+// change this kernel's instruction stream.
 #include <stdlib.h>
 
-#include "pio_device.h"
+#include "pio_attn_device.h"
 
 namespace pio {
 
@@ -58,28 +62,7 @@ struct XattnParams {
 // Left to the register allocator the wide-head instantiations spilled Q fragments to scratch, and every reload sat in
 // the vector-memory queue behind the LDS-DMA pieces.  The compiler's hazard recogniser does not look inside an asm
 // statement: the places where a VALU instruction reads what an MFMA wrote (softmax after S^T, the epilogue) or an MFMA
-// reads an accumulator the VALU wrote (after a rescale) carry explicit s_nop padding below.
-template <int DT, bool B_IN_AGPR>
-__device__ __forceinline__ void xa_mfma_v(f32x16 &c, typename Op<DT>::V8 a, typename Op<DT>::V8 b) {  // acc in VGPRs
-    if constexpr (DT == PIO_DT_F16) {
-        if constexpr (B_IN_AGPR) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "a"(b));
-        else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-    } else {
-        if constexpr (B_IN_AGPR) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "a"(b));
-        else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-    }
-}
-template <int DT, bool B_IN_AGPR>
-__device__ __forceinline__ void xa_mfma_v0(f32x16 &c, typename Op<DT>::V8 a, typename Op<DT>::V8 b) {  // c = a b
-    if constexpr (DT == PIO_DT_F16) {
-        if constexpr (B_IN_AGPR) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "a"(b));
-        else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "v"(b));
-    } else {
-        if constexpr (B_IN_AGPR) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "a"(b));
-        else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "v"(b));
-    }
-}
-
+// reads an accumulator the VALU wrote (after a rescale) carry explicit s_nop padding below.  (mfma32_asm: pio_device.h)
 template <int DT, int DKL, int DVS, bool QK_PAIR = false>
 __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn_kernel(const XattnParams p) {
     static_assert(!QK_PAIR || (DKL == 32 && DT == PIO_DT_F16), "pair-operand Q K^T: the dk <= 32 fp16 instantiations");
@@ -112,9 +95,7 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
     const int r32 = lane & 31, hh = lane >> 5;
     // 1-D grid; consecutive ids of ONE XCD (ids are dealt round-robin over the 8 XCDs) walk the query tiles and dv
     // slices of one (batch, head, key split), which stream the same K / V^T: their re-reads hit that L2.
-    int bid = blockIdx.x;
-    const int nblk = gridDim.x;
-    if ((nblk & 7) == 0) bid = (bid & 7) * (nblk >> 3) + (bid >> 3);
+    const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int qt = bid % p.nqt;
     int rest = bid / p.nqt;
     const int ds = rest % p.nslice;
@@ -323,8 +304,7 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
         static_for<0, NQS>([&](auto SI) {
             constexpr int sx = decltype(SI)::value;
             if constexpr (!PIN) sacc = Op<DT>::mfma32(kf[sx % RK], qf[sx], sacc);
-            else if constexpr (sx == 0) xa_mfma_v0<DT, (0 < NQ_A)>(sacc, kf[0], qf[0]);
-            else xa_mfma_v<DT, (sx < NQ_A)>(sacc, kf[sx % RK], qf[sx]);
+            else mfma32_asm<DT, false, (sx < NQ_A), sx == 0>(sacc, kf[sx % RK], qf[sx]);
             if constexpr (sx + RK < NQS) kf[sx % RK] = k_read(sx + RK);
             if constexpr (sx < KPW + VPW) stage_piece(std::integral_constant<int, sx>{});
             __builtin_amdgcn_sched_barrier(0);
@@ -353,7 +333,7 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
             const uint32_t bits = word >> (8 * hh);
 #pragma unroll
             for (int i = 0; i < 16; ++i)
-                if (!((bits >> (16 * (i >> 3) + (i & 7))) & 1u)) sacc[i] = -INFINITY;
+                if (!key_bit(bits, i)) sacc[i] = -INFINITY;
         }
         // ---- online softmax in base 2: p = exp2(s * c - m_ref * c).  The reference point m_ref follows the running
         // maximum LAZILY: it moves (and the accumulators are rescaled -- ~400 instructions with the accumulator in
@@ -363,7 +343,7 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
         float mx = -INFINITY;
 #pragma unroll
         for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[i]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * p.scale_log2;
+        mx = max_halves(mx) * p.scale_log2;
         const bool unset = m_run == -INFINITY;
         const float m_new = (unset || mx > m_run + 10.0f) ? fmaxf(m_run, mx) : m_run;
         const float m_use = m_new == -INFINITY ? 0.f : m_new;
@@ -387,10 +367,7 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
                     if constexpr (PIN) {
                         // explicit AGPR -> VGPR -> AGPR round trip INSIDE the branch: written as plain arithmetic
                         // the compiler hoists the copies of the whole accumulator out of it, into every tile
-                        float v;
-                        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(oacc[d][j]));
-                        v *= alpha;
-                        asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(oacc[d][j]) : "v"(v));
+                        oacc[d][j] = acc_write_ordered(acc_read_ordered(oacc[d][j]) * alpha);
                     } else {
                         oacc[d][j] *= alpha;
                     }
@@ -413,7 +390,7 @@ __global__ __launch_bounds__(256, (DKL <= 128 && DVS <= 160) ? 2 : 1) void xattn
         static_for<0, NVF>([&](auto FI) {
             constexpr int f = decltype(FI)::value;
             constexpr int d = f >> 1, s2 = f & 1;
-            if constexpr (PIN) mfma32_agpr<DT>(oacc[d], vf[f % RV], pf[s2]);
+            if constexpr (PIN) mfma32_asm<DT, true>(oacc[d], vf[f % RV], pf[s2]);
             else oacc[d] = Op<DT>::mfma32(vf[f % RV], pf[s2], oacc[d]);
             if constexpr (f + RV < NVF) vf[f % RV] = v_read(f + RV);
             __builtin_amdgcn_sched_barrier(0);
@@ -541,7 +518,7 @@ __global__ __launch_bounds__(256) void xattn_reduce_kernel(const float *part_o, 
     if (O_lo) *(V4 *)((T *)O_lo + off) = l;
 }
 
-// ---- host side (shape tables, key splits and scratch sizes: pio_attn_route.h) ---------------------------------------
+// ---- host side (shape tables, key splits, scratch sizes and the launch plan: pio_attn_route.h) ------------------------
 // the instantiation of one XCfg: operand dtype and, on the DKL = 32 fp16 heads, the pair-operand (QK_PAIR) form
 template <int DKL, int DVS>
 static void xattn_launch_dt(int dtype, bool pair, dim3 grid, hipStream_t s, const XattnParams &p) {
@@ -553,53 +530,37 @@ static void xattn_launch_dt(int dtype, bool pair, dim3 grid, hipStream_t s, cons
 
 int xattn_launch(int dtype, int dkp, int dvp, int dk_logical, const AttnOperands &t, int B, int H, int Tq, int Tk,
                  const uint8_t *kv_mask, const uint8_t *q_mask, void *partials, hipStream_t s) {
-    const XCfg *c = xattn_cfg(dkp, dvp);
-    if (!c) return PIO_E_SHAPE;
-    if (attn_operands_present(t) != PIO_OK) return PIO_E_ARG;
-    const bool pair = t.Q_lo != nullptr;  // Q and K as (hi, lo) pairs
-    if (pair && !xattn_pair_supported(dtype, dkp, dvp)) return PIO_E_SHAPE;  // (never a silent single-operand run)
-    if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0 || (dkp & 7) || (dvp & 7)) return PIO_E_SHAPE;
-    if (attn_operands_aligned(t) != PIO_OK) return PIO_E_ALIGN;
-    const int64_t ldk = t.ldk, ldvt = t.ldvt, ldo = t.ldo, sOb = t.sOb;
-    void *const O = t.O, *const O_lo = t.O_lo;
-    if (ldvt < 8 || 32 * ldk >= (1ll << 31) || (int64_t)dvp * ldvt >= (1ll << 31)) return PIO_E_SHAPE;
-    const int nslice = (dvp + c->dvs - 1) / c->dvs;
-    const int nqt = (Tq + 127) / 128;
-    const int nsplit = xattn_splits(dkp, dvp, B, H, Tq, Tk);
-    const int ntiles = (Tk + 31) / 32;
-    const int tps = (ntiles + nsplit - 1) / nsplit;
-    if ((nsplit > 1 || kv_mask) && !partials) return PIO_E_WORKSPACE;
-    if (ldvt % 32) return PIO_E_ALIGN;  // V^T rows are read in whole 32-key tiles (zero padded by the caller)
-    const int64_t nwg = (int64_t)B * H * nqt * nslice * nsplit;
-    if (nwg > 0x7fffffffLL) return PIO_E_SHAPE;
+    const XattnPlan plan = xattn_launch_plan(dtype, dkp, dvp, t, B, H, Tq, Tk, kv_mask != nullptr, partials != nullptr);
+    if (plan.err) return plan.err;
+    const XCfg &c = plan.cfg;
     XattnParams p{};
-    p.Q = t.Q; p.K = t.K; p.VT = t.VT; p.O = O; p.O_lo = O_lo;
+    p.Q = t.Q; p.K = t.K; p.VT = t.VT; p.O = t.O; p.O_lo = t.O_lo;
     p.Q_lo = t.Q_lo; p.K_lo = t.K_lo;
     p.key_bits = kv_mask ? (const uint32_t *)partials : nullptr;
-    p.part_o = (float *)((char *)partials + keybits_bytes(B, Tk));
-    p.part_ml = nsplit > 1 ? p.part_o + (size_t)B * H * nsplit * Tq * dvp : nullptr;
+    p.part_o = (float *)((char *)partials + plan.part_o_off);
+    p.part_ml = plan.nsplit > 1 ? (float *)((char *)partials + plan.part_ml_off) : nullptr;
     p.q_mask = q_mask;
-    p.Tq = Tq; p.Tk = Tk; p.H = H; p.nqt = nqt; p.nslice = nslice; p.nsplit = nsplit; p.tiles_per_split = tps;
+    p.Tq = Tq; p.Tk = Tk; p.H = H; p.nqt = plan.nqt; p.nslice = plan.nslice; p.nsplit = plan.nsplit;
+    p.tiles_per_split = plan.tiles_per_split;
     p.dkp = dkp; p.dvp = dvp;
-    p.ldq = t.ldq; p.ldk = ldk; p.ldvt = ldvt; p.ldo = ldo; p.sQb = t.sQb; p.sKb = t.sKb; p.sVb = t.sVb; p.sOb = sOb;
-    p.scale_log2 = 1.4426950408889634f / sqrtf((float)dk_logical);
-    dim3 grid((unsigned)nwg, 1, 1), block(256, 1, 1);
-    if (kv_mask) xattn_keybits_launch(kv_mask, (uint32_t *)partials, B, Tk, ntiles, s);
+    p.ldq = t.ldq; p.ldk = t.ldk; p.ldvt = t.ldvt; p.ldo = t.ldo; p.sQb = t.sQb; p.sKb = t.sKb; p.sVb = t.sVb; p.sOb = t.sOb;
+    p.scale_log2 = attn_scale_log2(dk_logical);
+    dim3 grid((unsigned)plan.grid, 1, 1), block(256, 1, 1);
+    if (kv_mask) xattn_keybits_launch(kv_mask, (uint32_t *)partials, B, Tk, plan.ntiles, s);
     {
-        // S recomputed per dv slice counts once: algorithmic flops of the reference formulation
-        ProfScope prof(PROF_FLASH, 2.0 * B * H * (double)Tq * Tk * (dkp + dvp),
-                       2.0 * B * H * ((double)Tq * (dkp + dvp) + (double)Tk * (dkp + dvp)), s);
-        if (c->dkl == 32 && c->dvs == 96) xattn_launch_dt<32, 96>(dtype, pair, grid, s, p);
-        else if (c->dkl == 32) xattn_launch_dt<32, 160>(dtype, pair, grid, s, p);
-        else if (c->dkl == 128) xattn_launch_dt<128, 128>(dtype, pair, grid, s, p);
-        else if (c->dkl == 352) xattn_launch_dt<352, 352>(dtype, pair, grid, s, p);
-        else if (c->dkl == 512) xattn_launch_dt<512, 512>(dtype, pair, grid, s, p);
-        else xattn_launch_dt<704, 256>(dtype, pair, grid, s, p);
-        if (nsplit > 1) {
+        const AttnWork work = attn_work(dkp, dvp, B, H, Tq, Tk);
+        ProfScope prof(PROF_FLASH, work.flops, work.bytes, s);
+        if (c.dkl == 32 && c.dvs == 96) xattn_launch_dt<32, 96>(dtype, plan.pair, grid, s, p);
+        else if (c.dkl == 32) xattn_launch_dt<32, 160>(dtype, plan.pair, grid, s, p);
+        else if (c.dkl == 128) xattn_launch_dt<128, 128>(dtype, plan.pair, grid, s, p);
+        else if (c.dkl == 352) xattn_launch_dt<352, 352>(dtype, plan.pair, grid, s, p);
+        else if (c.dkl == 512) xattn_launch_dt<512, 512>(dtype, plan.pair, grid, s, p);
+        else xattn_launch_dt<704, 256>(dtype, plan.pair, grid, s, p);
+        if (plan.nsplit > 1) {
             const int64_t total = (int64_t)B * H * Tq * (dvp / 4);
             auto reduce = dtype == PIO_DT_F16 ? xattn_reduce_kernel<PIO_DT_F16> : xattn_reduce_kernel<PIO_DT_BF16>;
-            hipLaunchKernelGGL(reduce, dim3((unsigned)((total + 255) / 256)), block, 0, s, p.part_o, p.part_ml, O, O_lo, q_mask,
-                               H, nsplit, Tq, dvp, ldo, sOb, total);
+            hipLaunchKernelGGL(reduce, dim3((unsigned)((total + 255) / 256)), block, 0, s, p.part_o, p.part_ml, t.O, t.O_lo, q_mask,
+                               H, plan.nsplit, Tq, dvp, t.ldo, t.sOb, total);
         }
     }
     return launch_status();

@@ -27,9 +27,12 @@
 // Keys beyond Tk (Tk < 512) read clamped (finite) K rows / V^T columns and are masked to -inf / p = 0; a key mask
 // arrives as one 32-bit word per 32 keys (xattn_keybits_kernel), a query mask wipes the row -- the same semantics as
 // pio_xattn.hip.
+// Shared with the other fused cores: the block-id remap, the MFMA wrapper and the AGPR read / write (pio_device.h), the
+// half-wave combines and the key-bit test (pio_attn_device.h); the launch plan (pio_attn_route.h).  The pair epilogue
+// keeps its own spelling: through scaled_pair4 it changes the instruction stream.
 #include <stdlib.h>
 
-#include "pio_device.h"
+#include "pio_attn_device.h"
 
 namespace pio {
 
@@ -52,9 +55,6 @@ constexpr int T_NP = 10;                  // LDS-DMA pieces per wave and chunk -
 constexpr int T_SINK = T_NST * T_STAGE;   // 1 KiB per wave
 constexpr int T_SMEM = T_SINK + 4096;
 
-// (a macro: an asm operand may name a vector element, a reference may not)
-#define XT_ACC_WRITE(dst, val) asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(dst) : "v"(val))
-
 template <int DT>
 __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p) {
     typedef typename Op<DT>::T T;
@@ -67,9 +67,7 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r32 = lane & 31, hh = lane >> 5;
     // consecutive ids of ONE XCD walk the query tiles of one (sample, head): they stream the same K / V^T through that L2
-    int bid = blockIdx.x;
-    const int nblk = gridDim.x;
-    if ((nblk & 7) == 0) bid = (bid & 7) * (nblk >> 3) + (bid >> 3);
+    const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int qt = bid % p.nqt;
     const int bh = bid / p.nqt;
     const int b = bh / p.H, h = bh % p.H;
@@ -196,7 +194,7 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
 #pragma unroll
         for (int kb = 0; kb < T_NKB; ++kb)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) XT_ACC_WRITE(sacc[kb][i], zero);
+            for (int i = 0; i < 16; ++i) sacc[kb][i] = acc_write_ordered(zero);
     }
 
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(T_NP) : "memory");
@@ -231,7 +229,7 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
         issue_begin(c + 2, nslot2);
         static_for<0, 32>([&](auto FI) {
             constexpr int f = decltype(FI)::value;
-            mfma32_agpr<DT>(sacc[f & 15], kf[f & 7], qf[f >> 4]);
+            mfma32_asm<DT, true>(sacc[f & 15], kf[f & 7], qf[f >> 4]);
             if constexpr ((f & 1) == 0 && f < 2 * T_NP) issue_piece(std::integral_constant<int, f / 2>{});
             if constexpr (f + 8 < 32) kf[f & 7] = k_read(st, f + 8);
             if constexpr (f == 27) {
@@ -288,8 +286,8 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
             for (int i = 0; i < 16; i += 2) {
                 float v0 = acc_read_ordered(sacc[kb][i]), v1 = acc_read_ordered(sacc[kb][i + 1]);
                 if constexpr (MASKED) {
-                    v0 = ((bits >> (16 * (i >> 3) + (i & 7))) & 1u) ? v0 : -INFINITY;
-                    v1 = ((bits >> (16 * ((i + 1) >> 3) + ((i + 1) & 7))) & 1u) ? v1 : -INFINITY;
+                    v0 = key_bit(bits, i) ? v0 : -INFINITY;
+                    v1 = key_bit(bits, i + 1) ? v1 : -INFINITY;
                 }
                 m0 = fmaxf(m0, v0);
                 m1 = fmaxf(m1, v1);
@@ -297,7 +295,7 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
             mx = fmaxf(mx, fmaxf(m0, m1));
             __builtin_amdgcn_sched_barrier(0);
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * p.scale_log2;
+        mx = max_halves(mx) * p.scale_log2;
         m_use = mx == -INFINITY ? 0.f : mx;   // no attendable key at all: every p = exp2(-inf) = 0, l = 0
 #pragma unroll
         for (int kb = 0; kb < T_NKB; ++kb) {
@@ -308,7 +306,7 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     float v = acc_read_ordered(sacc[kb][8 * s2 + j]);
-                    if constexpr (MASKED) v = ((bits >> (16 * s2 + j)) & 1u) ? v : -INFINITY;
+                    if constexpr (MASKED) v = key_bit(bits, 8 * s2 + j) ? v : -INFINITY;
                     const float e = __builtin_amdgcn_exp2f(fmaf(v, p.scale_log2, -m_use));
                     psum += e;
                     pf[2 * kb + s2][j] = Op<DT>::from_f32(e);
@@ -318,7 +316,7 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
     };
     if (masked) softmax(std::true_type{});
     else softmax(std::false_type{});
-    const float l_tot = psum + __shfl_xor(psum, 32, 64);
+    const float l_tot = sum_halves(psum);
     const bool live = l_tot > 0.f && q_live;  // no attendable key / masked query: the reference wipes the row to zeros
     const float inv = live ? 1.0f / l_tot : 0.f;
 
@@ -338,7 +336,7 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
 #pragma unroll
             for (int d = 0; d < 8; ++d)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) XT_ACC_WRITE(oacc[d][i], zero);
+                for (int i = 0; i < 16; ++i) oacc[d][i] = acc_write_ordered(zero);
         }
         {
             const char *st0 = smem + slot * T_STAGE;
@@ -357,7 +355,7 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
             issue_begin(n_a + pass * 8 + cb + 2, nslot2);
             static_for<0, 32>([&](auto FI) {
                 constexpr int f = decltype(FI)::value;
-                mfma32_agpr<DT>(oacc[f & 7], vf[f & 7], pf[4 * cb + (f >> 3)]);
+                mfma32_asm<DT, true>(oacc[f & 7], vf[f & 7], pf[4 * cb + (f >> 3)]);
                 if constexpr ((f & 1) == 0 && f < 2 * T_NP) issue_piece(std::integral_constant<int, f / 2>{});
                 if constexpr (f + 8 < 32) vf[f & 7] = v_read(st, f + 8);
                 if constexpr (f == 27) {
@@ -417,35 +415,27 @@ __global__ __launch_bounds__(256, 1) void xattn_tall_kernel(const XtallParams p)
     }
 }
 
-// ---- host side -----------------------------------------------------------------------------------------------------
+// ---- host side (the launch plan: pio_attn_route.h) ------------------------------------------------------------------
 void xattn_keybits_launch(const uint8_t *kv_mask, uint32_t *bits, int B, int Tk, int ntiles, hipStream_t s);
 
 int xtall_launch(int dtype, int dkp, int dvp, int dk_logical, const AttnOperands &t, int B, int H, int Tq, int Tk,
                  const uint8_t *kv_mask, const uint8_t *q_mask, void *scratch, hipStream_t s) {
-    if (!xtall_supported(dkp, dvp, Tk) || t.Q_lo) return PIO_E_SHAPE;  // (no pair-operand instantiation)
-    if (attn_operands_present(t) != PIO_OK) return PIO_E_ARG;
-    if (B <= 0 || H <= 0 || Tq <= 0) return PIO_E_SHAPE;
-    if (attn_operands_aligned(t) != PIO_OK) return PIO_E_ALIGN;
-    const int64_t ldq = t.ldq, ldk = t.ldk, ldvt = t.ldvt;
-    if (ldvt < 64 || (int64_t)Tk * ldk >= (1ll << 31) || (int64_t)Tq * ldq >= (1ll << 31) || 256 * ldvt >= (1ll << 31))
-        return PIO_E_SHAPE;
-    if (kv_mask && !scratch) return PIO_E_WORKSPACE;
+    const XtallPlan plan = xtall_launch_plan(dkp, dvp, t, B, H, Tq, Tk, kv_mask != nullptr, scratch != nullptr);
+    if (plan.err) return plan.err;
     XtallParams p{};
     p.Q = t.Q; p.K = t.K; p.VT = t.VT; p.O = t.O; p.O_lo = t.O_lo;
     p.q_mask = q_mask;
     p.key_bits = kv_mask ? (const uint32_t *)scratch : nullptr;
-    p.Tq = Tq; p.Tk = Tk; p.H = H; p.nqt = (Tq + 127) / 128; p.dkp = dkp; p.dvp = dvp;
-    p.nka = dkp / 32;
-    p.npass = dvp / 256;
-    p.ldq = ldq; p.ldk = ldk; p.ldvt = ldvt; p.ldo = t.ldo; p.sQb = t.sQb; p.sKb = t.sKb; p.sVb = t.sVb; p.sOb = t.sOb;
-    p.scale_log2 = 1.4426950408889634f / sqrtf((float)dk_logical);
-    const int64_t nwg = (int64_t)B * H * p.nqt;
-    if (nwg > 0x7fffffffLL) return PIO_E_SHAPE;
+    p.Tq = Tq; p.Tk = Tk; p.H = H; p.nqt = plan.nqt; p.dkp = dkp; p.dvp = dvp;
+    p.nka = plan.nka;
+    p.npass = plan.npass;
+    p.ldq = t.ldq; p.ldk = t.ldk; p.ldvt = t.ldvt; p.ldo = t.ldo; p.sQb = t.sQb; p.sKb = t.sKb; p.sVb = t.sVb; p.sOb = t.sOb;
+    p.scale_log2 = attn_scale_log2(dk_logical);
     if (kv_mask) xattn_keybits_launch(kv_mask, (uint32_t *)scratch, B, Tk, T_NKB, s);
-    dim3 grid((unsigned)nwg, 1, 1), block(256, 1, 1);
+    dim3 grid((unsigned)plan.grid, 1, 1), block(256, 1, 1);
     {
-        ProfScope prof(PROF_FLASH, 2.0 * B * H * (double)Tq * Tk * (dkp + dvp),
-                       2.0 * B * H * ((double)Tq * (dkp + dvp) + (double)Tk * (dkp + dvp)), s);
+        const AttnWork work = attn_work(dkp, dvp, B, H, Tq, Tk);
+        ProfScope prof(PROF_FLASH, work.flops, work.bytes, s);
         if (dtype == PIO_DT_F16) hipLaunchKernelGGL((xattn_tall_kernel<PIO_DT_F16>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((xattn_tall_kernel<PIO_DT_BF16>), grid, block, 0, s, p);
     }

@@ -1,9 +1,11 @@
 """CPU: which core every attention call runs on, what its plan carves and which variant of the self-attention kernel a
 launch gets (perceiverio_pytorch_amd/csrc/pio_attn_route.h, compiled with g++ into a small driver; the descriptors carry
 fake, aligned pointers that are never dereferenced).  The cases are the attention shapes of the four shipped models under
-their default policies and under "fp16x3fq", plus the edge of every rule.  The expected values were produced by the
+their default policies and under "fp16x3fq", plus the edge of every rule; then the launch plans of the three fused cores
+(accepted plans and every refusal, with calls that break two rules at once to pin the order of the checks).  The expected values were produced by the
 predicates and the attention_core ladder the header replaced (a sweep of 5.1e9 calls showed no disagreement); the table
-is a readable extract of it."""
+is a readable extract of it.  The launch-plan rows (FPLAN, XPLAN, TPLAN) were read off the three launchers as they stood
+before the plans existed: the order of their refusals and their grid arithmetic."""
 import os
 import subprocess
 import tempfile
@@ -161,10 +163,153 @@ static void flash_cases() {
     flash("v_transposed", 32, 160, 2, 8, 256, 256, false, true);
     flash("v_transposed_b32", 128, 128, 32, 8, 512, 512, false, true);
 }
+
+// ---- launch plans: what the three launchers decide before they fill their kernel's parameters ----------------------
+static const char *code(int err) {
+    return err == PIO_E_ARG ? "PIO_E_ARG" : err == PIO_E_SHAPE ? "PIO_E_SHAPE" : err == PIO_E_ALIGN ? "PIO_E_ALIGN"
+           : err == PIO_E_WORKSPACE ? "PIO_E_WORKSPACE" : "error";
+}
+// operands of a well-formed call: dense [T][H*d] rows, V^T rows padded to 64 keys, aligned fake pointers
+static AttnOperands ops(int H, int dkp, int dvp, int Tq, int Tk, bool v_rowmajor = false) {
+    AttnOperands t = {};
+    t.Q = t.K = t.VT = W; t.O = (void *)W;
+    t.ldq = t.ldk = (int64_t)H * dkp; t.ldo = (int64_t)H * dvp;
+    t.ldvt = v_rowmajor ? (int64_t)H * dvp : (Tk + 63) / 64 * 64;
+    t.sQb = Tq * t.ldq; t.sKb = Tk * t.ldk; t.sOb = Tq * t.ldo;
+    t.sVb = v_rowmajor ? Tk * t.ldvt : (int64_t)H * dvp * t.ldvt;
+    return t;
+}
+static void *const LO = (void *)(uintptr_t)0x20000000;
+static void as_pair(AttnOperands &t) { t.Q_lo = t.K_lo = LO; }
+static void none(AttnOperands &) {}
+typedef void (*Edit)(AttnOperands &);
+
+// fplan id: V layout, NW, KS, nqt, pair, o_rows16, grid
+static void fplan(const char *id, int dtype, int dkp, int dvp, int B, int H, int Tq, int Tk, bool vrow, Edit edit = none) {
+    AttnOperands t = ops(H, dkp, dvp, Tq, Tk, vrow);
+    edit(t);
+    const FlashPlan p = flash_launch_plan(dtype, dkp, dvp, t, B, H, Tq, Tk, vrow, true, 256);
+    if (p.err) printf("fplan %s %s\n", id, code(p.err));
+    else printf("fplan %s %s %d %d %d %d %d %lld\n", id, p.route.v_rowmajor ? "row" : "V^T", p.route.NW, p.route.KS,
+                p.route.nqt, p.pair, p.o_rows16, (long long)p.grid);
+}
+// xplan id: dkl, dvs, pair, nqt, nslice, nsplit, ntiles, tiles_per_split, grid, part_o_off, part_ml_off
+static void xplan(const char *id, int dtype, int dkp, int dvp, int B, int H, int Tq, int Tk, bool mask, bool scratch,
+                  Edit edit = none) {
+    AttnOperands t = ops(H, dkp, dvp, Tq, Tk);
+    edit(t);
+    const XattnPlan p = xattn_launch_plan(dtype, dkp, dvp, t, B, H, Tq, Tk, mask, scratch);
+    if (p.err) printf("xplan %s %s\n", id, code(p.err));
+    else printf("xplan %s %d %d %d %d %d %d %d %d %lld %zu %zu\n", id, p.cfg.dkl, p.cfg.dvs, p.pair, p.nqt, p.nslice,
+                p.nsplit, p.ntiles, p.tiles_per_split, (long long)p.grid, p.part_o_off, p.part_ml_off);
+}
+// tplan id: nqt, nka, npass, grid
+static void tplan(const char *id, int dkp, int dvp, int B, int H, int Tq, int Tk, bool mask, bool scratch, Edit edit = none) {
+    AttnOperands t = ops(H, dkp, dvp, Tq, Tk);
+    edit(t);
+    const XtallPlan p = xtall_launch_plan(dkp, dvp, t, B, H, Tq, Tk, mask, scratch);
+    if (p.err) printf("tplan %s %s\n", id, code(p.err));
+    else printf("tplan %s %d %d %d %lld\n", id, p.nqt, p.nka, p.npass, (long long)p.grid);
+}
+// one edit per alignment rule of attn_operands_aligned
+static const struct { const char *name; Edit edit; } MISALIGNED[] = {
+    {"ldq", [](AttnOperands &t) { t.ldq += 4; }},   {"ldk", [](AttnOperands &t) { t.ldk += 4; }},
+    {"ldvt", [](AttnOperands &t) { t.ldvt += 4; }}, {"ldo", [](AttnOperands &t) { t.ldo += 2; }},
+    {"sQb", [](AttnOperands &t) { t.sQb += 4; }},   {"sKb", [](AttnOperands &t) { t.sKb += 4; }},
+    {"sVb", [](AttnOperands &t) { t.sVb += 4; }},   {"sOb", [](AttnOperands &t) { t.sOb += 2; }},
+    {"Q_ptr", [](AttnOperands &t) { t.Q = (const char *)t.Q + 8; }},
+    {"O_ptr", [](AttnOperands &t) { t.O = (char *)t.O + 4; }},
+};
+
+static void plan_cases() {
+    const int F16 = PIO_DT_F16, BF16 = PIO_DT_BF16;
+    char id[64];
+    // ---- self-attention kernel: one plan per instantiation group of flash_launch
+    fplan("vt_4_1", F16, 32, 160, 2, 8, 256, 256, false);
+    fplan("row_4_1", F16, 128, 128, 1, 8, 512, 500, true);
+    fplan("row_8_1", BF16, 128, 128, 32, 8, 512, 512, true);
+    fplan("row_8_2", F16, 128, 128, 1, 8, 512, 512, true);
+    fplan("row_16_4", F16, 32, 32, 1, 16, 2048, 2048, true);
+    fplan("pair_128_no_key_split", F16, 128, 128, 1, 8, 512, 512, true, as_pair);
+    fplan("pair_32_key_split", F16, 32, 32, 1, 16, 2048, 2048, true, as_pair);
+    fplan("rows16_off_ldo", F16, 128, 128, 1, 8, 512, 512, true, [](AttnOperands &t) { t.ldo += 4; });
+    fplan("rows16_off_O_ptr", F16, 128, 128, 1, 8, 512, 512, true, [](AttnOperands &t) { t.O = (char *)t.O + 8; });
+    fplan("rows16_off_O_lo", F16, 128, 128, 1, 8, 512, 512, true, [](AttnOperands &t) { as_pair(t); t.O_lo = LO; });
+    fplan("no_shape", F16, 64, 128, 1, 8, 512, 512, true);
+    fplan("no_Q", F16, 128, 128, 1, 8, 512, 512, true, [](AttnOperands &t) { t.Q = nullptr; });
+    fplan("no_VT", F16, 128, 128, 1, 8, 512, 512, true, [](AttnOperands &t) { t.VT = nullptr; });
+    fplan("Q_lo_alone", F16, 128, 128, 1, 8, 512, 512, true, [](AttnOperands &t) { t.Q_lo = LO; });
+    fplan("O_lo_without_pair", F16, 128, 128, 1, 8, 512, 512, true, [](AttnOperands &t) { t.O_lo = LO; });
+    fplan("pair_64", F16, 64, 64, 1, 8, 512, 512, true, as_pair);
+    fplan("pair_bf16", BF16, 32, 32, 1, 8, 512, 512, true, as_pair);
+    fplan("no_batch", F16, 128, 128, 0, 8, 512, 512, true);
+    fplan("no_keys", F16, 128, 128, 1, 8, 512, 0, true);
+    fplan("grid_overflow", F16, 32, 32, 1 << 20, 1 << 10, 512, 512, true);
+    for (const auto &m : MISALIGNED) {
+        snprintf(id, sizeof id, "misaligned_%s", m.name);
+        fplan(id, F16, 128, 128, 1, 8, 512, 512, true, m.edit);
+    }
+    fplan("no_shape_before_no_Q", F16, 64, 128, 1, 8, 512, 512, true, [](AttnOperands &t) { t.Q = nullptr; });
+    fplan("O_lo_without_pair_before_misaligned", F16, 128, 128, 1, 8, 512, 512, true, [](AttnOperands &t) { t.O_lo = LO; t.ldq += 4; });
+    fplan("no_batch_before_misaligned", F16, 128, 128, 0, 8, 512, 512, true, [](AttnOperands &t) { t.ldq += 4; });
+    // ---- cross-attention kernel: one plan per XCfg, a key split, a mask
+    xplan("cfg_32_96", F16, 32, 96, 2, 8, 256, 256, false, false);
+    xplan("cfg_32_160_pair", F16, 32, 160, 2, 8, 256, 256, false, false, as_pair);
+    xplan("cfg_128_128", BF16, 128, 128, 2, 8, 256, 256, false, false);
+    xplan("cfg_352_352", F16, 328, 328, 2, 1, 256, 256, false, false);
+    xplan("cfg_512_512", F16, 512, 512, 2, 1, 256, 256, false, false);
+    xplan("cfg_704_256_sliced", F16, 704, 704, 2, 1, 256, 256, false, false);
+    xplan("key_split_flow_encoder", F16, 328, 328, 1, 1, 2048, 182528, false, true);
+    xplan("masked_language_encoder", F16, 32, 160, 2, 8, 256, 2048, true, true);
+    xplan("no_cfg", F16, 1024, 1024, 2, 1, 256, 256, false, false);
+    xplan("no_K", F16, 32, 96, 2, 8, 256, 256, false, false, [](AttnOperands &t) { t.K = nullptr; });
+    xplan("no_VT", F16, 32, 96, 2, 8, 256, 256, false, false, [](AttnOperands &t) { t.VT = nullptr; });
+    xplan("K_lo_alone", F16, 32, 96, 2, 8, 256, 256, false, false, [](AttnOperands &t) { t.K_lo = LO; });
+    xplan("pair_128", F16, 128, 128, 2, 8, 256, 256, false, false, as_pair);
+    xplan("pair_bf16", BF16, 32, 96, 2, 8, 256, 256, false, false, as_pair);
+    xplan("no_keys", F16, 32, 96, 2, 8, 256, 0, false, false);
+    xplan("dkp_not_padded", F16, 36, 96, 2, 8, 256, 256, false, false);
+    for (const auto &m : MISALIGNED) {
+        snprintf(id, sizeof id, "misaligned_%s", m.name);
+        xplan(id, F16, 32, 96, 2, 8, 256, 256, false, false, m.edit);
+    }
+    xplan("ldvt_below_8", F16, 32, 96, 2, 8, 256, 256, false, false, [](AttnOperands &t) { t.ldvt = 0; });
+    xplan("ldk_offset_limit", F16, 32, 96, 2, 8, 256, 256, false, false, [](AttnOperands &t) { t.ldk = 1ll << 26; });
+    xplan("ldvt_offset_limit", F16, 512, 512, 2, 1, 256, 256, false, false, [](AttnOperands &t) { t.ldvt = 1ll << 22; });
+    xplan("mask_without_scratch", F16, 32, 160, 2, 8, 256, 256, true, false);
+    xplan("split_without_scratch", F16, 328, 328, 1, 1, 2048, 182528, false, false);
+    xplan("ldvt_not_whole_tiles", F16, 32, 96, 2, 8, 256, 256, false, false, [](AttnOperands &t) { t.ldvt = 264; });
+    xplan("grid_overflow", F16, 32, 96, 1 << 20, 1 << 10, 256, 256, false, false);
+    xplan("no_scratch_before_ldvt_tiles", F16, 32, 160, 2, 8, 256, 256, true, false, [](AttnOperands &t) { t.ldvt = 264; });
+    xplan("pair_128_before_misaligned", F16, 128, 128, 2, 8, 256, 256, false, false, [](AttnOperands &t) { as_pair(t); t.ldq += 4; });
+    xplan("ldk_limit_before_no_scratch", F16, 32, 160, 2, 8, 256, 256, true, false, [](AttnOperands &t) { t.ldk = 1ll << 26; });
+    // ---- tall-head kernel
+    tplan("one_pass", 64, 256, 2, 2, 200, 100, false, false);
+    tplan("imagenet_decoder_four_passes", 1024, 1024, 8, 1, 1000, 512, true, true);
+    tplan("too_many_keys", 1024, 1024, 8, 1, 1000, 520, false, false);
+    tplan("pair", 1024, 1024, 8, 1, 1000, 512, false, false, as_pair);
+    tplan("no_O", 1024, 1024, 8, 1, 1000, 512, false, false, [](AttnOperands &t) { t.O = nullptr; });
+    tplan("no_VT", 1024, 1024, 8, 1, 1000, 512, false, false, [](AttnOperands &t) { t.VT = nullptr; });
+    tplan("no_queries", 1024, 1024, 8, 1, 0, 512, false, false);
+    for (const auto &m : MISALIGNED) {
+        snprintf(id, sizeof id, "misaligned_%s", m.name);
+        tplan(id, 1024, 1024, 8, 1, 1000, 512, false, false, m.edit);
+    }
+    tplan("ldvt_below_64", 1024, 1024, 8, 1, 1000, 512, false, false, [](AttnOperands &t) { t.ldvt = 32; });
+    tplan("ldk_offset_limit", 1024, 1024, 8, 1, 1000, 512, false, false, [](AttnOperands &t) { t.ldk = 1ll << 22; });
+    tplan("ldq_offset_limit", 1024, 1024, 8, 1, 1024, 512, false, false, [](AttnOperands &t) { t.ldq = 1ll << 21; });
+    tplan("ldvt_offset_limit", 1024, 1024, 8, 1, 1000, 512, false, false, [](AttnOperands &t) { t.ldvt = 1ll << 23; });
+    tplan("mask_without_scratch", 1024, 1024, 8, 1, 1000, 512, true, false);
+    tplan("grid_overflow", 64, 256, 1 << 20, 1 << 11, 128, 512, false, false);
+    tplan("Q_lo_alone_is_a_shape", 1024, 1024, 8, 1, 1000, 512, false, false, [](AttnOperands &t) { t.Q_lo = LO; });
+    tplan("ldvt_below_64_before_no_scratch", 1024, 1024, 8, 1, 1000, 512, true, false, [](AttnOperands &t) { t.ldvt = 32; });
+    tplan("no_O_before_no_queries", 1024, 1024, 8, 1, 0, 512, false, false, [](AttnOperands &t) { t.O = nullptr; });
+}
 int main() {
     cases();
     split_cases();
     flash_cases();
+    plan_cases();
     return 0;
 }
 '''
@@ -238,6 +383,118 @@ FLASH = {
     "v_transposed_b32": ("V^T", 4, 1, 4, 256),
 }
 
+# flash_launch_plan at 256 CUs, key split on: V layout, NW, KS, query tiles, pair, o_rows16, grid -- or the refusal.
+# Expected values read off flash_attention_launch as it stood before the plan existed: flash_supported, operands
+# present, O_lo without a pair, pair support, extents and grid, alignment -- in that order.
+FPLAN = {
+    "vt_4_1": ("V^T", 4, 1, 2, 0, 1, 32),
+    "row_4_1": ("row", 4, 1, 4, 0, 1, 32),
+    "row_8_1": ("row", 8, 1, 2, 0, 1, 512),
+    "row_8_2": ("row", 8, 2, 4, 0, 1, 32),
+    "row_16_4": ("row", 16, 4, 16, 0, 1, 256),
+    "pair_128_no_key_split": ("row", 4, 1, 4, 1, 1, 32),
+    "pair_32_key_split": ("row", 16, 4, 16, 1, 1, 256),
+    "rows16_off_ldo": ("row", 8, 2, 4, 0, 0, 32),
+    "rows16_off_O_ptr": ("row", 8, 2, 4, 0, 0, 32),
+    "rows16_off_O_lo": ("row", 4, 1, 4, 1, 0, 32),
+    "no_shape": "PIO_E_SHAPE",
+    "no_Q": "PIO_E_ARG",
+    "no_VT": "PIO_E_ARG",
+    "Q_lo_alone": "PIO_E_ARG",
+    "O_lo_without_pair": "PIO_E_ARG",
+    "pair_64": "PIO_E_SHAPE",
+    "pair_bf16": "PIO_E_SHAPE",
+    "no_batch": "PIO_E_SHAPE",
+    "no_keys": "PIO_E_SHAPE",
+    "grid_overflow": "PIO_E_SHAPE",
+    "misaligned_ldq": "PIO_E_ALIGN",
+    "misaligned_ldk": "PIO_E_ALIGN",
+    "misaligned_ldvt": "PIO_E_ALIGN",
+    "misaligned_ldo": "PIO_E_ALIGN",
+    "misaligned_sQb": "PIO_E_ALIGN",
+    "misaligned_sKb": "PIO_E_ALIGN",
+    "misaligned_sVb": "PIO_E_ALIGN",
+    "misaligned_sOb": "PIO_E_ALIGN",
+    "misaligned_Q_ptr": "PIO_E_ALIGN",
+    "misaligned_O_ptr": "PIO_E_ALIGN",
+    "no_shape_before_no_Q": "PIO_E_SHAPE",
+    "O_lo_without_pair_before_misaligned": "PIO_E_ARG",
+    "no_batch_before_misaligned": "PIO_E_SHAPE",
+}
+
+# xattn_launch_plan: XCfg (dkl, dvs), pair, nqt, nslice, nsplit, ntiles, tiles_per_split, grid, byte offsets of part_o /
+# part_ml in the scratch -- or the refusal.  Order in xattn_launch: cfg, operands present, pair support, extents and
+# padded widths, alignment, the 32-bit offset limits, scratch, ldvt % 32, grid.
+XPLAN = {
+    "cfg_32_96": (32, 96, 0, 2, 1, 1, 8, 8, 32, 256, 1573120),
+    "cfg_32_160_pair": (32, 160, 1, 2, 1, 1, 8, 8, 32, 256, 2621696),
+    "cfg_128_128": (128, 128, 0, 2, 1, 1, 8, 8, 32, 256, 2097408),
+    "cfg_352_352": (352, 352, 0, 2, 1, 1, 8, 8, 4, 256, 672000),
+    "cfg_512_512": (512, 512, 0, 2, 1, 1, 8, 8, 4, 256, 1048832),
+    "cfg_704_256_sliced": (704, 256, 0, 2, 3, 1, 8, 8, 12, 256, 1442048),
+    "key_split_flow_encoder": (352, 352, 0, 16, 1, 16, 5704, 357, 256, 23040, 43014656),
+    "masked_language_encoder": (32, 160, 0, 2, 1, 8, 64, 8, 256, 512, 20972032),
+    "no_cfg": "PIO_E_SHAPE",
+    "no_K": "PIO_E_ARG",
+    "no_VT": "PIO_E_ARG",
+    "K_lo_alone": "PIO_E_ARG",
+    "pair_128": "PIO_E_SHAPE",
+    "pair_bf16": "PIO_E_SHAPE",
+    "no_keys": "PIO_E_SHAPE",
+    "dkp_not_padded": "PIO_E_SHAPE",
+    "misaligned_ldq": "PIO_E_ALIGN",
+    "misaligned_ldk": "PIO_E_ALIGN",
+    "misaligned_ldvt": "PIO_E_ALIGN",
+    "misaligned_ldo": "PIO_E_ALIGN",
+    "misaligned_sQb": "PIO_E_ALIGN",
+    "misaligned_sKb": "PIO_E_ALIGN",
+    "misaligned_sVb": "PIO_E_ALIGN",
+    "misaligned_sOb": "PIO_E_ALIGN",
+    "misaligned_Q_ptr": "PIO_E_ALIGN",
+    "misaligned_O_ptr": "PIO_E_ALIGN",
+    "ldvt_below_8": "PIO_E_SHAPE",
+    "ldk_offset_limit": "PIO_E_SHAPE",
+    "ldvt_offset_limit": "PIO_E_SHAPE",
+    "mask_without_scratch": "PIO_E_WORKSPACE",
+    "split_without_scratch": "PIO_E_WORKSPACE",
+    "ldvt_not_whole_tiles": "PIO_E_ALIGN",
+    "grid_overflow": "PIO_E_SHAPE",
+    "no_scratch_before_ldvt_tiles": "PIO_E_WORKSPACE",
+    "pair_128_before_misaligned": "PIO_E_SHAPE",
+    "ldk_limit_before_no_scratch": "PIO_E_SHAPE",
+}
+
+# xtall_launch_plan: nqt, nka, npass, grid -- or the refusal.  Order in xtall_launch: shape / pair operands, operands
+# present, extents, alignment, ldvt and the 32-bit offset limits, scratch, grid.
+TPLAN = {
+    "one_pass": (2, 2, 1, 8),
+    "imagenet_decoder_four_passes": (8, 32, 4, 64),
+    "too_many_keys": "PIO_E_SHAPE",
+    "pair": "PIO_E_SHAPE",
+    "no_O": "PIO_E_ARG",
+    "no_VT": "PIO_E_ARG",
+    "no_queries": "PIO_E_SHAPE",
+    "misaligned_ldq": "PIO_E_ALIGN",
+    "misaligned_ldk": "PIO_E_ALIGN",
+    "misaligned_ldvt": "PIO_E_ALIGN",
+    "misaligned_ldo": "PIO_E_ALIGN",
+    "misaligned_sQb": "PIO_E_ALIGN",
+    "misaligned_sKb": "PIO_E_ALIGN",
+    "misaligned_sVb": "PIO_E_ALIGN",
+    "misaligned_sOb": "PIO_E_ALIGN",
+    "misaligned_Q_ptr": "PIO_E_ALIGN",
+    "misaligned_O_ptr": "PIO_E_ALIGN",
+    "ldvt_below_64": "PIO_E_SHAPE",
+    "ldk_offset_limit": "PIO_E_SHAPE",
+    "ldq_offset_limit": "PIO_E_SHAPE",
+    "ldvt_offset_limit": "PIO_E_SHAPE",
+    "mask_without_scratch": "PIO_E_WORKSPACE",
+    "grid_overflow": "PIO_E_SHAPE",
+    "Q_lo_alone_is_a_shape": "PIO_E_SHAPE",
+    "ldvt_below_64_before_no_scratch": "PIO_E_SHAPE",
+    "no_O_before_no_queries": "PIO_E_ARG",
+}
+
 
 def _run_driver():
     inc = os.path.join(ROOT, "include")
@@ -248,7 +505,7 @@ def _run_driver():
         exe = os.path.join(d, "route")
         subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", inc, "-I", csrc, src, "-o", exe])
         out = subprocess.check_output([exe]).decode().split("\n")
-    got = {"route": {}, "splits": {}, "flash": {}}
+    got = {"route": {}, "splits": {}, "flash": {}, "fplan": {}, "xplan": {}, "tplan": {}}
     for line in filter(None, out):
         f = line.split()
         vals = tuple(int(x) if x.isdigit() else x for x in f[2:])
@@ -287,6 +544,18 @@ def test_key_splits_and_partials():
 
 def test_flash_route_table():
     assert _got()["flash"] == FLASH
+
+
+def test_flash_launch_plans():
+    assert _got()["fplan"] == FPLAN
+
+
+def test_xattn_launch_plans():
+    assert _got()["xplan"] == XPLAN
+
+
+def test_xtall_launch_plans():
+    assert _got()["tplan"] == TPLAN
 
 
 def test_header_is_host_only():

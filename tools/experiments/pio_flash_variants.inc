@@ -34,9 +34,7 @@ __global__ __launch_bounds__(512, 1) void flash_attn_stag_kernel(const FlashPara
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r32 = lane & 31, hh = lane >> 5;
-    int bid = blockIdx.x;
-    const int nblk = gridDim.x;
-    if ((nblk & 7) == 0) bid = (bid & 7) * (nblk >> 3) + (bid >> 3);
+    const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int qt = bid % p.nqt, bh = bid / p.nqt;
     const int b = bh / p.H, h = bh % p.H;
     const int q0 = qt * (NW * 32) + wave * 32;
@@ -155,7 +153,7 @@ __global__ __launch_bounds__(512, 1) void flash_attn_stag_kernel(const FlashPara
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[t][i]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * p.scale_log2;
+        mx = max_halves(mx) * p.scale_log2;
         const float m_new = fmaxf(m_run, mx);
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
         m_run = m_new;
@@ -333,20 +331,17 @@ extern "C" int pio_debug_flash_mode(void) { return PIO_FLASH_ABL; }
 template <int DT>
 __device__ __forceinline__ void fp_mfma_s0(f32x16 &c, typename Op<DT>::V8 a, typename Op<DT>::V8 b) {  // c = a b, b in AGPRs
     if constexpr (PIO_FLASH_ABL & 4) asm volatile("; no mfma %0 %1 %2" : "=&v"(c) : "v"(a), "a"(b));
-    else if constexpr (DT == PIO_DT_F16) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "a"(b));
-    else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "a"(b));
+    else mfma32_asm<DT, false, true, true>(c, a, b);
 }
 template <int DT>
 __device__ __forceinline__ void fp_mfma_s(f32x16 &c, typename Op<DT>::V8 a, typename Op<DT>::V8 b) {  // c += a b
     if constexpr (PIO_FLASH_ABL & 4) asm volatile("; no mfma %0 %1 %2" : "+v"(c) : "v"(a), "a"(b));
-    else if constexpr (DT == PIO_DT_F16) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "a"(b));
-    else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "a"(b));
+    else mfma32_asm<DT, false, true>(c, a, b);
 }
 template <int DT>
 __device__ __forceinline__ void fp_mfma_o(f32x16 &c, typename Op<DT>::V8 a, typename Op<DT>::V8 b) {  // acc in AGPRs
     if constexpr (PIO_FLASH_ABL & 4) asm volatile("; no mfma %0 %1 %2" : "+a"(c) : "v"(a), "v"(b));
-    else if constexpr (DT == PIO_DT_F16) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-    else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
+    else mfma32_asm<DT, true>(c, a, b);
 }
 
 // LDS fragment reads as inline assembly, waited for by hand (s_waitcnt lgkmcnt(N) below; LDS returns in order).  Two
@@ -394,9 +389,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pipe_kernel(const FlashPara
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r32 = lane & 31, hh = lane >> 5;
-    int bid = blockIdx.x;
-    const int nblk = gridDim.x;
-    if ((nblk & 7) == 0) bid = (bid & 7) * (nblk >> 3) + (bid >> 3);
+    const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
     const int qt = bid % p.nqt, bh = bid / p.nqt;
     const int b = bh / p.H, h = bh % p.H;
     const int q0 = qt * 256 + wave * 64;
@@ -510,10 +503,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pipe_kernel(const FlashPara
             for (int d = 0; d < 4; ++d) {
 #pragma unroll
                 for (int j = 0; j < 16; ++j) {
-                    float v;
-                    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(oacc[X][d][j]));
-                    v *= alpha;
-                    asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(oacc[X][d][j]) : "v"(v));
+                    oacc[X][d][j] = acc_write_ordered(acc_read_ordered(oacc[X][d][j]) * alpha);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -676,13 +666,7 @@ __global__ __launch_bounds__(256, 1) void flash_attn_pipe_kernel(const FlashPara
     stage(1, 1);
     // Q fragments: lane holds Q[q0 + 32 X + r32][16 s + 8 hh + 0..7] (their latency overlaps the tiles')
 #pragma unroll
-    for (int X = 0; X < 2; ++X) {
-        int q = q0 + 32 * X + r32;
-        q = q < p.Tq ? q : p.Tq - 1;
-        const T *qrow = Qg + (int64_t)q * p.ldq + 8 * hh;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) qf[X][s] = *(const V8 *)(qrow + 16 * s);
-    }
+    for (int X = 0; X < 2; ++X) load_q_frags<DT>(qf[X], Qg, q0 + 32 * X + r32, p.Tq, p.ldq, hh);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     PIO_FSTAMP_K(10);
